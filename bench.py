@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- merge-path throughput of the MI355X engine (BASELINE.json metric: "Gbp/sec indexed (build merge)").
 
-HEADLINE (value, ms_per_step, config.workload, roofline, cpu_baseline) = BASELINE configs[2], the north_star's target:
+HEADLINE (value, ms_per_step, config.workload, roofline; cpu_baseline with --full) = BASELINE configs[2], the north_star's target:
 **mtb152**, 152 synthetic M. tuberculosis-like genomes of 4.4 Mbp (tools/gen_mtb.py: star phylogeny, 0.1 % substitutions +
 10 indels each), one genome per batch as the reference is run = 151 merge rounds, 1,328,837,368 symbols merged.
 
@@ -10,24 +10,30 @@ metric -- per round the H2D copy of the batch (its nt6 text, from page-locked me
 interleave/rebuild, summed over the 151 rounds; suffix sorting of the batch (the reference's libsais call, excluded by the
 metric's definition) runs on the GPU between the two timed parts of a round and is not counted; file I/O happens before the
 timed region.  Every timed part is bracketed by host clocks with the device idle on both sides (the upload returns after its
-stream synchronisation, a merge ends with its one synchronisation).  After the last step the index is packed into an .fmd
+stream synchronisation, a merge ends with its one synchronisation).  With --full, the index is then packed into an .fmd
 on the GPU and its md5 is compared with the one the UNMODIFIED REFERENCE produced for the same 152 files
 (tests/golden/MANIFEST.json, tools/make_golden_mtb.py): `fmd_identical_to_reference`.
 
-The same JSON line also carries: `roofline` (dominant kernel k_chain<mixed>: 208 B x LF steps / its HIP-event time; traffic
-from the committed rocprofv3 --pmc passes), `roofline_path` (SURVEY 8(d)'s whole-path formula), `cpu_baseline` (the unmodified
-reference binary timed here on a stated prefix of the same files), and auxiliary legs, each labelled: the whole build through
-the CLI (sorting overlapped, wall clock), BASELINE configs[1] (one genome into one: the former headline), the reads regime and
-the HBM-resident large index.
+A plain run sets up, warms up, times the steps and prints the line, which also carries `roofline` (dominant kernel
+k_chain<mixed>: 208 B x LF steps / its HIP-event time over the timed steps; traffic from the committed rocprofv3 --pmc passes)
+and `roofline_path` (SURVEY 8(d)'s whole-path formula).  `--full` adds everything that takes work of its own: the md5 gate
+above, the H2D copies with nothing beside them, `cpu_baseline` (the unmodified reference binary timed here on a stated prefix
+of the same files), and auxiliary legs, each labelled: the build through the reference's signature, whole-index merges, the
+whole build through the CLI (sorting overlapped, wall clock), BASELINE configs[1] (one genome into one: the former headline),
+the reads regime, the HBM-resident large index and the index beyond 2^32 symbols.  `--only LEG` runs one leg with all of that.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step built -- the index in the handle -- as .npy files
+(dump_outputs): a fixed, seeded sample of it, so that two builds of the project can be compared output for output.
 
 N > 1 (python bench.py --gpus N starts its N ranks itself; under torch.distributed.run it uses the ranks it is given): the SAME
 build, partitioned -- rank r builds the index of its contiguous slice of the 152 genomes, then the slices are combined by a
 binary tree of whole-index merges over RCCL (ropebwt3_amd/multi.py); one step = the whole partitioned build, same md5 gate,
 `scaling` = "strong" (the job is fixed: one mtb152 index).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 import argparse
+import atexit
 import hashlib
 import json
 import os
@@ -366,6 +372,26 @@ class BuildLoop:
         self.h.close()
 
 
+DUMP_SAMPLE = 1 << 19   # positions of the final index that --dump-outputs samples: about 31 MB of .npy files
+
+
+def dump_outputs(h, out_dir):
+    """--dump-outputs: the index the last timed step left in the handle, as float .npy files in out_dir -- its C array (acc.npy:
+    where each symbol's rows begin) and, at a fixed, seeded sample of positions k (sample_pos.npy), the BWT symbol at k
+    (bwt_sample.npy) and the occurrences of every symbol before k (occ_sample.npy), read back through rb3gpu_rank1a_batch.
+    The positions depend on the index length alone, so the same arguments give the same files for any correct build."""
+    n = h.get_tot()
+    k = np.unique(np.concatenate([np.random.default_rng(20260).integers(0, n, size=DUMP_SAMPLE), [0, n - 1]]))
+    occ = h.rank1a(np.concatenate([k, k + 1]))
+    before, step = occ[:k.size], occ[k.size:] - occ[:k.size]
+    if not np.all(step.sum(axis=1) == 1):
+        raise RuntimeError("rb3gpu_rank1a_batch: ranks at k and k + 1 differ by other than one symbol")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("acc", h.get_acc().astype(np.float64)), ("sample_pos", k.astype(np.float64)),
+                    ("bwt_sample", np.argmax(step, axis=1).astype(np.float32)), ("occ_sample", before.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def reference_prefix(files, n_ref, K):
     """cpu_baseline of the headline: the UNMODIFIED reference binary (oracle/_ref/ropebwt3, built by oracle/Makefile from the
     sources under /root/reference; it travels with the repository) on the first n_ref of the same files, merge-only seconds by
@@ -563,7 +589,13 @@ def main():
     ap.add_argument("--mtb-3b-batch", type=int, default=16, help="cpu_baseline_config3b: genomes concatenated into the ONE merged batch (0 = skip)")
     ap.add_argument("--walker-step", type=int, default=WALKER_STEP)
     ap.add_argument("--host-walkers", action="store_true", help="make the walker lists on the host before the timed steps (rb3h_walkers_text, rounds 2-4) instead of on the device inside the merge call")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the timed steps also run everything beyond the headline figure (the md5 gate, the H2D copies alone, the CPU baselines, the auxiliary legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="N = 1: after the timed steps write what the last step built (a seeded sample of the index, dump_outputs) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.mode is not None or args.scale or args.only not in (None, "headline")):
+        ap.error("--dump-outputs writes the index of the single-GPU headline build: not with --gpus N > 1, --mode, --scale or another --only leg")
     if args.scale:   # (a recorded-run script, run now: its JSON object is the line)
         r = subprocess.run(["bash", os.path.join(ROOT, "tools", "r6", "scale_reads.sh" if args.scale == "reads" else "scale_hap.sh")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT)
         lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -585,16 +617,19 @@ def main():
             emit_json({"selftest": "launch", "n_gpus": args.gpus, "world": world})
         return
 
-    import torch
-    from ropebwt3_amd import Rb3Gpu
-
-    if not torch.cuda.is_available():
-        sys.exit("bench.py needs an MI355X: torch.cuda.is_available() is False and the engine has no CPU fallback")
     if world > 1 or args.mode is not None:
+        if args.dump_outputs:
+            sys.exit("--dump-outputs writes the index of the single-GPU headline build: not with %d ranks" % world)
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("bench.py needs an MI355X: torch.cuda.is_available() is False and the engine has no CPU fallback")
         from ropebwt3_amd import multi
         args.mode = args.mode or "partition"
         return multi.bench_main(args, rank, local_rank, world)
-    torch.cuda.set_device(local_rank)
+    # one GPU: everything goes through the engine's C ABI, so torch (seconds of start-up) is not imported
+    from ropebwt3_amd import Rb3Gpu, gpu
+    if gpu.load_library().rb3gpu_device_count() < 1:
+        sys.exit("bench.py needs an MI355X: no HIP device is visible and the engine has no CPU fallback")
     mk = lambda: Rb3Gpu(device=local_rank, verbose=1)
     if args.only == "8g":
         emit_json(index_8g(args.index_8g, local_rank))
@@ -607,6 +642,8 @@ def main():
     K, L = args.mtb, args.genome_len
     gold = mtb_manifest(K, L)
     tmp, files, t_gen = mtb_files(K, L)
+    atexit.register(shutil.rmtree, tmp, True)
+    full = args.full or args.only == "headline"   # (--only headline: the headline leg with everything --full adds to it)
     if args.only == "cli":
         emit_json(cli_build(files, K, gold))
         return
@@ -621,7 +658,6 @@ def main():
     for _ in range(args.warmup):
         bl.run(texts, walkers)
     bl.h.sync()
-    torch.cuda.synchronize()
     bl.h.stats_reset()
     tot_h2d = tot_mrg = tot_sort = tot_wall = 0.0
     nsym = 0
@@ -629,19 +665,24 @@ def main():
         a, b, c, n, w = bl.run(texts, walkers)
         tot_h2d, tot_mrg, tot_sort, tot_wall, nsym = tot_h2d + a, tot_mrg + b, tot_sort + c, tot_wall + w, nsym + n
     bl.h.sync()
-    torch.cuda.synchronize()
     st = bl.h.stats()
-    h2d_serial = None
-    if bl.overlap:   # for the record: the same copies with nothing beside them (one more build, not part of the timed steps)
+    if args.dump_outputs:   # (before anything below builds the index again)
+        dump_outputs(bl.h, args.dump_outputs)
+    h2d_serial = md5 = fmd_len = ident = None
+    if full and bl.overlap:   # for the record: the same copies with nothing beside them (one more build, not part of the timed steps)
         bl.overlap = False
         h2d_serial = bl.run(texts, walkers)[0]
         bl.overlap = True
-    md5, fmd_len = bl.fmd_md5()
+    if full:
+        md5, fmd_len = bl.fmd_md5()
+        ident = (md5 == gold["fmd_md5"]) if gold else None
+        if ident is False:
+            log("ERROR: the .fmd differs from the reference's (md5 %s vs %s)" % (md5, gold["fmd_md5"]))
     # the same 151 rounds through the REFERENCE'S signature -- rb3gpu_merge_plain_dev gets the partial BWT and nothing else
     # (rb3_fmi_merge_plain, fm-index.c:279), so the walkers of the long strings come from a sparse LF walk of the batch itself and the walk reads
     # row words instead of streaming the inverse suffix array: what not having the sorter's products costs on the headline workload
     refsig = None
-    if not args.no_aux:
+    if full and not args.no_aux:
         try:
             bl.run(texts, walkers, reference_signature=True)
             bl.h.sync()
@@ -660,7 +701,7 @@ def main():
     # merged into the index of the first half, both resident in HBM -- rb3gpu_merge_index(a, b): b's BWT expanded to 1 byte per symbol, walked
     # through the reference's signature (VERDICT r4 item 8 asks for a walk that ranks on b's block array instead: not built)
     mrg_idx = None
-    if not args.no_aux and K >= 4:
+    if full and not args.no_aux and K >= 4:
         try:
             half = K // 2
             la, lb = BuildLoop(local_rank), BuildLoop(local_rank)
@@ -682,9 +723,6 @@ def main():
             la.close(), lb.close()
         except Exception as e:
             mrg_idx = {"error": repr(e)[:300]}
-    ident = (md5 == gold["fmd_md5"]) if gold else None
-    if ident is False:
-        log("ERROR: the .fmd differs from the reference's (md5 %s vs %s)" % (md5, gold["fmd_md5"]))
     S = args.steps
     dt = tot_h2d + tot_mrg
     sym_step = nsym // S
@@ -722,6 +760,9 @@ def main():
                              "achieved": round(st["bytes_rebuild"] / max(1e-9, st["ms_build"]) / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(st["bytes_rebuild"] / max(1e-9, st["ms_build"]) / 1e6 / HBM_PEAK_GBS, 5),
                              "note": "streaming roofline: 9 B per batch row + old block array + new block array per round"},
     }
+    if not full:   # (the md5 gate is one of --full's extras)
+        for k in ("fmd_md5", "fmd_bytes", "fmd_identical_to_reference", "reference_fmd_md5_source"):
+            del out["config"][k]
     if refsig is not None:
         out["aux_mtb152_reference_signature"] = refsig
     if mrg_idx is not None:
@@ -730,7 +771,7 @@ def main():
     if args.only == "headline":
         emit_json(out)
         return
-    if not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         cb = reference_prefix(files, args.mtb_ref_prefix, K)
         if cb is None:   # the reference binary did not travel: the OpenMP port of the oracle on one round
             from ropebwt3_amd import host
@@ -747,7 +788,7 @@ def main():
             cb3 = reference_many_chains(files, args.mtb_3b_first, args.mtb_3b_batch)
             if cb3 is not None:
                 out["cpu_baseline_config3b"] = cb3
-    if not args.no_aux:
+    if full and not args.no_aux:
         out["aux_cli_build"] = cli_build(files, K, gold)
         # everything around the metric in one place
         out["end_to_end"] = {"in_process_loop_wall_ms_per_build": out["not_counted_ms_per_step"]["wall_of_the_whole_loop"],
@@ -786,15 +827,6 @@ def main():
                 pass
         if rec:
             out["scale_runs_recorded"] = rec
-    for f in files:
-        try:
-            os.unlink(f)
-        except OSError:
-            pass
-    try:
-        os.rmdir(tmp)
-    except OSError:
-        pass
     emit_json(out)
 
 

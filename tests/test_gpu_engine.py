@@ -1734,18 +1734,101 @@ def test_interval_sharded_merge_peer_rounds_between_processes(world):
     assert all(r[1] for r in res), res
 
 
-@pytest.mark.parametrize("world,ipc", [(8, False), (8, True)])
+class _GlooGroup:
+    """the torch.distributed calls of the gloo callbacks (all_gather, send, recv) on a gloo group of one rank's own: a process can host several ranks"""
+
+    def __init__(self, store, rank, world):
+        import torch.distributed as dist
+        self.pg = dist.ProcessGroupGloo(dist.PrefixStore("rb3_text", store), rank, world)
+
+    def all_gather(self, out, t):
+        self.pg.allgather([out], [t]).wait()
+
+    def send(self, t, dst):
+        self.pg.send([t], dst, 0).wait()
+
+    def recv(self, t, src):
+        self.pg.recv([t], src, 0).wait()
+
+
+def _text_ranks_worker(ranks, world, port, q, n_reads):
+    """ranks `ranks` of rb3gpu_sh_merge_text between processes, a thread each with an engine handle (and so a stream) and a gloo group of its
+    own: the case and the callbacks of tools/probe_gloo_text.worker"""
+    import sys
+    import threading
+    from datetime import timedelta
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    import torch.distributed as dist
+    from ropebwt3_amd import Rb3Gpu, CallbackComm, multi, host
+    orc = util.Oracle()
+    rng = np.random.default_rng(99)   # the same case in every process
+    g0 = util.random_genome(rng, 300000)
+    cur = host.build_bwt(util.make_text([g0]))
+    t2 = util.make_text(util.reads_from(rng, g0, n_reads, 75, err=0.01))
+    want = orc.merge(cur, host.build_bwt(t2.copy()))
+    stores = {}
+
+    def run(rank):
+        try:
+            stores[rank] = dist.TCPStore("127.0.0.1", port, world, rank == 0, timedelta(seconds=300), wait_for_workers=False)   # (rank 0's serves)
+            g = _GlooGroup(stores[rank], rank, world)
+            bounds = multi.interval_bounds(cur.size, world)
+            h = Rb3Gpu(verbose=1)
+
+            def all_gather(vec):
+                out = [torch.zeros(len(vec), dtype=torch.int64) for _ in range(world)]
+                g.all_gather(out, torch.from_numpy(np.ascontiguousarray(vec, dtype=np.int64)))
+                return torch.stack(out).numpy()
+
+            def exchange(d_send, stride, send_cnt, d_recv, recv_cnt):   # synchronous copies out of the send regions, right behind the kernel that fills them
+                parts = []
+                for d in range(world):
+                    n = int(send_cnt[d])
+                    parts.append(torch.from_numpy(h.dev_download_i64(d_send + d * stride * 16, n * 2)) if n else torch.zeros(0, dtype=torch.int64))
+                recv = [torch.zeros(int(recv_cnt[s]) * 2, dtype=torch.int64) for s in range(world)]
+                _gloo_all_to_all(g, rank, world, parts, recv)
+                got = torch.cat(recv).numpy()
+                if got.size:
+                    h.dev_upload_to(d_recv, got)
+
+            comm = CallbackComm(rank, world, all_gather, exchange)
+            h.from_plain(cur[bounds[rank]:bounds[rank + 1]])
+            d_bwt, d_tw = h.sort_text(t2)
+            n2 = t2.size
+            t_lo = n2 // world * rank + (n2 % world) * rank // world
+            d_tprev = h.tprev_from_tw(d_tw, n2)
+            bounds, _ = h.sh_merge_text(comm, bounds, d_tprev, d_tw.value + t_lo * 8, n2, np.flatnonzero(t2 == 0))
+            _check_interval(h, np.random.default_rng(rank), want, bounds, rank)
+            h.close()
+            q.put((rank, True, ""))
+        except BaseException as e:
+            q.put((rank, False, repr(e)))
+
+    th = [threading.Thread(target=run, args=(r,)) for r in ranks]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=600)
+
+
+@pytest.mark.parametrize("world,ipc", [(8, False), (5, True)])
 def test_batch_sharded_merge_between_processes(world, ipc):
-    """rb3gpu_sh_merge_text between eight PROCESSES over the gloo callbacks (what bench.py --gpus 8 runs where the ranks share a GPU): the exchange with the owners of
+    """rb3gpu_sh_merge_text between PROCESSES over the gloo callbacks (what bench.py --gpus N runs where the ranks share a GPU): the exchange with the owners of
     the text ranges is called right behind the kernel that fills the send regions, and a communicator that reads them with the runtime's synchronous copies must
-    wait for the engine's (non-blocking) stream first -- CallbackComm does (rb3gpu_stream_sync); without it eight processes lost rows where four got away with it"""
+    wait for the engine's (non-blocking) stream first -- CallbackComm does (rb3gpu_stream_sync); without it eight processes lost rows where four got away with it.
+    Eight ranks, two per process (a thread, an engine handle and a gloo group each), so that five processes hold the GPU rather than nine.  With peer rounds
+    (ipc) every rank must be a process of its own -- a process maps the buffers of the others through HIP IPC handles -- and five ranks keep it at six."""
     import socket
     import torch.multiprocessing as mp
     from tools import probe_gloo_text
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=probe_gloo_text.worker, args=(r, world, port, q, ipc, 20000)) for r in range(world)]
+    if ipc:
+        procs = [ctx.Process(target=probe_gloo_text.worker, args=(r, world, port, q, ipc, 20000)) for r in range(world)]
+    else:
+        procs = [ctx.Process(target=_text_ranks_worker, args=([r, r + 1], world, port, q, 20000)) for r in range(0, world, 2)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=600) for _ in range(world))

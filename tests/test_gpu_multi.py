@@ -1,9 +1,9 @@
-"""Everything that needs TWO DEVICES: these tests skip themselves on a one-GPU box and run unasked on a box with more (VERDICT r4
-item 4a) -- the thread-group communicator with hipMemcpyPeerAsync between two devices, the RCCL communicator of world 2 across
-two devices (its all-gather, its grouped send/recv, one rb3gpu_sh_merge through it), the shard object over two devices, and the
-CLI's `build --gpus 2` / `--gpus 2 --interval` with distinct devices.  No multi-GPU box was available in rounds 1-5: until one
-is, what these cover on hardware is UNMEASURED; the same code paths run with every rank on device 0 in test_gpu_engine.py /
-test_gpu_cli.py."""
+"""The multi-device paths: the thread-group communicator with hipMemcpyPeerAsync between two devices, the
+RCCL communicator of world 2 across two devices (its all-gather, its grouped send/recv, one rb3gpu_sh_merge through it), the
+shard object over two devices, and the CLI's `build --gpus 2` / `--gpus 2 --interval` with distinct devices.  Rank r runs on
+device r % (devices of the box): on a one-GPU box the ranks share device 0 and every test but the RCCL one runs the same calls
+with the copies between ranks staying on that device; RCCL refuses two ranks on one device, so that test needs two.  No
+multi-GPU box was available in rounds 1-5: until one is, the copies between distinct devices are UNMEASURED on hardware."""
 import hashlib
 import json
 import os
@@ -33,11 +33,10 @@ need2 = pytest.mark.skipif(NDEV < 2, reason="needs two HIP devices (this box has
 MAN = json.load(open(os.path.join(util.GOLDEN, "MANIFEST.json")))
 
 
-@need2
 @pytest.mark.parametrize("world", [2, min(4, max(NDEV, 2))])
 def test_thread_group_communicator_over_distinct_devices(oracle, world):
     """rb3gpu_sh_merge with one rank per DEVICE: the thread-group communicator's all-to-all is hipMemcpyPeerAsync between two
-    devices here (every rank pulls its share), its barriers join threads that drive different devices"""
+    devices here (every rank pulls its share), its barriers join threads that drive different devices (one device: the ranks share it)"""
     from ropebwt3_amd import Rb3Gpu, CommGroup, multi
     rng = np.random.default_rng(700 + world)
     cur, batches, want = _sharded_case(oracle, rng, "reads")
@@ -72,16 +71,15 @@ def test_thread_group_communicator_over_distinct_devices(oracle, world):
     assert not errs, errs
 
 
-@need2
 def test_shard_object_over_two_devices(oracle):
-    """rb3gpu_shard_split / _merge / _gather with the intervals on devices 0 and 1 (what `build --gpus 2 --interval` calls)"""
+    """rb3gpu_shard_split / _merge / _gather with the intervals on devices 0 and 1 (what `build --gpus 2 --interval` calls; one device: both on it)"""
     from ropebwt3_amd import Rb3Gpu, Shard
     rng = np.random.default_rng(41)
     cur, batches, want = _sharded_case(oracle, rng, "family")
     h = Rb3Gpu(verbose=1)
     try:
         h.from_plain(cur)
-        sh = Shard(h, [0, 1])
+        sh = Shard(h, [0, 1 % NDEV])
         for t2 in batches:
             d_bwt, d_tw = h.sort_text(t2)
             sh.merge(d_bwt, d_tw, t2.size, np.flatnonzero(t2 == 0))
@@ -170,11 +168,10 @@ def _cli(args):
     return r.stdout, r.stderr.decode()
 
 
-@need2
 @pytest.mark.parametrize("mode", [[], ["--interval"]])
 def test_cli_build_on_two_devices(mode):
     """`build --gpus 2` (slices + tree merge, peer copy of the right operand) and `build --gpus 2 --interval` with the two
-    handles on DIFFERENT devices: the reference's .fmd"""
+    handles on DIFFERENT devices (one device: both handles on it): the reference's .fmd"""
     for name, extra in (("reads_fwd", ["-m40k"]), ("reads_fq", ["-m40k"]), ("genomes12_files", [])):
         if mode and name == "genomes12_files":
             continue   # (--interval is for batches of short strings)
@@ -186,5 +183,5 @@ def test_cli_build_on_two_devices(mode):
 
 def test_this_file_reports_the_device_count():
     """(always runs: the log of a GPU run says how many devices the multi-device tests saw)"""
-    print("HIP devices visible: %d -- two-device tests %s" % (NDEV, "RUN" if NDEV >= 2 else "skipped"))
+    print("HIP devices visible: %d -- ranks of the multi-device tests %s" % (NDEV, "on distinct devices" if NDEV >= 2 else "share device 0; the RCCL test skipped"))
     assert NDEV >= 1

@@ -1,8 +1,9 @@
 #!/bin/bash
-# GPU box: the round's committed evidence (copy gpurun_out/prof/r3_* into profiles/)
+# GPU box: the round's committed evidence (copy the r3_* files of the prof/ output folder, and $OUT/r3_bench_default.json -- bench_out/ by default -- into profiles/)
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; mkdir -p gpurun_out/prof
+OUT=${OUT:-$R/bench_out}; mkdir -p "$OUT"   # the full bench line (bench.py --full)
 # 1. the default bench line
-timeout 900 python bench.py > gpurun_out/prof/r3_bench_default.json 2> gpurun_out/prof/r3_bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > "$OUT/r3_bench_default.json" 2> "$OUT/r3_bench_default.err"; echo "bench rc=$?"
 # 2. kernel statistics of the headline (one warm-up build + one timed build)
 LINES_OUT=45 bash tools/prof_bench.sh r3_mtb152 --only headline --steps 1 --warmup 1 | cut -c1-130
 # 3. counters of the headline's kernels: HBM traffic of k_chain, issue/stall counters of k_chain and the run-space rebuild

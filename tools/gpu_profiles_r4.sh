@@ -1,9 +1,10 @@
 #!/bin/bash
-# GPU box: the round's committed evidence (copy gpurun_out/prof/r4_* into profiles/)
+# GPU box: the round's committed evidence (copy the r4_* files of the prof/ output folder, and $OUT/r4_bench_default.json -- bench_out/ by default -- into profiles/)
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; mkdir -p gpurun_out/prof
+OUT=${OUT:-$R/bench_out}; mkdir -p "$OUT"   # the full bench line (bench.py --full)
 WHAT=${1:-all}
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-	timeout 900 python bench.py > gpurun_out/prof/r4_bench_default.json 2> gpurun_out/prof/r4_bench_default.err; echo "bench rc=$?"
+	timeout 900 python bench.py --full > "$OUT/r4_bench_default.json" 2> "$OUT/r4_bench_default.err"; echo "bench rc=$?"
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = stats ]; then
 	# kernel statistics: the headline (warm-up build + timed build + the one with serial H2D), the large-index leg, the index beyond 2^32 symbols

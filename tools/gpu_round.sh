@@ -10,11 +10,12 @@ if [ "$WHAT" = all ] || [ "$WHAT" = tests ]; then
 	tail -3 gpurun_out/pytest_gpu.log
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-	timeout 900 python bench.py > gpurun_out/bench_n1.json 2> gpurun_out/bench_n1.err; echo "bench rc=$?"; tail -3 gpurun_out/bench_n1.err
-	python - <<'PY'
-import json
+	OUT=${OUT:-$R/bench_out}; mkdir -p "$OUT"   # the full bench line (bench.py --full)
+	timeout 900 python bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"; echo "bench rc=$?"; tail -3 "$OUT/bench_n1.err"
+	OUT="$OUT" python - <<'PY'
+import json, os
 try:
-    d = json.loads(open("gpurun_out/bench_n1.json").read().strip().splitlines()[-1])
+    d = json.loads(open(os.path.join(os.environ["OUT"], "bench_n1.json")).read().strip().splitlines()[-1])
     print({k: d[k] for k in ("value", "ms_per_step", "phases_ms_per_step", "not_counted_ms_per_step", "h2d")})
     print(d["config"]["fmd_identical_to_reference"], d["roofline"]["frac"], d["roofline"]["ms_per_launch"], d["roofline_path"]["frac"], d["roofline_rebuild"]["frac"])
     print(d.get("aux_cli_build"))

@@ -8,7 +8,7 @@ TAG=${1:-r2}; KPAT=${2:-k_chain}; KOUT=${3:-k_chain}; shift 3
 export TMPDIR=/tmp
 mkdir -p $R/gpurun_out/prof
 cd /tmp
-BENCH="python $R/bench.py --no-cpu-baseline $*"
+BENCH="python $R/bench.py --full --no-cpu-baseline $*"
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof/trace -o $TAG -- $BENCH > $R/gpurun_out/prof/trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $R/gpurun_out/prof/pmc_fetch -o $TAG -- $BENCH > $R/gpurun_out/prof/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $R/gpurun_out/prof/pmc_write -o $TAG -- $BENCH > $R/gpurun_out/prof/pmc_write.log 2>&1

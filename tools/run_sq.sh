@@ -8,7 +8,7 @@ EXTRA=${2:-}
 export TMPDIR=/tmp
 mkdir -p $R/gpurun_out/prof
 cd /tmp
-BENCH="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline $EXTRA"
+BENCH="python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline $EXTRA"
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM SQ_INSTS_SMEM"; do
 	i=$((i+1))
