@@ -116,7 +116,7 @@ typedef struct {
 	                                right neighbour owns and records; flags >> 16 & 255: if not 0, the walker does not start at all when the
 	                                row that many positions further right already carries a record (it comes too late: rb3h_walkers_text, RB3H_PROBE = 64) */
 } rb3gpu_walker_t;
-#define RB3GPU_KA_SENTINEL (-2)  /* ka0 of a sentinel row: the engine substitutes acc[1] of the index */
+#define RB3GPU_KA_SENTINEL (-2)  /* ka0 of a sentinel row: the engine substitutes acc[1] of the index (in a sorted order: p0 of the string, rb3gpu_set_order) */
 #define RB3GPU_WK_CHECK 2        /* the rows ahead may already be recorded: check each before recording */
 
 /* rb3gpu_merge_plain with an explicit walker list (host memory); same result, more parallelism
@@ -286,6 +286,33 @@ int rb3gpu_sorter_sort_uploaded_sa(rb3gpu_sorter_t *s, int64_t len, void **d_bwt
 int rb3gpu_sorter_sort_sa(rb3gpu_sorter_t *s, int64_t len, const uint8_t *text, void **d_bwt, void **d_tw, void **d_sa);
 /* cumulative times of a sorter: text upload (host -> HBM, through its pinned staging buffer) and suffix sorting proper */
 int rb3gpu_sorter_stats(const rb3gpu_sorter_t *s, double *ms_upload, double *ms_sort, int64_t *n_batches, int64_t *n_symbols);
+
+/* Sorted string orders (build -s / -r; mrope.h MR_SO_*).  The reference's ropebwt2 insertion (mr_insert_multi) builds the BWT of a
+ * collection in reverse lexicographic order (RLO: the strings sorted by their reversed contents, $ < A < C < G < T < N, a string that is
+ * a suffix of another first) or reverse-complement lexicographic order (RCLO: the same with $ < T < G < C < A < N).  That BWT is the
+ * input-order BWT of the collection reordered that way, so the engine builds it through its own merge: every batch is put into the order
+ * on the device before it is suffix-sorted, and the sentinels of a merged batch go to their places among the index's strings (p0, below)
+ * instead of behind them all.  The default is RB3GPU_SO_IO: nothing changes.
+ *   rb3gpu_set_order: the order of the index in the handle (set it before the first merge into an index built that way).  Honoured by
+ *     rb3gpu_merge_plain[_dev][_walkers], rb3gpu_merge_plain_dev_walkers, rb3gpu_merge_text_dev, rb3gpu_merge_text_sa_dev,
+ *     rb3gpu_merge_text_step_dev, rb3gpu_mg_rank_plain[_walkers], rb3gpu_mg_rank_text_dev -- the batch given to them must already be in the
+ *     order --, and by rb3gpu_bwt_from_text / rb3gpu_sort_text[_sa], which order the text first.  RB3GPU_EUNSUP from rb3gpu_mg_begin,
+ *     rb3gpu_merge_index, rb3gpu_merge_fmd_words and the interval-sharded merge (rb3gpu_sh_*; rb3gpu_shard_split returns NULL).
+ *   rb3gpu_sorter_set_order: a sorter orders every batch before it sorts it (after the reverse strands of rb3gpu_sorter_upload_fwd).
+ *   rb3gpu_order_strings_dev: d_text (len symbols of device memory, strings ending in 0) reordered in place, in order so (RLO or RCLO).
+ *   rb3gpu_sentinel_ranks_dev: p0 of the next merge of a batch (already in order) into the handle's index, into host memory (n_strings
+ *     entries): p0[i] = the index strings that sort before string i in the handle's order.  d_tw may be NULL (the strings are then read
+ *     through the batch's BWT).  RB3GPU_EINVAL if n_strings is not the batch's count, RB3GPU_EINTERNAL if p0 decreases anywhere (a batch
+ *     not in the order), RB3GPU_ESTATE for an empty index or the input order. */
+#define RB3GPU_SO_IO   0
+#define RB3GPU_SO_RLO  1
+#define RB3GPU_SO_RCLO 2
+int rb3gpu_set_order(rb3gpu_t *h, int so);
+int rb3gpu_get_order(const rb3gpu_t *h);
+int rb3gpu_sorter_set_order(rb3gpu_sorter_t *s, int so);
+int rb3gpu_sorter_order_stats(const rb3gpu_sorter_t *s, double *ms_order); /* cumulative time of the ordering (not in ms_sort of rb3gpu_sorter_stats) */
+int rb3gpu_order_strings_dev(rb3gpu_t *h, int64_t len, uint8_t *d_text, int so);
+int rb3gpu_sentinel_ranks_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, const uint64_t *d_tw, int64_t n_strings, int64_t *p0);
 
 /* Import for `build -i` (rb3_enc_fmd2fmr fm-index.c:56-85, mr_restore mrope.c:161-177):
  * runs[i] = len<<3 | sym in BWT order (host memory). */

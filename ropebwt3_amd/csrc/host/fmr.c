@@ -36,7 +36,7 @@ typedef struct {
 } fmr_rope_t;
 
 struct rb3h_fmrw_s {
-	int max_nodes, block_len, cur;
+	int max_nodes, block_len, cur, so;
 	int64_t acc[7];
 	fmr_rope_t r[6];
 };
@@ -183,10 +183,15 @@ static void fmr_dump_level(const rb3h_fmrw_t *w, const fmr_rope_t *r, int64_t be
 	}
 }
 
+void rb3h_fmrw_set_order(rb3h_fmrw_t *w, int so)
+{
+	w->so = so;
+}
+
 int rb3h_fmrw_dump(rb3h_fmrw_t *w, FILE *fp)
 {
 	int a;
-	const uint8_t so = 0; /* MR_SO_IO */
+	const uint8_t so = (uint8_t)w->so; /* the string order (MR_SO_*; 0 unless rb3h_fmrw_set_order) */
 	for (a = 0; a < 6; ++a) {
 		if (w->r[a].remaining != 0) return -2; /* fewer symbols than announced */
 		if (fmr_flush_run(w, &w->r[a]) < 0) return -1;

@@ -34,10 +34,12 @@ typedef struct {
 	int64_t gpu_batch;      /* with GPU suffix sorting a batch (-m) is cut into sub-batches of at most this many symbols, at record
 	                           boundaries: the .fmd does not depend on the batching, and the GPU sorter takes < 2^31 */
 	int64_t gpu_sort_limit; /* batches of this many symbols or more go to the host sorter (one record longer than a sub-batch) */
+	int so;                 /* string order (-s RLO, -r RCLO; RB3GPU_SO_*): asked for, then the one the build uses (main_build) */
 } bopt_t;
 
 /* how the batches of this run were sorted (for the closing statistics line) */
-static struct { int64_t n_gpu, n_host, sym_gpu, sym_host; double ms_upload, ms_sort; } g_sorted;
+static struct { int64_t n_gpu, n_host, sym_gpu, sym_host; double ms_upload, ms_sort, ms_order; } g_sorted;
+static int g_order = 0; /* the build's string order (RB3GPU_SO_*): its batches are ordered on the GPU, never sorted on the host */
 static pthread_mutex_t g_sorted_mtx = PTHREAD_MUTEX_INITIALIZER; /* (the slices of a multi-GPU build end at different times) */
 /* what the handles of the other slices of a multi-GPU build did, added up before they are destroyed (the closing statistics) */
 static struct { double ms_path; int64_t n_sym; } g_other_slices;
@@ -92,7 +94,10 @@ static int usage_build(FILE *fp, const bopt_t *opt)
 	fprintf(fp, "    -d          dump in the fermi-delta format (FMD)\n");
 	fprintf(fp, "    -b          dump in the ropebwt format (FMR)\n");
 	fprintf(fp, "    -S FILE     save the current index to FILE after each input file []\n");
-	fprintf(fp, "  Not available in this build (ropebwt2 insertion and debugging formats): -2 -s -r -T -e\n");
+	fprintf(fp, "  String order:\n");
+	fprintf(fp, "    -s          reverse lexicographic order (RLO): fewer runs for short reads (GPU sorting, one GPU)\n");
+	fprintf(fp, "    -r          reverse-complement lexicographic order (RCLO)\n");
+	fprintf(fp, "  Not available in this build (ropebwt2 insertion and debugging formats): -2 -T -e\n");
 	return fp == stdout ? 0 : 1;
 }
 
@@ -257,10 +262,23 @@ static int dump_fmr(rb3gpu_t *h, const bopt_t *opt, FILE *fp)
 	else rb3gpu_get_acc(h, acc);
 	w = rb3h_fmrw_init(acc, opt->max_nodes, opt->block_len);
 	if (w == 0) return -1;
+	rb3h_fmrw_set_order(w, opt->so); /* mr_dump, mrope.c:155-156 */
 	ret = iv_live() ? iv_export_runs(sink_fmr, w) : rb3gpu_export_runs(h, sink_fmr, w);
 	if (ret == 0) ret = rb3h_fmrw_dump(w, fp);
 	rb3h_fmrw_destroy(w);
 	return ret;
+}
+
+/* the string order of an index file: byte 3 of an FMR header (mr_restore, mrope.c:170), input order for anything else */
+static int index_order(const char *fn)
+{
+	FILE *fp = fopen(fn, "rb");
+	unsigned char magic[4];
+	int so = RB3GPU_SO_IO;
+	if (fp == 0) return so; /* (load_index reports it) */
+	if (fread(magic, 1, 4, fp) == 4 && memcmp(magic, "RB\2", 3) == 0 && magic[3] <= RB3GPU_SO_RCLO) so = magic[3];
+	fclose(fp);
+	return so;
 }
 
 /* an existing index into HBM (build.c:172-184, rb3_fmi_restore): an FMD file is decoded on the device
@@ -416,6 +434,10 @@ static int process_batch(rb3gpu_t *h, batch_t *b, int *has_index)
 		const int first = !*has_index;
 		ret = process_raw_batch(h, b, has_index);
 		if (ret == 1) { /* host sorter instead */
+			if (g_order) {
+				fprintf(stderr, "ERROR: the GPU could not take a batch of %ld symbols; -s/-r put batches into order on the GPU only\n", (long)b->len);
+				return -1;
+			}
 			if (rb3h_verbose >= 2) fprintf(stderr, "[W::%s] the GPU suffix sorter could not take a batch of %ld symbols; sorting it on the host\n", "main_build", (long)b->len);
 			ret = b->step > 0 ? rb3h_build_bwt_walkers(b->n_seq, b->len, b->bwt, 1, b->step, &b->n_walkers, &b->walkers) : rb3h_build_bwt(b->n_seq, b->len, b->bwt, 1);
 			if (ret < 0) { fprintf(stderr, "ERROR: failed to construct the partial BWT (code %d)\n", ret); return -1; }
@@ -503,7 +525,7 @@ static int sort_batch(const bopt_t *opt, int device, rb3h_buf_t *seq, int64_t n_
 			if (r2 == 0) {
 				if (rb3h_verbose >= 3)
 					fprintf(stderr, "[M::%s::%.3f*%.2f] constructed partial BWT for %ld symbols on the GPU\n", "main_build", rb3h_realtime(), rb3h_percent_cpu(), (long)b->len);
-				if (b->step > 0 && getenv("RB3_HOST_WALKERS") && rb3h_walkers_text(b->len, b->bwt, b->step, &b->n_walkers, &b->walkers) < 0) b->walkers = 0, b->n_walkers = 0; /* (experiments: the host's list) */
+				if (b->step > 0 && !g_order && getenv("RB3_HOST_WALKERS") && rb3h_walkers_text(b->len, b->bwt, b->step, &b->n_walkers, &b->walkers) < 0) b->walkers = 0, b->n_walkers = 0; /* (experiments: the host's list) */
 				walkers_pin(b);
 				b->gs = gs, b->raw = 0; /* (the walker list of a batch of long strings is made on the device, inside the merge call: b->n_seq and b->step say how) */
 				if (opt->interval) b->sent = sentinels_of(b->bwt, b->len, n_seq, &b->n_sent);
@@ -513,6 +535,10 @@ static int sort_batch(const bopt_t *opt, int device, rb3h_buf_t *seq, int64_t n_
 		}
 		*out = b;
 		return 0;
+	}
+	if (g_order) { /* (a record longer than the GPU sorter takes) */
+		fprintf(stderr, "ERROR: a batch of %ld symbols is beyond the GPU sorter; -s/-r put batches into order on the GPU only\n", (long)seq->l);
+		return -1;
 	}
 	__sync_fetch_and_add(&g_sorted.n_host, 1), __sync_fetch_and_add(&g_sorted.sym_host, seq->l);
 	if (opt->split_log2 >= 0 && n_seq > 0 && seq->l / n_seq > 4 * step && seq->l / step + n_seq < (1 << 22))
@@ -715,6 +741,7 @@ static void *run_slice(void *arg)
 		pthread_create(&rt, 0, reader_main, &rd);
 		for (k = 0; k < n_sort; ++k) {
 			sa[k].q = &q, sa[k].gs = opt->gpu_sort ? rb3gpu_sorter_create(sl->device) : 0; /* NULL: the consumer's handle sorts */
+			if (sa[k].gs && opt->so) rb3gpu_sorter_set_order(sa[k].gs, opt->so); /* every batch into the build's string order before it is sorted */
 			pthread_create(&st[k], 0, sorter_main, &sa[k]);
 		}
 		for (;;) {
@@ -738,10 +765,11 @@ static void *run_slice(void *arg)
 		pthread_join(rt, 0);
 		for (k = 0; k < n_sort; ++k) pthread_join(st[k], 0);
 		for (k = 0; k < n_sort; ++k) {
-			double up = 0, so = 0;
+			double up = 0, so = 0, om = 0;
 			if (sa[k].gs && rb3gpu_sorter_stats(sa[k].gs, &up, &so, 0, 0) == 0) {
+				rb3gpu_sorter_order_stats(sa[k].gs, &om);
 				pthread_mutex_lock(&g_sorted_mtx);
-				g_sorted.ms_upload += up, g_sorted.ms_sort += so;
+				g_sorted.ms_upload += up, g_sorted.ms_sort += so, g_sorted.ms_order += om;
 				pthread_mutex_unlock(&g_sorted_mtx);
 			}
 			/* the sorters' scratch (tens of bytes per symbol of a batch) is given back AFTER the index has been written: freeing
@@ -794,7 +822,9 @@ int main_build(int argc, char *argv[])
 		else if (c == 'p') opt.sais_threads = atoi(optarg);
 		else if (c == 'l') opt.block_len = atoi(optarg);
 		else if (c == 'n') opt.max_nodes = atoi(optarg);
-		else if (c == '2' || c == 's' || c == 'r') {
+		else if (c == 's') opt.so = RB3GPU_SO_RLO;
+		else if (c == 'r') opt.so = RB3GPU_SO_RCLO;
+		else if (c == '2') {
 			fprintf(stderr, "ERROR: -%c selects the ropebwt2 insertion algorithm, which this build does not include; the default (suffix sorting + merge) gives the same BWT for -2\n", c);
 			return 1;
 		} else if (c == 'T' || c == 'e') {
@@ -827,6 +857,19 @@ int main_build(int argc, char *argv[])
 		fprintf(stderr, "ERROR: -F and -R together leave nothing to index\n");
 		return 1;
 	}
+	if (opt.so) { /* -s / -r: a sorted string order (build.c:146-219 decides which one the build really uses) */
+		if (opt.n_gpus > 1 || opt.interval || !opt.gpu_sort) {
+			fprintf(stderr, "ERROR: -%c is available with GPU suffix sorting on one GPU only (not with --gpus, --interval or --host-sort)\n", opt.so == RB3GPU_SO_RLO ? 's' : 'r');
+			return 1;
+		}
+		if (fn_in && strcmp(fn_in, "-") == 0) { /* (the order of an index on stdin is in its header: not read twice here) */
+			fprintf(stderr, "ERROR: -%c needs the index of -i in a file, not on stdin\n", opt.so == RB3GPU_SO_RLO ? 's' : 'r');
+			return 1;
+		}
+		if (fn_in) opt.so = index_order(fn_in); /* -i: the order of that index (an FMR's header byte 3; an FMD is in input order) */
+		if (argc - optind == 1 && opt.sais_threads > 0 && opt.n_threads - opt.sais_threads > 0) opt.so = RB3GPU_SO_IO; /* the reference's pipeline (build.c:178, 55-83) merges in input order */
+	}
+	g_order = opt.so;
 
 	rb3gpu_opt_init(&gopt);
 	gopt.device = opt.device, gopt.split_log2 = opt.split_log2, gopt.verbose = rb3h_verbose;
@@ -835,6 +878,7 @@ int main_build(int argc, char *argv[])
 		fprintf(stderr, "ERROR: no usable MI355X/HIP device (device %d); the merge path has no CPU fallback\n", opt.device);
 		return 1;
 	}
+	if (opt.so) rb3gpu_set_order(h, opt.so);
 
 	if (getenv("RB3_PINNED_LIMIT")) g_pin_limit = atoll(getenv("RB3_PINNED_LIMIT"));
 	if (!getenv("RB3_NO_PINNED")) g_pin_on = 1, rb3h_seq_set_batch_allocator(pin_alloc, pin_release); /* batch buffers in page-locked memory (one DMA per batch) */
@@ -1027,6 +1071,8 @@ int main_build(int argc, char *argv[])
 			fprintf(stderr, "[M::%s] GPU suffix sorting: %.3f ms in all (%ld doubling rounds), text upload included\n", __func__, st.ms_sort, (long)st.n_sort_rounds);
 		if (g_sorted.ms_sort > 0)
 			fprintf(stderr, "[M::%s] GPU sorter threads: text upload %.3f ms, suffix sorting %.3f ms (overlapped with the merges)\n", __func__, g_sorted.ms_upload, g_sorted.ms_sort);
+		if (g_sorted.ms_order > 0)
+			fprintf(stderr, "[M::%s] GPU sorter threads: strings put into %s order in %.3f ms\n", __func__, opt.so == RB3GPU_SO_RLO ? "RLO" : "RCLO", g_sorted.ms_order);
 		fprintf(stderr, "[M::%s] rebuild: %.3f ms for %ld algorithmic bytes (9 B x rows + old + new block array per round) = %.1f GB/s; LF walkers: k_chain %.3f ms in %ld launches, %ld steps\n", __func__,
 				st.ms_build, (long)st.bytes_rebuild, st.ms_build > 0 ? st.bytes_rebuild / st.ms_build / 1e6 : 0.0, st.ms_chain, (long)st.n_rank_launches, (long)st.n_lf_steps);
 		fprintf(stderr, "[M::%s] run-space rebuild: %ld groups, %ld of them handed on to the window kernels; %ld merges redone without tentative records, %ld needed the long settle pass; %ld rows LF-checked; %.1f ms in %ld device allocations\n", __func__,

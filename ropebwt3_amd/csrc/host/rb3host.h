@@ -88,6 +88,7 @@ typedef struct rb3h_fmrw_s rb3h_fmrw_t;
 rb3h_fmrw_t *rb3h_fmrw_init(const int64_t acc[7], int max_nodes, int block_len);
 int rb3h_fmrw_enc(rb3h_fmrw_t *w, int64_t l, int c);
 int rb3h_fmrw_dump(rb3h_fmrw_t *w, FILE *fp);
+void rb3h_fmrw_set_order(rb3h_fmrw_t *w, int so); /* byte 3 of the header (mr_dump, mrope.c:155-156): RB3GPU_SO_* / MR_SO_* */
 void rb3h_fmrw_destroy(rb3h_fmrw_t *w);
 /* decode an FMR file (mr_restore, mrope.c:161-177; rope_restore, rope.c:289-330) */
 int rb3h_fmr_read_runs(FILE *fp, rb3h_run_f emit, void *data);

@@ -37,6 +37,11 @@ rb3sort_ws *rb3sort_create(void);
 void rb3sort_destroy(rb3sort_ws *ws);
 int64_t rb3sort_bytes(const rb3sort_ws *ws);
 int rb3sort_bwt(rb3sort_ws *ws, hipStream_t st, int64_t n, const uint8_t *d_text, uint8_t *d_bwt, int64_t step, int64_t *d_ckrow, int *rounds, uint64_t *d_tw, uint32_t *d_sa);
+struct rb3order_ws; // rb3gpu_order.hip: the strings of a batch in a sorted order (RLO / RCLO)
+rb3order_ws *rb3order_create(void);
+void rb3order_destroy(rb3order_ws *ws);
+int64_t rb3order_bytes(const rb3order_ws *ws);
+int rb3order_text(rb3order_ws *ws, rb3sort_ws *sws, hipStream_t st, int64_t n, uint8_t *d_text, int so, int *rounds);
 /* the FMD packer lives in rb3gpu_fmdenc.hip */
 int rb3fmd_encode(hipStream_t st, int64_t n_sym, int64_t nr, const uint64_t *d_words, uint64_t **z_out, int64_t *n_words);
 struct rb3fmd_enc;
@@ -222,6 +227,11 @@ struct rb3gpu_s {
 	const uint32_t *mg_sa = nullptr; // the suffix array of the batch being merged, if its caller has it (rb3gpu_merge_text_sa_dev): records in text order
 	int tent_q = 1;          // masks of 256 * tent_q bits (merge_core doubles it when walkers report intervals wider than that)
 	int64_t sid_dirty[2] = {RB3_TENT_HALF, RB3_TENT_HALF}; // entries of the two halves of the stretch tables (dl) that may be non-zero
+	int order = RB3GPU_SO_IO;        // string order of the index (rb3gpu_set_order): batches are ordered before they are sorted, their sentinels go to p0
+	bool p0_live = false;            // p0b holds the sentinels' insertion points of the merge in progress (order_prepare): view_of hands them to the walkers
+	Buf p0b;                         // p0 of the batch being merged, the sentinels' text positions and a counter behind it
+	int64_t p0_n = 0;                // entries of p0
+	rb3order_ws *ows = nullptr;      // scratch of the string order (rb3gpu_order.hip), created on first use
 };
 
 static double now_s(void)
@@ -566,8 +576,12 @@ static IdxView view_of(const rb3gpu_t *h)
 	v.abs = RB3_ABS_HEADERS(h->n, h->tn.abs_limit) ? (h->n >= RB3_ABS_LIMIT || h->tn.abs_table ? 2 : 1) : 0;
 	v.sb = h->ib[h->cur].sbt;
 	v.dense = h->nslots == nwin ? (v.abs ? 2 : 1) : 0;
+	v.p0 = h->p0_live ? (const int64_t*)h->p0b.p : nullptr, v.p0n = h->p0_live ? h->p0_n : 0;
 	return v;
 }
+
+/* the entry points that merge in input order only (a sorted string order needs the batch's strings: rb3gpu_set_order) */
+#define RB3_IO_ONLY(h) do { if ((h) && (h)->order != RB3GPU_SO_IO) return RB3GPU_EUNSUP; } while (0)
 
 extern "C" {
 
@@ -825,7 +839,7 @@ void rb3gpu_destroy(rb3gpu_t *h)
 #endif
 	index_drop(h);
 	ib_release(h, 0), ib_release(h, 1);
-	Buf *all[] = { &h->b2, &h->pos, &h->post, &h->tcnt, &h->tpre, &h->ctot, &h->ctot2, &h->gstat, &h->gpre, &h->jg, &h->misc, &h->xbuf, &h->wl, &h->wls, &h->dl, &h->dlx, &h->wstat, &h->wplane, &h->wruns, &h->gslots, &h->glist, &h->pslots, &h->lbst, &h->shc, &h->shn, &h->shs, &h->shr, &h->shk, &h->twb, &h->shp0, &h->shp1 };
+	Buf *all[] = { &h->b2, &h->pos, &h->post, &h->tcnt, &h->tpre, &h->ctot, &h->ctot2, &h->gstat, &h->gpre, &h->jg, &h->misc, &h->xbuf, &h->wl, &h->wls, &h->dl, &h->dlx, &h->wstat, &h->wplane, &h->wruns, &h->gslots, &h->glist, &h->pslots, &h->lbst, &h->shc, &h->shn, &h->shs, &h->shr, &h->shk, &h->twb, &h->shp0, &h->shp1, &h->p0b };
 	for (Buf *b : all) buf_release(h, *b);
 	garbage_collect(h, true);
 	for (int i = 0; i < 8; ++i) (void)hipEventDestroy(h->ev[i]);
@@ -834,6 +848,7 @@ void rb3gpu_destroy(rb3gpu_t *h)
 	(void)hipStreamDestroy(h->st2);
 	for (int i = 0; i < 2; ++i) if (h->stage[i]) (void)hipHostFree(h->stage[i]);
 	rb3sort_destroy(h->sorter);
+	rb3order_destroy(h->ows);
 	(void)hipStreamDestroy(h->st);
 	delete h;
 }
@@ -1241,6 +1256,7 @@ static int pick_split(const rb3gpu_t *h, int64_t len, int64_t m2)
 int rb3gpu_mg_begin(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, void *d_pos_ext, int64_t acc2_out[RB3GPU_ASIZE+1])
 {
 	if (!h || len <= 0 || !d_bwt) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
 	int r;
@@ -1290,7 +1306,7 @@ static int mg_walk_impl(rb3gpu_t *h, int64_t n_walkers, const rb3gpu_walker_t *w
 			if (!tmp) return RB3GPU_ENOMEM;
 			memcpy(tmp, walkers, (size_t)n_walkers * sizeof(rb3gpu_walker_t));
 			for (int64_t i = 0; i < n_walkers; ++i)
-				if (tmp[i].ka0 == RB3GPU_KA_SENTINEL) tmp[i].ka0 = h->acc[1];
+				if (tmp[i].ka0 == RB3GPU_KA_SENTINEL && !h->p0_live) tmp[i].ka0 = h->acc[1]; // (a sorted order: k_chain takes p0 of the row)
 			hipError_t e = hipMemcpy(dwl, tmp, (size_t)n_walkers * 32, hipMemcpyHostToDevice);
 			free(tmp);
 			HIPCHK(e);
@@ -2391,14 +2407,82 @@ static int merge_plain_via_tw(rb3gpu_t *h, int64_t len, const uint8_t *d_b2, int
 	return r;
 }
 
-int rb3gpu_merge_plain_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, int commit)
+/* A merge in a sorted string order (RLO / RCLO; the batch was ordered before it was sorted): the sentinel of string i of the batch goes to
+ * p0[i] = the index strings that sort before it (k_sentinel_ranks) instead of acc[1], everything else of the merge stays as it is.  Computed
+ * here, in front of the merge, with one synchronisation (the batch's string count); d_tw NULL: the strings are read through the batch's row
+ * words.  Leaves h->p0_live set (view_of hands p0 to the walkers and the LF check) until order_done.  Nothing to do in input order. */
+static int order_prepare(rb3gpu_t *h, int64_t len, const uint8_t *d_b2, const uint64_t *d_tw, int64_t n_strings = -1, int64_t *host_p0 = nullptr)
 {
-	if (!h || len <= 0 || !d_bwt) return RB3GPU_EINVAL;
-	HIPCHK(hipSetDevice(h->dev));
+	h->p0_live = false;
+	if (h->order == RB3GPU_SO_IO) return 0;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	int r;
+	int64_t acc2[7] = {0, 0, 0, 0, 0, 0, 0};
+	if (!d_tw && (r = buf_ensure(h, h->pos, (size_t)len * 8)) < 0) return r; // (the merge's record buffer holds the row words until the merge writes its own)
+	if ((r = buf_ensure(h, h->misc, MISC_WORDS * 8)) < 0) return r;
+	HIPCHK(hipEventRecord(h->ev[0], h->st));
+	// text-order words and the caller's string count: nothing to count (the merge's own histogram pass does that, and a count that is not the batch's
+	// leaves sentinel positions unfound below); else the batch's counts, and without text-order words its row words, with one synchronisation
+	const bool counted = d_tw != nullptr && n_strings > 0;
+	if (!counted && (r = lf_build(h, len, d_b2, d_tw ? nullptr : (int64_t*)h->pos.p, acc2, d_tw == nullptr, d_tw != nullptr)) < 0) return r;
+	const int64_t m2 = counted ? n_strings : acc2[1];
+	if (m2 <= 0 || m2 > len || (n_strings >= 0 && n_strings != m2)) return RB3GPU_EINVAL;
+	if ((r = buf_ensure(h, h->p0b, (size_t)m2 * 16 + 64)) < 0) return r;
+	int64_t *dp0 = (int64_t*)h->p0b.p, *dsent = dp0 + m2;
+	unsigned long long *bad = (unsigned long long*)(dsent + m2); // [0]: p0 out of order, [1]: strings without a sentinel (a wrong count)
+	HIPCHK(hipMemsetAsync(bad, 0, 16, h->st));
+	if (d_tw) {
+		HIPCHK(hipMemsetAsync(dsent, 0xff, (size_t)m2 * 8, h->st));
+		hipLaunchKernelGGL(k_wl_sentinels, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, h->st, d_tw, len, m2, dsent);
+	}
+	HIPCHK(hipEventRecord(h->ev[1], h->st));
+	int64_t nblk = (m2 * 8 + 255) / 256;
+	if (nblk > 8192) nblk = 8192;
+	hipLaunchKernelGGL(k_sentinel_ranks, dim3((unsigned)nblk), dim3(256), 0, h->st, view_of(h), h->acc[1], m2, d_tw, (const int64_t*)dsent,
+			d_tw ? (const int64_t*)nullptr : (const int64_t*)h->pos.p, h->order, dp0, bad + 1);
+	hipLaunchKernelGGL(k_p0_check, dim3((unsigned)((m2 + 255) / 256)), dim3(256), 0, h->st, (const int64_t*)dp0, m2, h->acc[1], bad);
+	HIPCHK(hipEventRecord(h->ev[2], h->st));
+	unsigned long long hb[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(hb, bad, 16, hipMemcpyDeviceToHost, h->st));
+	if (host_p0) HIPCHK(hipMemcpyAsync(host_p0, dp0, (size_t)m2 * 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	const float ms_lf = ev_ms(h->ev[0], h->ev[1]), ms_ranks = ev_ms(h->ev[1], h->ev[2]);
+	if (!counted) h->stt.ms_lf += ms_lf;
+	if (h->opt.verbose >= 3)
+		fprintf(stderr, "[M::%s::%.3f] sentinel ranks of %lld strings in %s order: %.3f ms (+ %.3f ms counts%s)\n", __func__, now_s() - h->t0, (long long)m2,
+				h->order == RB3GPU_SO_RLO ? "RLO" : "RCLO", ms_ranks, ms_lf, d_tw ? " and sentinel positions" : " and row words");
+	if (hb[1] != 0) return RB3GPU_EINVAL; // (a string count that is not the batch's)
+	if (hb[0] != 0) {
+		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] %llu sentinel ranks out of order: the batch is not in the index's string order\n", hb[0]);
+		return RB3GPU_EINTERNAL;
+	}
+	h->p0_live = true, h->p0_n = m2;
+	return 0;
+}
+
+static int order_done(rb3gpu_t *h, int r)
+{
+	h->p0_live = false;
+	return r;
+}
+
+/* the entry points below that honour the handle's string order: p0 first, then the merge as always */
+#define RB3_ORDERED(h, len, d_b2, d_tw, call) RB3_ORDERED_N(h, len, d_b2, d_tw, -1, call)
+#define RB3_ORDERED_N(h, len, d_b2, d_tw, n_strings, call) do { int r_ = order_prepare(h, len, d_b2, d_tw, n_strings); if (r_ < 0) return order_done(h, r_); return order_done(h, (call)); } while (0)
+
+static int merge_plain_dev_impl(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, int commit)
+{
 	bool done = false;
 	const int r = merge_plain_via_tw(h, len, d_bwt, commit, &done);
 	if (r < 0 || done) return r;
 	return merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, 0, nullptr);
+}
+
+int rb3gpu_merge_plain_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, int commit)
+{
+	if (!h || len <= 0 || !d_bwt) return RB3GPU_EINVAL;
+	HIPCHK(hipSetDevice(h->dev));
+	RB3_ORDERED(h, len, d_bwt, nullptr, merge_plain_dev_impl(h, len, d_bwt, commit));
 }
 
 int rb3gpu_merge_plain(rb3gpu_t *h, int64_t len, const uint8_t *bwt)
@@ -2408,10 +2492,7 @@ int rb3gpu_merge_plain(rb3gpu_t *h, int64_t len, const uint8_t *bwt)
 	if (h->n <= 0) return RB3GPU_ESTATE;
 	int r;
 	if ((r = upload_b2(h, len, bwt)) < 0) return r;
-	bool done = false;
-	r = merge_plain_via_tw(h, len, (const uint8_t*)h->b2.p, 1, &done);
-	if (r < 0 || done) return r;
-	return merge_core(h, len, (const uint8_t*)h->b2.p, 1, nullptr, nullptr, 0, 0, nullptr);
+	RB3_ORDERED(h, len, (const uint8_t*)h->b2.p, nullptr, merge_plain_dev_impl(h, len, (const uint8_t*)h->b2.p, 1));
 }
 
 int rb3gpu_merge_plain_walkers(rb3gpu_t *h, int64_t len, const uint8_t *bwt, int64_t n_walkers, const rb3gpu_walker_t *walkers)
@@ -2421,21 +2502,21 @@ int rb3gpu_merge_plain_walkers(rb3gpu_t *h, int64_t len, const uint8_t *bwt, int
 	if (h->n <= 0) return RB3GPU_ESTATE;
 	int r;
 	if ((r = upload_b2(h, len, bwt)) < 0) return r;
-	return merge_core(h, len, (const uint8_t*)h->b2.p, 1, nullptr, nullptr, 0, n_walkers, walkers);
+	RB3_ORDERED(h, len, (const uint8_t*)h->b2.p, nullptr, merge_core(h, len, (const uint8_t*)h->b2.p, 1, nullptr, nullptr, 0, n_walkers, walkers));
 }
 
 int rb3gpu_merge_plain_dev_walkers(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, int64_t n_walkers, const rb3gpu_walker_t *walkers, int commit)
 {
 	if (!h || len <= 0 || !d_bwt || n_walkers <= 0) return RB3GPU_EINVAL;
 	HIPCHK(hipSetDevice(h->dev));
-	return merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_walkers, walkers);
+	RB3_ORDERED(h, len, d_bwt, nullptr, merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_walkers, walkers));
 }
 
 int rb3gpu_merge_text_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, const uint64_t *d_tw, int64_t n_walkers, const rb3gpu_walker_t *walkers, int commit)
 {
 	if (!h || len <= 0 || !d_bwt || !d_tw || n_walkers <= 0) return RB3GPU_EINVAL;
 	HIPCHK(hipSetDevice(h->dev));
-	return merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_walkers, walkers, d_tw);
+	RB3_ORDERED_N(h, len, d_bwt, d_tw, walkers ? -1 : n_walkers, merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_walkers, walkers, d_tw));
 }
 
 /* ... with the walker list made on the device: n_strings strings, a walker at every sentinel and at every multiple of `step` inside a string (the list of
@@ -2444,10 +2525,12 @@ int rb3gpu_merge_text_step_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, c
 {
 	if (!h || len <= 0 || !d_bwt || !d_tw || n_strings <= 0 || n_strings > len || step < 2) return RB3GPU_EINVAL;
 	HIPCHK(hipSetDevice(h->dev));
+	int r = order_prepare(h, len, d_bwt, d_tw, n_strings);
+	if (r < 0) return order_done(h, r);
 	h->mg_sa = d_sa, h->mg_step = step;
-	const int r = merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_strings, nullptr, d_tw);
+	r = merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_strings, nullptr, d_tw);
 	h->mg_sa = nullptr, h->mg_step = 0;
-	return r;
+	return order_done(h, r);
 }
 
 /* the list rb3gpu_merge_text_step_dev walks, copied to the host without its empty slots (tests; *walkers is malloc'ed: rb3gpu_host_free) */
@@ -2462,10 +2545,12 @@ int rb3gpu_merge_text_sa_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, con
 {
 	if (!h || len <= 0 || !d_bwt || !d_tw || n_walkers <= 0) return RB3GPU_EINVAL;
 	HIPCHK(hipSetDevice(h->dev));
+	int r = order_prepare(h, len, d_bwt, d_tw, walkers ? -1 : n_walkers);
+	if (r < 0) return order_done(h, r);
 	h->mg_sa = d_sa; // (NULL: rb3gpu_merge_text_dev)
-	const int r = merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_walkers, walkers, d_tw);
+	r = merge_core(h, len, d_bwt, commit, nullptr, nullptr, 0, n_walkers, walkers, d_tw);
 	h->mg_sa = nullptr;
-	return r;
+	return order_done(h, r);
 }
 
 int rb3gpu_mg_rank_text_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, const uint64_t *d_tw, int64_t n_walkers, const rb3gpu_walker_t *walkers, int64_t *pos, int64_t acc2[RB3GPU_ASIZE+1])
@@ -2473,7 +2558,7 @@ int rb3gpu_mg_rank_text_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, cons
 	if (!h || len <= 0 || !d_bwt || !d_tw || n_walkers <= 0 || !pos) return RB3GPU_EINVAL;
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->n <= 0) return RB3GPU_ESTATE;
-	return merge_core(h, len, d_bwt, 0, pos, acc2, 1, n_walkers, walkers, d_tw);
+	RB3_ORDERED_N(h, len, d_bwt, d_tw, walkers ? -1 : n_walkers, merge_core(h, len, d_bwt, 0, pos, acc2, 1, n_walkers, walkers, d_tw));
 }
 
 int rb3gpu_mg_rank_plain(rb3gpu_t *h, int64_t len, const uint8_t *bwt, int64_t *pos, int64_t acc2[RB3GPU_ASIZE+1])
@@ -2483,7 +2568,7 @@ int rb3gpu_mg_rank_plain(rb3gpu_t *h, int64_t len, const uint8_t *bwt, int64_t *
 	if (h->n <= 0) return RB3GPU_ESTATE;
 	int r;
 	if ((r = upload_b2(h, len, bwt)) < 0) return r;
-	return merge_core(h, len, (const uint8_t*)h->b2.p, 0, pos, acc2, 1, 0, nullptr);
+	RB3_ORDERED(h, len, (const uint8_t*)h->b2.p, nullptr, merge_core(h, len, (const uint8_t*)h->b2.p, 0, pos, acc2, 1, 0, nullptr));
 }
 
 int rb3gpu_mg_rank_plain_walkers(rb3gpu_t *h, int64_t len, const uint8_t *bwt, int64_t n_walkers, const rb3gpu_walker_t *walkers, int64_t *pos, int64_t acc2[RB3GPU_ASIZE+1])
@@ -2493,7 +2578,7 @@ int rb3gpu_mg_rank_plain_walkers(rb3gpu_t *h, int64_t len, const uint8_t *bwt, i
 	if (h->n <= 0) return RB3GPU_ESTATE;
 	int r;
 	if ((r = upload_b2(h, len, bwt)) < 0) return r;
-	return merge_core(h, len, (const uint8_t*)h->b2.p, 0, pos, acc2, 1, n_walkers, walkers);
+	RB3_ORDERED(h, len, (const uint8_t*)h->b2.p, nullptr, merge_core(h, len, (const uint8_t*)h->b2.p, 0, pos, acc2, 1, n_walkers, walkers));
 }
 
 int rb3gpu_rank1a_batch(rb3gpu_t *h, int64_t n, const int64_t *k, int64_t *ok)
@@ -2620,6 +2705,11 @@ static int sort_text_impl(rb3gpu_t *h, int64_t len, const uint8_t *text, uint8_t
 	int r, rounds = 0;
 	if (h->sorter == nullptr && (h->sorter = rb3sort_create()) == nullptr) return RB3GPU_ENOMEM;
 	if ((r = upload_b2(h, len, text)) < 0) return r; // the text, into the batch buffer
+	if (h->order != RB3GPU_SO_IO) { // a sorted string order: the batch's strings into it first (rb3gpu_order.hip)
+		if (h->ows == nullptr && (h->ows = rb3order_create()) == nullptr) return RB3GPU_ENOMEM;
+		r = rb3order_text(h->ows, h->sorter, h->st, len, (uint8_t*)h->b2.p, h->order, nullptr);
+		if (r < 0) return r == -1 ? RB3GPU_ENOMEM : r == -3 ? RB3GPU_ESYMBOL : RB3GPU_ENODEV;
+	}
 	int64_t *d_ck = nullptr;
 	const int64_t nck = step > 0 && ckrow ? (len + step - 1) / step : 0;
 	if (nck > 0) {
@@ -2674,6 +2764,9 @@ struct rb3gpu_sorter_s {
 	int64_t text_len = 0;     // symbols of the text that rb3gpu_sorter_upload left in `text`
 	double ms_upload = 0, ms_sort = 0; // cumulative: text host -> HBM; suffix sorting + BWT + text-order words
 	int64_t n_sorted = 0, n_symbols = 0;
+	int order = RB3GPU_SO_IO;          // rb3gpu_sorter_set_order: the strings of every batch into this order before the sort
+	rb3order_ws *ows = nullptr;
+	double ms_order = 0;
 	pthread_mutex_t mtx;
 	pthread_cond_t cv;
 };
@@ -2711,6 +2804,7 @@ void rb3gpu_sorter_destroy(rb3gpu_sorter_t *s)
 	(void)hipSetDevice(s->dev);
 	(void)hipStreamSynchronize(s->st);
 	rb3sort_destroy(s->ws);
+	rb3order_destroy(s->ows);
 	void *all[] = { s->text, s->ck, s->out[0], s->out[1] };
 	for (void *p : all) if (p) (void)hipFree(p);
 	for (int i = 0; i < 2; ++i) if (s->stage[i]) { (void)hipHostFree(s->stage[i]); (void)hipEventDestroy(s->done[i]); }
@@ -2819,7 +2913,15 @@ static int sorter_sort_uploaded(rb3gpu_sorter_t *s, int64_t len, void **d_bwt, i
 		sorter_give_back(s, slot); // (or the next two calls would wait for it for ever)
 		return r;
 	}
-	const double t_so = now_s();
+	double t_so = now_s();
+	if (s->order != RB3GPU_SO_IO) { // a sorted string order: the batch's strings into it first, in the sorter's text buffer (rb3gpu_order.hip)
+		r = s->ows == nullptr && (s->ows = rb3order_create()) == nullptr ? -1 : rb3order_text(s->ows, s->ws, s->st, len, (uint8_t*)s->text, s->order, nullptr);
+		s->ms_order += (now_s() - t_so) * 1e3, t_so = now_s();
+		if (r < 0) {
+			sorter_give_back(s, slot);
+			return r == -1 ? RB3GPU_ENOMEM : r == -3 ? RB3GPU_ESYMBOL : RB3GPU_ENODEV;
+		}
+	}
 	r = rb3sort_bwt(s->ws, s->st, len, (const uint8_t*)s->text, (uint8_t*)s->out[slot], step, nck > 0 ? (int64_t*)s->ck : nullptr, &rounds,
 			d_tw ? (uint64_t*)((uint8_t*)s->out[slot] + tw_off) : nullptr, d_sa ? (uint32_t*)((uint8_t*)s->out[slot] + tw_off + (size_t)len * 8) : nullptr);
 	s->ms_sort += (now_s() - t_so) * 1e3, s->n_sorted += 1, s->n_symbols += len;
@@ -2934,6 +3036,53 @@ int rb3gpu_sorter_stats(const rb3gpu_sorter_t *s, double *ms_upload, double *ms_
 	if (n_batches) *n_batches = s->n_sorted;
 	if (n_symbols) *n_symbols = s->n_symbols;
 	return 0;
+}
+
+int rb3gpu_sorter_order_stats(const rb3gpu_sorter_t *s, double *ms_order)
+{
+	if (!s || !ms_order) return RB3GPU_EINVAL;
+	*ms_order = s->ms_order;
+	return 0;
+}
+
+int rb3gpu_sorter_set_order(rb3gpu_sorter_t *s, int so)
+{
+	if (!s || so < RB3GPU_SO_IO || so > RB3GPU_SO_RCLO) return RB3GPU_EINVAL;
+	s->order = so;
+	return 0;
+}
+
+int rb3gpu_set_order(rb3gpu_t *h, int so)
+{
+	if (!h || so < RB3GPU_SO_IO || so > RB3GPU_SO_RCLO) return RB3GPU_EINVAL;
+	h->order = so;
+	return 0;
+}
+
+int rb3gpu_get_order(const rb3gpu_t *h)
+{
+	return h ? h->order : RB3GPU_EINVAL;
+}
+
+int rb3gpu_order_strings_dev(rb3gpu_t *h, int64_t len, uint8_t *d_text, int so)
+{
+	if (!h || !d_text || len <= 0 || len >= (1LL << 31) || (so != RB3GPU_SO_RLO && so != RB3GPU_SO_RCLO)) return RB3GPU_EINVAL;
+	HIPCHK(hipSetDevice(h->dev));
+	if (h->sorter == nullptr && (h->sorter = rb3sort_create()) == nullptr) return RB3GPU_ENOMEM;
+	if (h->ows == nullptr && (h->ows = rb3order_create()) == nullptr) return RB3GPU_ENOMEM;
+	const double t0 = now_s();
+	const int r = rb3order_text(h->ows, h->sorter, h->st, len, d_text, so, nullptr);
+	if (r < 0) return r == -1 ? RB3GPU_ENOMEM : r == -3 ? RB3GPU_ESYMBOL : RB3GPU_ENODEV;
+	if (h->opt.verbose >= 3) fprintf(stderr, "[M::%s::%.3f] ordered the strings of %lld symbols in %.3f ms\n", __func__, now_s() - h->t0, (long long)len, (now_s() - t0) * 1e3);
+	return 0;
+}
+
+int rb3gpu_sentinel_ranks_dev(rb3gpu_t *h, int64_t len, const uint8_t *d_bwt, const uint64_t *d_tw, int64_t n_strings, int64_t *p0)
+{
+	if (!h || len <= 0 || !d_bwt || n_strings <= 0 || n_strings > len || !p0) return RB3GPU_EINVAL;
+	if (h->order == RB3GPU_SO_IO) return RB3GPU_ESTATE;
+	HIPCHK(hipSetDevice(h->dev));
+	return order_done(h, order_prepare(h, len, d_bwt, d_tw, n_strings, p0));
 }
 
 int rb3gpu_sorter_release(rb3gpu_sorter_t *s, void *d_bwt)
@@ -3343,6 +3492,7 @@ int rb3gpu_from_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, c
 int rb3gpu_merge_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, const int64_t mcnt[RB3GPU_ASIZE])
 {
 	if (!h || n_words < 8 || !words) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->n <= 0) return RB3GPU_ESTATE;
 	int64_t n_sym = 0;
@@ -3357,6 +3507,8 @@ int rb3gpu_merge_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, 
 int rb3gpu_merge_index(rb3gpu_t *h, rb3gpu_t *src)
 {
 	if (!h || !src || h == src) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
+	RB3_IO_ONLY(src);
 	if (h->n <= 0 || h->grp == nullptr || src->n <= 0 || src->grp == nullptr) return RB3GPU_ESTATE;
 	const int64_t n = src->n;
 	int r;
@@ -3420,6 +3572,7 @@ int rb3gpu_sh_step(rb3gpu_t *h, int64_t n_states, const rb3gpu_state_t *d_in, co
 {
 	if (!h || n_states < 0 || !d_tw || !d_ka || !adj || !iv_bounds || !counts || n_iv < 1 || n_iv > RB3_SH_MAXIV || my_iv < 0 || my_iv >= n_iv) return RB3GPU_EINVAL;
 	if (n_states > 0 && (!d_in || !d_send)) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->grp == nullptr) return RB3GPU_ESTATE;
 	for (int i = 0; i <= n_iv; ++i) counts[i] = 0;
@@ -3472,6 +3625,7 @@ int rb3gpu_sh_step(rb3gpu_t *h, int64_t n_states, const rb3gpu_state_t *d_in, co
 int rb3gpu_sh_finish(rb3gpu_t *h, int64_t jlo, int64_t n_rows, const uint8_t *d_bwt, const int64_t *d_ka, int64_t iv_start, int commit)
 {
 	if (!h || jlo < 0 || n_rows < 0 || !d_bwt || !d_ka) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
 	HIPCHK(hipSetDevice(h->dev));
 	if (h->grp == nullptr) return RB3GPU_ESTATE;
 	if (n_rows == 0) return 0; // nothing landed in this interval
@@ -3919,6 +4073,7 @@ int rb3gpu_sh_merge(rb3gpu_t *h, const rb3gpu_comm_t *comm, int64_t *iv_bounds, 
 {
 	if (!h || !comm || !iv_bounds || len <= 0 || !d_bwt || !d_tw || n_chains <= 0 || n_chains > len || !chain_tp) return RB3GPU_EINVAL;
 	if (comm->world < 1 || comm->world > RB3_SH_MAXIV || comm->rank < 0 || comm->rank >= comm->world || !comm->all_gather || (comm->world > 1 && !comm->all_to_all)) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
 	const int r = sh_merge_impl(h, comm, iv_bounds, len, d_bwt, d_tw, n_chains, chain_tp, commit, n_rounds);
 	if (r < 0 && comm->abort) comm->abort(comm->ctx); // the other ranks are (or will be) waiting in a collective
 	return r;
@@ -3931,6 +4086,7 @@ int rb3gpu_sh_merge_text(rb3gpu_t *h, const rb3gpu_comm_t *comm, int64_t *iv_bou
 {
 	if (!h || !comm || !iv_bounds || len <= 0 || !d_tprev || !d_tw_slice || n_chains <= 0 || n_chains > len || !chain_tp) return RB3GPU_EINVAL;
 	if (comm->world < 1 || comm->world > RB3_SH_MAXIV || comm->rank < 0 || comm->rank >= comm->world || !comm->all_gather || (comm->world > 1 && !comm->all_to_all)) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
 	const int64_t w = comm->world, q = comm->rank;
 	const int64_t t_lo = len / w * q + (len % w) * q / w, t_hi = q + 1 == w ? len : len / w * (q + 1) + (len % w) * (q + 1) / w;
 	const int r = sh_merge_impl(h, comm, iv_bounds, len, nullptr, d_tw_slice, n_chains, chain_tp, commit, n_rounds, d_tprev, t_lo, t_hi);

@@ -658,6 +658,7 @@ static void shard_free(rb3gpu_shard_s *s, bool handles)
 rb3gpu_shard_t *rb3gpu_shard_split(rb3gpu_t *h0, int n, const int *devices, const rb3gpu_opt_t *opt)
 {
 	if (!h0 || !devices || !opt || n < 1 || n > RB3GPU_SH_MAXIV || devices[0] != rb3gpu_device_of(h0)) return nullptr;
+	if (rb3gpu_get_order(h0) != RB3GPU_SO_IO) return nullptr; // (the interval merge walks in input order only)
 	const int64_t tot = rb3gpu_get_tot(h0);
 	if (tot < n) return nullptr;
 	rb3gpu_shard_s *s = new (std::nothrow) rb3gpu_shard_s;

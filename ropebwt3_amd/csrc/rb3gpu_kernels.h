@@ -42,7 +42,16 @@ struct IdxView {
 	                         // writers have always stored -- and the rest comes from the table `sb` (lf_base): the same two lines per rank at any size.  0: headers
 	                         // relative to the group (rb3gpu_tune abs_limit; the layout of 2^32 symbols and more in rounds 3-5)
 	const uint64_t *sb;      // abs = 2: sb[s * 8 + c] = the LF base of c at position s << 31, i.e. the counts of directory entry s << 18 (k_sb_table): a few hundred bytes
+	const int64_t *p0;       // a merge in a sorted string order (RLO / RCLO): the insertion point of the sentinel of string i of the batch is p0[i], not m (k_sentinel_ranks); NULL: m
+	int64_t p0n;             // entries of p0 (the batch's strings): a row beyond them is no sentinel, whatever a caller's walker list says
 };
+
+/* where the walker of sentinel row kb starts: p0[kb] in a sorted order, acc[1] of the index otherwise (and for a row that is no sentinel row:
+ * a caller's list that says otherwise gets the input order's value, which the LF check of the merge then refuses, as it always has) */
+__device__ __forceinline__ int64_t sentinel_ka(const IdxView &ix, int64_t kb)
+{
+	return ix.p0 != nullptr && (uint64_t)kb < (uint64_t)ix.p0n ? ix.p0[kb] : ix.m;
+}
 
 /* the LF base from a slot header.  wrap = 0: T + hdr (T = 0: the header is the base; T = the group's count: the header is relative to the group).  wrap = 1
  * (IdxView.abs = 2): the header holds the low 32 bits of the base and T is the base 2^31 symbols or less further down -- a base grows by at most one per symbol,
@@ -426,6 +435,58 @@ __global__ void __launch_bounds__(256) k_rank_batch(IdxView ix, Acc7 acc, int64_
 			if (j == 0) ok[q * 6 + c] = v;
 		}
 	}
+}
+
+/* ----------------------------------------------------------------------------------------- */
+/* sorted string orders (RLO / RCLO): where the sentinels of an ordered batch go               */
+/* ----------------------------------------------------------------------------------------- */
+
+/* p0[i] = the number of index strings that sort before string i of the batch in order so (1 RLO: $ < A < C < G < T < N on the reversed
+ * strings; 2 RCLO: $ < T < G < C < A < N), a new string before identical old ones -- the backward search of mr_insert_multi_aux
+ * (mrope.c:224-270) over B1: the interval [l, u) of the sentinel rows whose strings end like string i so far, p the rows that sort before
+ * it.  One octet per string.  The string's symbols, last to first: tw given, tw[t] & 7 going left from its sentinel at sent[i] (text-order
+ * words); else the row words of the batch (lf_build: B2 | LF_B2 << 3), from row i (the sentinel of string i is row i). */
+__device__ __forceinline__ bool so_before(int a, int c, int so) // does symbol a (1..4) sort before c (1..5) in order so?
+{
+	if (c == 5) return true;
+	return so == 2 ? a > c : a < c;
+}
+
+__global__ void __launch_bounds__(256) k_sentinel_ranks(IdxView ix, int64_t m1, int64_t m2, const uint64_t *tw, const int64_t *sent, const int64_t *rows,
+		int so, int64_t *p0, unsigned long long *bad)
+{
+	const int lane = threadIdx.x & 63, j = lane & 7;
+	int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+	const int64_t stride = ((int64_t)gridDim.x * blockDim.x) >> 3;
+	for (; q < m2; q += stride) {
+		int64_t l = 0, u = m1, p = 0, t = tw ? sent[q] : 0, kb = q;
+		if (tw && t < 0) { if (j == 0) atomicAdd(bad, 1ull); continue; } // (a string count that is not the batch's)
+		for (;;) {
+			int c;
+			if (tw) c = t >= 0 ? (int)(tw[t] & 7u) : 0, --t;
+			else { const uint64_t x = (uint64_t)rows[kb]; c = (int)(x & 7u), kb = RB3_ROW_NEXT(x); }
+			if (l >= u || c == 0) break; // ties with identical old strings: the new one goes first (mrope.c:240; the bytes are the same either way)
+			RankLoad rl, ru;
+			oct_rank_issue(ix, l, j, rl);
+			oct_rank_issue(ix, u, j, ru);
+			int64_t add = 0, nl = 0, nu = 0;
+#pragma unroll
+			for (int a = 0; a < 6; ++a) {
+				const int64_t x = oct_rank_finish(rl, a, j, ix.abs), y = oct_rank_finish(ru, a, j, ix.abs);
+				if (a == 0 || (a <= 4 && so_before(a, c, so))) add += y - x;
+				if (a == c) nl = x, nu = y;
+			}
+			p += add, l = nl, u = nu;
+		}
+		if (j == 0) p0[q] = p;
+	}
+}
+
+/* p0 must not decrease along the batch (its strings are in the same order): anything else would be a wrong index */
+__global__ void __launch_bounds__(256) k_p0_check(const int64_t *p0, int64_t m2, int64_t m1, unsigned long long *bad)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < m2 && (p0[i] < 0 || p0[i] > m1 || (i > 0 && p0[i] < p0[i - 1]))) atomicAdd(bad, 1ull);
 }
 
 /* ----------------------------------------------------------------------------------------- */
@@ -1234,6 +1295,7 @@ __global__ void __launch_bounds__(256, RB3_CHAIN_WPE) k_chain(IdxView b1, int64_
 			wcur = (uint32_t)wid;
 			if (TENT && TEXT && LIST && jmet != nullptr && j == 0) jmet[wid] = 0; // (every list entry is taken by exactly one octet: the table needs no clearing)
 			int probe = 0; // TEXT: text distance to a row of the right neighbour's segment that tells whether this walker comes too late (below)
+			bool sent0 = false; // a walker that starts at a sentinel
 			if (LIST) {
 				const Walker w = wl[wid];
 				kb = w.row, remaining = w.nsteps;
@@ -1247,11 +1309,12 @@ __global__ void __launch_bounds__(256, RB3_CHAIN_WPE) k_chain(IdxView b1, int64_
 				}
 				if (TEXT) tp = w.row;
 				if (w.ka0 >= 0) lo = hi = w.ka0;
-				else if (w.ka0 == -2) lo = hi = b1.m; // RB3GPU_KA_SENTINEL: a sentinel row, ka = acc[1] of the index (fm-index.c:164)
+				else if (w.ka0 == -2) lo = hi = !TEXT ? sentinel_ka(b1, kb) : b1.m; // RB3GPU_KA_SENTINEL: a sentinel row, ka = acc[1] of the index (fm-index.c:164), or p0 of its string (TEXT: below, once the row is known)
 				else lo = 0, hi = b1.n;
+				sent0 = w.ka0 == -2;
 			} else {
 				remaining = INT64_MAX;
-				if (wid < m2) kb = wid, lo = hi = b1.m;
+				if (wid < m2) kb = wid, lo = hi = sentinel_ka(b1, wid);
 				else kb = first_marked + ((wid - m2) << logM), lo = 0, hi = b1.n;
 			}
 			gap = hi - lo > 1 ? 2 : (int)(hi - lo);
@@ -1263,6 +1326,7 @@ __global__ void __launch_bounds__(256, RB3_CHAIN_WPE) k_chain(IdxView b1, int64_
 					blk8 = tw[a > 0 ? a : 0];
 				}
 				kb = (int64_t)(x >> 3);
+				if (sent0 && b1.p0) lo = hi = sentinel_ka(b1, kb); // (the sentinel's row is its string's number)
 				rc = (uint64_t)ld_pos(&row[trec ? tp : kb]);
 				if (gap && (int64_t)rc >= 0) continue;
 				// A walker that starts LATE (its wave was not resident when the kernel began: it starts when the first waves finish, i.e.
@@ -2726,7 +2790,7 @@ __global__ void __launch_bounds__(256) k_lf_check(IdxView b1, const int64_t *pos
 	const int64_t ka = pos[kb] - kb;
 	const int c = (int)b2[kb];
 	bool ok = ka >= 0 && ka <= b1.n && c <= 5;
-	if (kb < m2 && ka != b1.m) ok = false; // a sentinel row
+	if (kb < m2 && ka != sentinel_ka(b1, kb)) ok = false; // a sentinel row
 	if (ok && c != 0) {
 		const int64_t tile = kb >> 12, base = tile << 12;
 		const int r = (int)(kb - base);

@@ -127,6 +127,12 @@ SYMBOLS = {
     "rb3gpu_ipc_peer_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_ipc_peer_disable": (None, [ctypes.c_void_p]),
     "rb3gpu_merge_text_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "rb3gpu_set_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rb3gpu_get_order": (ctypes.c_int, [ctypes.c_void_p]),
+    "rb3gpu_sorter_set_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rb3gpu_sorter_order_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    "rb3gpu_order_strings_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int]),
+    "rb3gpu_sentinel_ranks_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "rb3gpu_walkers_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_shard_split": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_shard_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
@@ -158,6 +164,11 @@ class CommStruct(ctypes.Structure):
                 ("peer_export", ctypes.c_void_p), ("peer_import", ctypes.c_void_p)]
 
 _libs = {}
+
+
+# string orders of an index (include/rb3gpu.h RB3GPU_SO_*; mrope.h MR_SO_*): input order, reverse lexicographic (build -s), reverse
+# complement lexicographic (build -r)
+SO_IO, SO_RLO, SO_RCLO = 0, 1, 2
 
 
 def load_library(hooks=False, path=None):
@@ -270,6 +281,16 @@ class Sorter:
 
     def release(self, d_bwt):
         self._chk(self._lib.rb3gpu_sorter_release(self._s, d_bwt), "rb3gpu_sorter_release")
+
+    def set_order(self, so):
+        """every batch sorted from now on is first put into string order so (SO_IO, SO_RLO, SO_RCLO) on the device"""
+        self._chk(self._lib.rb3gpu_sorter_set_order(self._s, int(so)), "rb3gpu_sorter_set_order")
+
+    def order_ms(self):
+        """cumulative milliseconds spent putting batches into order (not part of stats()["ms_sort"])"""
+        ms = ctypes.c_double()
+        self._chk(self._lib.rb3gpu_sorter_order_stats(self._s, ctypes.byref(ms)), "rb3gpu_sorter_order_stats")
+        return ms.value
 
     def stats(self):
         up, so, nb, ns = ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
@@ -417,6 +438,35 @@ class Rb3Gpu:
     def merge_index(self, other):
         """merge the whole index of another handle (any GPU of the node) into this one (rb3_fmi_merge, fm-index.c:251-277)"""
         self._chk(self._lib.rb3gpu_merge_index(self._h, other._h), "rb3gpu_merge_index")
+
+    def set_order(self, so):
+        """the string order of the index (SO_IO, SO_RLO, SO_RCLO): batches sorted by this handle are put into it first, merged batches
+        must be in it (their sentinels go among the index's strings, not behind them)"""
+        self._chk(self._lib.rb3gpu_set_order(self._h, int(so)), "rb3gpu_set_order")
+
+    def get_order(self):
+        return int(self._lib.rb3gpu_get_order(self._h))
+
+    def order_strings_dev(self, d_text, length, so):
+        """rb3gpu_order_strings_dev: a batch text in device memory reordered in place into string order so (SO_RLO or SO_RCLO)"""
+        self._chk(self._lib.rb3gpu_order_strings_dev(self._h, int(length), d_text, int(so)), "rb3gpu_order_strings_dev")
+
+    def order_strings(self, text, so):
+        """a batch text (host) put into string order so on the device: the reordered text"""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        d = self.dev_upload(text)
+        try:
+            self.order_strings_dev(d, text.size, so)
+            return self.dev_download(d, text.size)
+        finally:
+            self.dev_free(d)
+
+    def sentinel_ranks_dev(self, d_bwt, d_tw, length, n_strings):
+        """rb3gpu_sentinel_ranks_dev: p0 of the next merge of an ordered batch (n_strings strings) in the handle's order, as an int64 array;
+        d_tw None: the strings are read through the batch's BWT"""
+        p0 = np.empty(int(n_strings), dtype=np.int64)
+        self._chk(self._lib.rb3gpu_sentinel_ranks_dev(self._h, int(length), d_bwt, d_tw, int(n_strings), p0.ctypes.data), "rb3gpu_sentinel_ranks_dev")
+        return p0
 
     def export_plain_dev(self, d_out):
         self._chk(self._lib.rb3gpu_export_plain_dev(self._h, d_out), "rb3gpu_export_plain_dev")
