@@ -461,6 +461,21 @@ int rb3gpu_shard_rebalance(rb3gpu_shard_t *s, int pct);
 rb3gpu_t *rb3gpu_shard_handle(rb3gpu_shard_t *s, int i);
 int rb3gpu_shard_bounds(const rb3gpu_shard_t *s, int64_t *bounds);
 
+/* k-mer counting over one or more indexes (`ropebwt3 kount`, main.c:333-423 of the reference): every k-mer over A C G T (no $, no N)
+ * that occurs at least min_occ times in SOME index of hs[0..n_idx), with its count in every index (0 where it does not occur); all 4^k
+ * k-mers for min_occ <= 0.  The trie is expanded one depth at a time on the device of hs[0], on its stream, after the pending work of
+ * every handle; all handles must be on one device.  Results reach cb in the reference's output order, in chunks:
+ *   kmers   n_out * k symbols, 1..4 = A C G T, k-mer r at kmers[r * k]
+ *   counts  n_out * n_idx, the counts of k-mer r at counts[r * n_idx]
+ * (host memory that is valid during the call only).  A nonzero return from cb stops the walk and is returned.  max_level_nodes caps the
+ * nodes of one depth held at once (0: a share of the free device memory); a depth whose children exceed it is walked in slices, each to
+ * the end, which changes nothing in the output.  RB3GPU_EINVAL for k < 1, n_idx < 1, a NULL callback or handles on different devices;
+ * RB3GPU_ESTATE for a handle without an index.  st (may be NULL): ms_total wall time of the call, ms_expand the expansion kernel alone
+ * (HIP events), n_nodes nodes expanded (rank pairs: n_nodes * n_idx), n_out k-mers, n_slices 1 + the times a depth was cut */
+typedef int (*rb3gpu_kount_cb)(void *ud, int64_t n_out, int n_idx, int k, const uint8_t *kmers, const int64_t *counts);
+typedef struct { double ms_total, ms_expand; int64_t n_nodes, n_out, n_slices; } rb3gpu_kount_stats_t;
+int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t max_level_nodes, rb3gpu_kount_cb cb, void *ud, rb3gpu_kount_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);

@@ -1262,6 +1262,113 @@ int main_ssa(int argc, char *argv[])
 	return ret == 0 ? 0 : 1;
 }
 
+/* kount: the k-mers that occur at least -m times in some index, with their count in every index (the reference's main_kount,
+ * main.c:333-423), counted on the GPU (rb3gpu_kount).  The lines are formatted here, into a buffer written in large pieces.
+ * One difference: -k below 1 is refused (the reference crashes on -k 0). */
+typedef struct { FILE *fp; char *buf; size_t l, m; int err; double t_fmt; } kount_out_t;
+
+static void kount_flush(kount_out_t *o)
+{
+	if (o->l > 0 && fwrite(o->buf, 1, o->l, o->fp) != o->l) o->err = 1;
+	o->l = 0;
+}
+
+static int kount_sink(void *ud, int64_t n, int n_idx, int k, const uint8_t *kmers, const int64_t *counts)
+{
+	kount_out_t *o = (kount_out_t*)ud;
+	const double t0 = rb3h_realtime();
+	const size_t line_max = (size_t)k + (size_t)n_idx * 21 + 1;
+	int64_t r;
+	int i, p;
+	for (r = 0; r < n; ++r) {
+		const uint8_t *s = kmers + r * k;
+		char *b;
+		if (o->l + line_max > o->m) kount_flush(o);
+		b = o->buf + o->l;
+		for (p = 0; p < k; ++p) b[p] = "$ACGTN"[s[p] < 6 ? s[p] : 5];
+		b += k;
+		for (i = 0; i < n_idx; ++i) { /* "\t%ld" */
+			int64_t x = counts[r * n_idx + i];
+			char t[24];
+			int nt = 0, neg = x < 0;
+			uint64_t u = neg ? (uint64_t)0 - (uint64_t)x : (uint64_t)x;
+			do t[nt++] = (char)('0' + u % 10), u /= 10; while (u);
+			*b++ = '\t';
+			if (neg) *b++ = '-';
+			while (nt > 0) *b++ = t[--nt];
+		}
+		*b++ = '\n';
+		o->l = (size_t)(b - o->buf);
+	}
+	o->t_fmt += rb3h_realtime() - t0;
+	return o->err ? -1 : 0;
+}
+
+static int main_kount(int argc, char *argv[])
+{
+	int c, k = 51, min_occ = 100, device = 0, n, i, ret;
+	rb3gpu_t **hs;
+	rb3gpu_opt_t gopt;
+	rb3gpu_kount_stats_t st;
+	kount_out_t o;
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "k:m:", long_opts, 0)) >= 0) {
+		if (c == 'k') k = (int)atol(optarg); /* (an int, as in the reference) */
+		else if (c == 'm') min_occ = (int)atol(optarg);
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+		else if (c == '?') return 1;
+	}
+	if (argc == optind) {
+		fprintf(stderr, "Usage: ropebwt3-amd kount [options] <in1.fmd> [in2.fmd [...]]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -k INT     k-mer length [%d]\n", k);
+		fprintf(stderr, "  -m INT     min k-mer occurrence [%d]\n", min_occ);
+		fprintf(stderr, "  --gpu INT  HIP device ordinal [0]\n");
+		return 1;
+	}
+	if (k < 1) {
+		fprintf(stderr, "ERROR: the k-mer length (-k) must be at least 1\n");
+		return 1;
+	}
+	n = argc - optind;
+	hs = (rb3gpu_t**)calloc((size_t)n, sizeof(*hs));
+	if (hs == 0) return 1;
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	for (i = 0, ret = 0; i < n && ret == 0; ++i) {
+		hs[i] = rb3gpu_create(&gopt);
+		if (hs[i] == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); ret = 1; }
+		else if (load_index(hs[i], argv[optind + i]) < 0) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind + i]);
+			ret = 1;
+		}
+	}
+	if (ret == 0) {
+		if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded %d index(es)\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), n);
+		o.fp = stdout, o.l = 0, o.err = 0, o.t_fmt = 0;
+		o.m = (size_t)k + (size_t)n * 21 + 1;
+		o.m = o.m < ((size_t)1 << 20) ? (size_t)1 << 20 : o.m * 2;
+		o.buf = (char*)malloc(o.m);
+		if (o.buf == 0) ret = 1;
+		else {
+			const int r = rb3gpu_kount(hs, n, k, min_occ, 0, kount_sink, &o, &st);
+			kount_flush(&o);
+			if (fflush(stdout) != 0) o.err = 1;
+			if (r != 0 && !o.err) fprintf(stderr, "ERROR: the GPU engine failed to count the k-mers: %s\n", rb3gpu_strerror(r));
+			else if (o.err) fprintf(stderr, "ERROR: failed to write the output\n");
+			else if (rb3h_verbose >= 3)
+				fprintf(stderr, "[M::%s::%.3f*%.2f] %lld k-mers; %lld nodes expanded in %lld slice(s): %.3f ms in the engine, of which %.3f ms formatting lines; expansion kernel %.3f ms\n",
+						__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_out, (long long)st.n_nodes, (long long)st.n_slices, st.ms_total, o.t_fmt * 1e3, st.ms_expand);
+			ret = r != 0 || o.err ? 1 : 0;
+			free(o.buf);
+		}
+	}
+	for (i = 0; i < n; ++i) if (hs[i]) rb3gpu_destroy(hs[i]);
+	free(hs);
+	return ret;
+}
+
 /* recode: decode an FMD/FMR file on the host and write it back as plain text (default), FMD (-d)
  * or FMR (-b).  Host-only utility; also the CPU-side test bench of the two codecs. */
 typedef struct { int64_t cnt[6]; runvec_t rv; } recode_t;
@@ -1360,6 +1467,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    build      construct a BWT (merge path on an MI355X)\n");
 	fprintf(fp, "    merge      merge BWTs (on an MI355X)\n");
 	fprintf(fp, "    ssa        generate sampled suffix array (on an MI355X)\n");
+	fprintf(fp, "    kount      count k-mers in one or more FM-indexes (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
 	fprintf(fp, "    plain2fmd  convert BWT in plain text to FMD (host only)\n");
 	fprintf(fp, "    version    print the version number\n");
@@ -1375,6 +1483,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "build") == 0) ret = main_build(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "merge") == 0) ret = main_merge(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "ssa") == 0) ret = main_ssa(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "kount") == 0) ret = main_kount(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "plain2fmd") == 0) ret = main_plain2fmd(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "version") == 0) { printf("%s\n", RB3H_VERSION); return 0; }

@@ -24,6 +24,7 @@
 #include "rb3gpu_kernels.h"
 #include "rb3gpu_planes.h"
 #include "rb3gpu_part.h"
+#include "rb3gpu_kount.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
 		if (h && h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); \
@@ -4206,6 +4207,213 @@ int rb3gpu_sync(rb3gpu_t *h)
 	HIPCHK(hipSetDevice(h->dev));
 	HIPCHK(hipStreamSynchronize(h->st));
 	return 0;
+}
+
+/* ---- kount: k-mer counting over one or more indexes (rb3gpu_kount.h) ------------------------- */
+
+int rb3kount_scan(void *tmp, size_t *tmp_bytes, const uint32_t *cnt, int64_t *off, int64_t n, hipStream_t st); // rb3gpu_kount.hip
+
+#define RB3_KOUNT_OUT_CHUNK ((int64_t)1 << 20) // output records per callback at most
+#define RB3_KOUNT_SYNC_UB   ((int64_t)1 << 20) // a frontier bounded by this many nodes is expanded without asking the host for its count
+
+/* the buffers of one depth: its frontier (codes, intervals) and the scratch of its expansion (child intervals, counts, their scan,
+ * the split of a slice); one allocation, grown on demand (what it held is dead by then: the walk below it has finished) */
+struct KountLevel { void *p = nullptr; int64_t cap = 0; uint64_t *code = nullptr; int64_t *iv = nullptr, *ci = nullptr, *off = nullptr, *sc = nullptr; uint32_t *cnt = nullptr; };
+
+struct KountWs {
+	std::vector<KountLevel> lv;
+	IdxView *tab = nullptr;
+	int64_t *misc = nullptr;       // [0]: the count of the root frontier, [1]: nodes expanded
+	void *tmp = nullptr;           // scan scratch
+	size_t tmp_bytes = 0;
+	uint8_t *d_out = nullptr, *h_out = nullptr;
+	int64_t out_cap = 0;
+	int64_t *h_small = nullptr;    // page-locked landing place of the counts the host asks for
+	std::vector<hipEvent_t> ev;    // pairs around k_kount_expand, read at the next synchronisation
+	size_t ev_used = 0;
+	~KountWs()
+	{
+		for (auto &l : lv) if (l.p) (void)hipFree(l.p);
+		if (tab) (void)hipFree(tab);
+		if (misc) (void)hipFree(misc);
+		if (tmp) (void)hipFree(tmp);
+		if (d_out) (void)hipFree(d_out);
+		if (h_out) (void)hipHostFree(h_out);
+		if (h_small) (void)hipHostFree(h_small);
+		for (auto e : ev) (void)hipEventDestroy(e);
+	}
+};
+
+static int kount_level_ensure(rb3gpu_t *h, KountLevel &l, int64_t need, int64_t cap, int W, int ni)
+{
+	if (l.cap >= need) return 0;
+	const int64_t c = std::max(need, std::min(cap, 2 * l.cap));
+	if (l.p) {
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipFree(l.p));
+		l.p = nullptr, l.cap = 0;
+	}
+	const size_t bytes = (size_t)c * (8 * W + 16 * ni + 64 * ni) + (size_t)(c + 1) * 12 + 64;
+	HIPCHK(hipMalloc(&l.p, bytes));
+	l.cap = c;
+	l.code = (uint64_t*)l.p;
+	l.iv = (int64_t*)(l.code + c * W);
+	l.ci = l.iv + c * ni * 2;
+	l.off = l.ci + c * ni * 8;
+	l.sc = l.off + (c + 1);
+	l.cnt = (uint32_t*)(l.sc + 4);
+	return 0;
+}
+
+int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t max_level_nodes, rb3gpu_kount_cb cb, void *ud, rb3gpu_kount_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!hs || n_idx < 1 || k < 1 || !cb || max_level_nodes < 0) return RB3GPU_EINVAL;
+	for (int i = 0; i < n_idx; ++i)
+		if (!hs[i] || hs[i]->dev != hs[0]->dev) return RB3GPU_EINVAL;
+	for (int i = 0; i < n_idx; ++i)
+		if (hs[i]->n <= 0 || hs[i]->grp == nullptr) return RB3GPU_ESTATE;
+	rb3gpu_t *h = hs[0];
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	for (int i = 0; i < n_idx; ++i) {
+		HIPCHK(hipStreamSynchronize(hs[i]->st));
+		HIPCHK(hipStreamSynchronize(hs[i]->st2));
+	}
+	const int ni = n_idx, W = (k + 31) / 32;
+	const int64_t node_bytes = 8LL * W + 80LL * ni + 12;
+	// the level cap: a frontier of at most `cap` nodes.  A sliced walk holds up to k of them, so by default k + 1 of them take half the free memory
+	int64_t cap = max_level_nodes;
+	if (cap == 0) {
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
+		cap = (int64_t)(fr / 2 / ((size_t)node_bytes * (size_t)(k + 1)));
+		if (cap < 4096) cap = 4096;
+	}
+	if (cap < 4) cap = 4; // (a parent has up to four children: every slice takes at least one)
+	const int64_t lim_out = std::min(cap, RB3_KOUNT_OUT_CHUNK), sync_ub = std::min(cap, RB3_KOUNT_SYNC_UB);
+	KountWs ws;
+	ws.lv.resize((size_t)k);
+	std::vector<IdxView> hv((size_t)ni);
+	for (int i = 0; i < ni; ++i) hv[i] = view_of(hs[i]);
+	HIPCHK(hipMalloc(&ws.tab, sizeof(IdxView) * ni));
+	HIPCHK(hipMemcpyAsync(ws.tab, hv.data(), sizeof(IdxView) * ni, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMalloc(&ws.misc, 64));
+	HIPCHK(hipMemsetAsync(ws.misc, 0, 64, h->st));
+	HIPCHK(hipHostMalloc((void**)&ws.h_small, 64, hipHostMallocDefault));
+	{
+		int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, cap + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
+	}
+	double ms_expand = 0;
+	auto ev_get = [&]() -> hipEvent_t {
+		if (ws.ev_used == ws.ev.size()) {
+			hipEvent_t e;
+			if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+			ws.ev.push_back(e);
+		}
+		return ws.ev[ws.ev_used++];
+	};
+	auto harvest = [&]() { // (after a synchronisation of the stream)
+		for (size_t i = 0; i + 1 < ws.ev_used; i += 2) ms_expand += ev_ms(ws.ev[i], ws.ev[i + 1]);
+		ws.ev_used = 0;
+	};
+	auto grid = [](int64_t threads) { int64_t nb = (threads + 255) / 256; return (unsigned)(nb < 1 ? 1 : nb > 16384 ? 16384 : nb); };
+	// child intervals, kept counts and their scan of the frontier of depth d (count at *pn, at most nub nodes)
+	auto expand = [&](int d, const int64_t *pn, int64_t nub) -> int {
+		KountLevel &P = ws.lv[d];
+		hipEvent_t e0 = ev_get(), e1 = e0 ? ev_get() : nullptr;
+		if (e1) HIPCHK(hipEventRecord(e0, h->st));
+		hipLaunchKernelGGL(k_kount_expand, dim3(grid((nub + 1) * ni * 8)), dim3(256), 0, h->st, (const IdxView*)ws.tab, ni, pn, nub, (const int64_t*)P.iv, P.ci,
+				P.cnt, min_occ, (unsigned long long*)(ws.misc + 1));
+		if (e1) HIPCHK(hipEventRecord(e1, h->st));
+		else if (e0) ws.ev_used--;
+		if (ni > 1) hipLaunchKernelGGL(k_kount_keep, dim3(grid(nub + 1)), dim3(256), 0, h->st, (const int64_t*)P.ci, ni, pn, nub, min_occ, P.cnt);
+		size_t b = ws.tmp_bytes + 256;
+		const int r = rb3kount_scan(ws.tmp, &b, P.cnt, P.off, nub + 1, h->st);
+		return r < 0 ? (r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV) : 0;
+	};
+	struct Frame { const int64_t *pn; int64_t nub, n, total, i, base; int phase; }; // phase 0: to expand, 1: slices of its children, 2: done
+	std::vector<Frame> F((size_t)k);
+	int r;
+	if ((r = kount_level_ensure(h, ws.lv[0], 1, cap, W, ni)) < 0) return r;
+	hipLaunchKernelGGL(k_kount_root, dim3(1), dim3(64), 0, h->st, (const IdxView*)ws.tab, ni, W, ws.lv[0].code, ws.lv[0].iv, ws.misc);
+	F[0] = {ws.misc, 1, 0, 0, 0, 0, 0};
+	int64_t n_out = 0, n_split = 0;
+	int ret = 0;
+	for (int d = 0; d >= 0 && ret == 0;) {
+		Frame &f = F[d];
+		KountLevel &P = ws.lv[d];
+		const bool leaf = d == k - 1;
+		if (f.phase == 2) { --d; continue; }
+		if (f.phase == 0) {
+			if ((r = expand(d, f.pn, f.nub)) < 0) return r;
+			if (!leaf && 4 * f.nub <= sync_ub) { // every child fits: the next frontier without a word to the host
+				if ((r = kount_level_ensure(h, ws.lv[d + 1], 4 * f.nub, cap, W, ni)) < 0) return r;
+				KountLevel &C = ws.lv[d + 1];
+				hipLaunchKernelGGL(k_kount_emit, dim3(grid(f.nub)), dim3(256), 0, h->st, (const uint64_t*)P.code, (const int64_t*)P.ci, (const int64_t*)P.off, W, ni, d, k,
+						min_occ, (int64_t)0, (int64_t)0, f.pn, 0, C.code, C.iv, (uint8_t*)nullptr, (int64_t*)nullptr);
+				F[d + 1] = {P.off + f.nub, 4 * f.nub, 0, 0, 0, 0, 0};
+				f.phase = 2, ++d;
+				continue;
+			}
+			HIPCHK(hipMemcpyAsync(ws.h_small, f.pn, 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(ws.h_small + 1, P.off + f.nub, 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			harvest();
+			f.n = ws.h_small[0], f.total = ws.h_small[1], f.i = 0, f.base = 0, f.phase = 1;
+		}
+		// the children of the parents [f.i, f.n) in slices of at most lim nodes, each walked to the end before the next
+		if (f.i >= f.n || f.base >= f.total) { f.phase = 2, --d; continue; }
+		const int64_t lim = leaf ? lim_out : cap;
+		int64_t j = f.n, c = f.total - f.base;
+		const int64_t *pc = P.off + f.nub;
+		if (c > lim || f.i > 0) {
+			hipLaunchKernelGGL(k_kount_split, dim3(1), dim3(64), 0, h->st, (const int64_t*)P.off, f.i, f.n, lim, P.sc);
+			HIPCHK(hipMemcpyAsync(ws.h_small, P.sc, 16, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			harvest();
+			j = ws.h_small[0], c = ws.h_small[1], pc = P.sc + 1;
+			if (j <= f.i || j > f.n || c < 0 || c > lim) return RB3GPU_EINTERNAL;
+			if (j < f.n) ++n_split;
+		}
+		if (leaf) {
+			if (c > ws.out_cap) {
+				const int64_t oc = std::max(c, std::min(lim_out, 2 * ws.out_cap));
+				if (ws.d_out) { HIPCHK(hipFree(ws.d_out)); ws.d_out = nullptr; }
+				if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
+				ws.out_cap = 0;
+				const size_t ob = ((size_t)oc * k + 7) / 8 * 8 + (size_t)oc * ni * 8;
+				HIPCHK(hipMalloc(&ws.d_out, ob));
+				HIPCHK(hipHostMalloc((void**)&ws.h_out, ob, hipHostMallocDefault));
+				ws.out_cap = oc;
+			}
+			const size_t coff = ((size_t)ws.out_cap * k + 7) / 8 * 8;
+			hipLaunchKernelGGL(k_kount_emit, dim3(grid(j - f.i)), dim3(256), 0, h->st, (const uint64_t*)P.code, (const int64_t*)P.ci, (const int64_t*)P.off, W, ni, d, k,
+					min_occ, f.i, j, (const int64_t*)nullptr, 1, (uint64_t*)nullptr, (int64_t*)nullptr, ws.d_out, (int64_t*)(ws.d_out + coff));
+			HIPCHK(hipMemcpyAsync(ws.h_out, ws.d_out, (size_t)c * k, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(ws.h_out + coff, ws.d_out + coff, (size_t)c * ni * 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			harvest();
+			f.i = j, f.base += c, n_out += c;
+			if (c > 0) ret = cb(ud, c, ni, k, ws.h_out, (const int64_t*)(ws.h_out + coff));
+			continue;
+		}
+		if ((r = kount_level_ensure(h, ws.lv[d + 1], c, cap, W, ni)) < 0) return r;
+		KountLevel &C = ws.lv[d + 1];
+		hipLaunchKernelGGL(k_kount_emit, dim3(grid(j - f.i)), dim3(256), 0, h->st, (const uint64_t*)P.code, (const int64_t*)P.ci, (const int64_t*)P.off, W, ni, d, k,
+				min_occ, f.i, j, (const int64_t*)nullptr, 0, C.code, C.iv, (uint8_t*)nullptr, (int64_t*)nullptr);
+		F[d + 1] = {pc, c, 0, 0, 0, 0, 0};
+		f.i = j, f.base += c, ++d;
+	}
+	unsigned long long nodes = 0;
+	HIPCHK(hipMemcpyAsync(ws.h_small, ws.misc + 1, 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	harvest();
+	nodes = (unsigned long long)ws.h_small[0];
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_expand = ms_expand, st->n_nodes = (int64_t)nodes, st->n_out = n_out, st->n_slices = 1 + n_split;
+	return ret;
 }
 
 } // extern "C"

@@ -45,6 +45,14 @@ class Stats(ctypes.Structure):
 EMIT_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64)
 EMITW_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64)
 EMIT_WORDS_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64)
+KOUNT_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64))
+
+
+class KountStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_expand", ctypes.c_double), ("n_nodes", ctypes.c_int64), ("n_out", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
@@ -149,6 +157,7 @@ SYMBOLS = {
     "rb3gpu_shard_handle": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int]),
     "rb3gpu_shard_bounds": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_device_of": (ctypes.c_int, [ctypes.c_void_p]),
+    "rb3gpu_kount": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, KOUNT_F, ctypes.c_void_p, ctypes.POINTER(KountStats)]),
     "rb3gpu_stream_of": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
 
@@ -646,6 +655,26 @@ class Rb3Gpu:
         self._chk(self._lib.rb3gpu_balanced_bounds(self._h, int(n), b.ctypes.data), "rb3gpu_balanced_bounds")
         return b
 
+    def kount(self, k, min_occ, others=(), max_level_nodes=0, stats=None):
+        """rb3gpu_kount: the k-mers that occur at least min_occ times in this index or one of `others` (handles on the same device; all 4^k
+        for min_occ <= 0), in the reference's output order: (kmers, counts), uint8 (N, k) with symbols 1..4 = A C G T and int64 (N, 1 + len(others)).
+        max_level_nodes: the cap of one depth's frontier (0: by the free device memory); stats: a dict that receives rb3gpu_kount_stats_t"""
+        hs = [self] + list(others)
+        arr = (ctypes.c_void_p * len(hs))(*[x._h for x in hs])
+        kms, cts = [], []
+
+        def cb(_ud, n, n_idx, kk, kmers, counts):
+            kms.append(np.ctypeslib.as_array(kmers, shape=(n * kk,)).reshape(n, kk).copy())
+            cts.append(np.ctypeslib.as_array(counts, shape=(n * n_idx,)).reshape(n, n_idx).copy())
+            return 0
+        st = KountStats()
+        self._chk(self._lib.rb3gpu_kount(arr, len(hs), int(k), int(min_occ), int(max_level_nodes), KOUNT_F(cb), None, ctypes.byref(st)), "rb3gpu_kount")
+        if stats is not None:
+            stats.update(st.as_dict())
+        if not kms:
+            return np.zeros((0, int(k)), dtype=np.uint8), np.zeros((0, len(hs)), dtype=np.int64)
+        return np.concatenate(kms), np.concatenate(cts)
+
     def sync(self):
         self._chk(self._lib.rb3gpu_sync(self._h), "rb3gpu_sync")
 
@@ -878,3 +907,14 @@ class Shard:
         r = self._lib.rb3gpu_shard_gather(s)
         if r < 0:
             raise Rb3GpuError(int(r), "rb3gpu_shard_gather")
+
+
+def kount_lines(kmers, counts):
+    """the reference's `kount` output for (kmers, counts) of Rb3Gpu.kount: the k-mer, then a tab and the count per index, per line (bytes)"""
+    kmers = np.asarray(kmers, dtype=np.uint8)
+    counts = np.asarray(counts, dtype=np.int64)
+    lut = np.frombuffer(b"$ACGTN", dtype=np.uint8)
+    out = []
+    for s, c in zip(lut[kmers], counts):
+        out.append(s.tobytes() + b"".join(b"\t%d" % x for x in c) + b"\n")
+    return b"".join(out)
