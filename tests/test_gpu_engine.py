@@ -2170,6 +2170,80 @@ def test_slot_headers_relative_to_the_group(oracle, limit):
         h.close()
 
 
+def _rank_and_kount_beyond_2_32(h, sb=31):
+    """rank1a of an index past 2^32 symbols (slot headers = low halves of the LF bases + the table of bases every 2^31 symbols) against a
+    CPU table of counts every 2^16 symbols of its exported plain BWT: at random positions, around every multiple of 2^31, around every
+    C[a], around every position where an LF base C[a] + rank(a, k) crosses a multiple of 2^31 (where the low-half arithmetic wraps;
+    for T that is inside the index) and at the end; then kount(6, 1) against a backward search on the same table.  The positions are
+    checked around multiples of 2^sb (the table's spacing is 2^31); returns them."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from tests import kount_model as km
+    t0 = time.time()
+    plain = h.export_plain()
+    n = plain.size
+    S = 16
+    nb = (n >> S) + 1                                  # blocks of 2^16 symbols, the last one partial
+    cp = np.zeros((nb + 1, 6), dtype=np.int64)        # cp[j] = counts before position j << S (cp[nb] = the totals)
+
+    def fill(j0):
+        j1 = min(nb, j0 + 1024)
+        for j in range(j0, j1, 256):
+            je = min(j1, j + 256)
+            blk = plain[j << S: min(n, je << S)]
+            full = (je - j) if (je << S) <= n else (je - j - 1)
+            for c in range(6):
+                if full:
+                    cp[j + 1: j + 1 + full, c] = np.count_nonzero(blk[: full << S].reshape(full, 1 << S) == c, axis=1)
+                if full < je - j:
+                    cp[je, c] = np.count_nonzero(blk[full << S:] == c)
+    with ThreadPoolExecutor(8) as ex:
+        list(ex.map(fill, range(0, nb, 1024)))
+    np.cumsum(cp, axis=0, out=cp)
+    acc = h.get_acc()
+    assert np.array_equal(acc[1:], np.cumsum(cp[nb]))
+
+    def rank(ks):
+        out = cp[ks >> S].copy()
+        for i, k in enumerate(ks):
+            out[i] += np.bincount(plain[(k >> S) << S: k], minlength=6)
+        return out
+    rng = np.random.default_rng(232)
+    ks = [rng.integers(0, n + 1, size=4096), np.arange(n - 4095, n + 1)]
+    near = [m << sb for m in range(1, (n >> sb) + 1)] + [1 << 32] + [int(x) for x in acc]
+    for a in range(6):   # where C[a] + rank(a, k) reaches a multiple of 2^31: the k just past the occurrence of a that gets it there
+        for M in range(1, (n >> sb) + 2):
+            r = (M << sb) - int(acc[a])
+            if 0 < r <= int(acc[a + 1] - acc[a]):
+                j = int(np.searchsorted(cp[:, a], r)) - 1     # the last block start with fewer than r occurrences before it
+                occ = np.flatnonzero(plain[j << S: min(n, (j + 1) << S)] == a)
+                k = (j << S) + int(occ[r - int(cp[j, a]) - 1]) + 1
+                assert cp[j, a] < r and int(acc[a]) + int(rank(np.array([k]))[0, a]) == M << sb
+                near.append(k)
+    ks.append((np.array(near, dtype=np.int64)[:, None] + np.arange(-3, 4)[None, :]).ravel())
+    ks = np.unique(np.clip(np.concatenate(ks), 0, n)).astype(np.int64)
+    got, want = h.rank1a(ks), rank(ks)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, "rank1a differs at %d of %d positions beyond 2^32, first k = %d" % (bad.size, ks.size, ks[bad[0]] if bad.size else -1)
+    # kount(6, 1): the backward search of every 6-mer on the CPU table (a k-mer's occurrences = the size of its BWT interval)
+    lev = [(np.array([[c]], dtype=np.uint8), np.array([acc[c]]), np.array([acc[c + 1]])) for c in range(1, 5)]
+    km_, lo, hi = (np.concatenate([x[i] for x in lev]) for i in range(3))
+    for _ in range(5):
+        rl, rh = rank(lo), rank(hi)
+        nk, nl, nh = [], [], []
+        for c in range(1, 5):
+            l2, h2 = acc[c] + rl[:, c], acc[c] + rh[:, c]
+            keep = h2 > l2
+            nk.append(np.concatenate([np.full((int(keep.sum()), 1), c, dtype=np.uint8), km_[keep]], axis=1))
+            nl.append(l2[keep]), nh.append(h2[keep])
+        km_, lo, hi = np.concatenate(nk), np.concatenate(nl), np.concatenate(nh)
+    o = km.order(km_)
+    gk, gc = h.kount(6, 1)
+    assert np.array_equal(gk, km_[o]) and np.array_equal(gc[:, 0], (hi - lo)[o])
+    print("beyond 2^32: %d ranks and kount(6, 1) (%d 6-mers) checked against the CPU table in %.1f s" % (ks.size, gk.shape[0], time.time() - t0))
+    return near
+
+
 def test_index_beyond_2_32_symbols():
     """the regime BASELINE configs[3]/[4] live in.  12 haplotypes of a 180 Mbp genome (contigs of 20-100 Mbp, both
     strands: 360 M symbols per merge round) grow an index to 4.32 G symbols -- past 2^32, where the slot headers count from the
@@ -2189,6 +2263,7 @@ def test_index_beyond_2_32_symbols():
         assert man is not None, "no golden for this size: run tools/make_golden_big.py"
         assert rounds[-1]["index_symbols"] == man["symbols"]
         assert big_index.fmd_md5(h) == man["fmd_md5"]
+        _rank_and_kount_beyond_2_32(h)
         rd = big_index.reads_into(h, base, 200000, reps=1)
         assert rd["fallbacks"] == 0 and rd["lf_steps"] == rd["symbols"]
     finally:
