@@ -476,6 +476,22 @@ typedef int (*rb3gpu_kount_cb)(void *ud, int64_t n_out, int n_idx, int k, const 
 typedef struct { double ms_total, ms_expand; int64_t n_nodes, n_out, n_slices; } rb3gpu_kount_stats_t;
 int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t max_level_nodes, rb3gpu_kount_cb cb, void *ud, rb3gpu_kount_stats_t *st);
 
+/* super-maximal exact matches of queries against the index (`ropebwt3 mem`, search.c and rb3_fmd_smem_TG, fm-index.c:483-528 of the reference):
+ * the matches of query q = symbols[offsets[q], offsets[q + 1]) (nt6 codes 0..5, as rb3_char2nt6 makes them; n_query + 1 offsets, offsets[0] = 0) that are
+ * at least min_len long, occur at least min_occ times (both strands) and lie in no other such match, as the reference finds them.  Every query is cut
+ * into chunks of `chunk` symbols (<= 0: the default, 2048) that are searched independently, a walker of eight lanes each; the result does not depend on
+ * `chunk`.  Records reach cb in the reference's output order -- queries in input order, matches by start -- in one piece per output slice (host memory
+ * valid during the call only): st, en the match in the query, size its occurrences, x0 the first row of its interval.  A nonzero return from cb stops
+ * the call and is returned.  The call holds the symbols, 8 bytes per walker and 36 bytes per query symbol of a slice (rb3gpu_tune "mem_slice", default 8 M
+ * symbols) on the device; callers bound the symbols of a call (the CLI: -K).  RB3GPU_EINVAL for min_len < 1, min_occ < 1, a query longer than 2^31 - 1,
+ * 2^31 queries or more, or a NULL callback; RB3GPU_ESTATE for a handle without an index or with one that does not hold both strands.  st (may be NULL):
+ * ms_total wall time of the call, ms_walk the walkers' kernel alone (HIP events), n_steps extensions (a rank pair each), n_walkers, n_records, n_slices */
+typedef struct { int64_t query, x0, size; int32_t st, en; } rb3gpu_mem_rec_t;
+typedef int (*rb3gpu_mem_cb)(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs);
+typedef struct { double ms_total, ms_walk; int64_t n_steps, n_walkers, n_records, n_slices; } rb3gpu_mem_stats_t;
+int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk,
+		rb3gpu_mem_cb cb, void *ud, rb3gpu_mem_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -491,6 +507,7 @@ int rb3gpu_stream_sync(void *stream);
  *   text-order walk in text order: never / always / where the index does not fit the caches), "copy_walkers" 0/1, "b2_split" S (splitter
  *   spacing 2^S of the walker list the engine makes for the BWT-only entry points; -1 = by the size of the batch), "abs_limit" N (indexes
  *   of fewer than N symbols carry the LF base in their slot headers; at most 2^32, only before an index exists: RB3GPU_ESTATE after);
+ *   "mem_slice" N (query symbols per output slice of rb3gpu_mem; 0 = 8 M);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c
  * Test hooks "force_fallback", "tent_limit", "text_mode" exist only in the test build of the library (compiled with
  * -DRB3GPU_TEST_HOOKS, librb3gpu_hooks.so); the release library answers RB3GPU_EUNSUP.  Unknown key: RB3GPU_EINVAL. */

@@ -1369,6 +1369,196 @@ static int main_kount(int argc, char *argv[])
 	return ret;
 }
 
+/* mem: the super-maximal exact matches of every query in the index (the reference's main_search for `mem`, search.c:443-582, with its
+ * default algorithm), found on the GPU (rb3gpu_mem).  Queries are taken in batches of -K symbols; the lines of a batch are formatted
+ * into one buffer (rb3h_mem_format) that is written in large pieces.  Differences, each a refusal with exit status 1: -p (positions),
+ * --old-mem, -l or -c below 1, the options of `sw` and `hapdiv`; and every refusal exits 1 (the reference exits 0 on some). */
+typedef struct {
+	FILE *fp;
+	rb3h_buf_t out;
+	int mode, err;
+	int64_t min_gap, id0, n_query, next_q, pend_q, n_pend, m_pend;
+	rb3h_mem_rec_t *pend;       /* the matches of query pend_q so far (a query's matches may come in several pieces) */
+	const int64_t *off;         /* the batch: offsets of the queries' symbols, of their names in `names` (-1: none) */
+	const int64_t *name_off;
+	const char *names;
+} mem_out_t;
+
+static void mem_flush(mem_out_t *o)
+{
+	if (o->out.l > 0 && fwrite(o->out.s, 1, (size_t)o->out.l, o->fp) != (size_t)o->out.l) o->err = 1;
+	o->out.l = 0;
+}
+
+/* the lines of the queries [next_q, q) (the matches collected for pend_q among them) */
+static void mem_advance(mem_out_t *o, int64_t q)
+{
+	for (; o->next_q < q; ++o->next_q) {
+		const int64_t i = o->next_q, n = o->n_pend > 0 && o->pend_q == i ? o->n_pend : 0;
+		if (n == 0 && o->mode != RB3H_MEM_GAP) continue; /* (only --gap has something to say about a query without matches) */
+		if (rb3h_mem_format(&o->out, o->mode, o->min_gap, o->name_off[i] >= 0 ? o->names + o->name_off[i] : 0, o->id0 + i, o->off[i + 1] - o->off[i], n, o->pend) < 0) o->err = 1;
+		if (n > 0) o->n_pend = 0;
+		if (o->out.l > (1 << 20)) mem_flush(o);
+	}
+}
+
+static int mem_sink(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs)
+{
+	mem_out_t *o = (mem_out_t*)ud;
+	int64_t i = 0;
+	while (i < n && !o->err) {
+		const int64_t q = recs[i].query;
+		int64_t k = i + 1;
+		while (k < n && recs[k].query == q) ++k;
+		if (q < o->next_q || q >= o->n_query) { o->err = 2; break; }
+		if (o->n_pend == 0 || o->pend_q != q) mem_advance(o, q), o->pend_q = q, o->n_pend = 0;
+		if (o->n_pend + (k - i) > o->m_pend) {
+			const int64_t m = (o->n_pend + (k - i)) * 2 + 256;
+			rb3h_mem_rec_t *t = (rb3h_mem_rec_t*)realloc(o->pend, (size_t)m * sizeof(*t));
+			if (t == 0) { o->err = 1; break; }
+			o->pend = t, o->m_pend = m;
+		}
+		memcpy(o->pend + o->n_pend, recs + i, (size_t)(k - i) * sizeof(*recs));
+		o->n_pend += k - i, i = k;
+	}
+	return o->err ? -1 : 0;
+}
+
+static const struct option mem_long_opts[] = {
+	{ "gap", required_argument, 0, 403 },
+	{ "cov", no_argument, 0, 404 },
+	{ "old-mem", no_argument, 0, 405 },
+	{ "no-ssa", no_argument, 0, 406 },
+	{ "seq", no_argument, 0, 406 },
+	{ "all-e2e", no_argument, 0, 406 },
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ "chunk", required_argument, 0, 407 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_mem(int argc, char *argv[])
+{
+	int c, is_line = 0, device = 0, mode = RB3H_MEM_LINES, ret = 0, j;
+	int64_t min_len = 19, min_occ = 1, batch_size = 100000000, min_gap = 0, chunk = 0, id = 0;
+	int64_t n_steps = 0, n_walkers = 0, n_records = 0, n_slices = 0, n_batches = 0;
+	double ms_walk = 0, ms_engine = 0;
+	rb3gpu_t *h;
+	rb3gpu_opt_t gopt;
+	int64_t acc[7];
+	mem_out_t o;
+	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0};
+	int64_t *off = 0, *name_off = 0, m_q = 0;
+	_Static_assert(sizeof(rb3h_mem_rec_t) == sizeof(rb3gpu_mem_rec_t), "one record layout on both sides");
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", mem_long_opts, 0)) >= 0) {
+		if (c == 'L') is_line = 1;
+		else if (c == 'l') min_len = atol(optarg);
+		else if (c == 'c') min_occ = atol(optarg);
+		else if (c == 't' || c == 'M') {} /* threads of the reference's kt_for, its mmap loader: nothing to size here */
+		else if (c == 'K') batch_size = rb3h_parse_num(optarg);
+		else if (c == 403) min_gap = (int32_t)rb3h_parse_num(optarg);
+		else if (c == 404) mode = RB3H_MEM_COV;
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+		else if (c == 407) chunk = rb3h_parse_num(optarg);
+		else if (c == 'p') { fprintf(stderr, "ERROR: -p (positions of the matches) is not supported by this build of mem\n"); return 1; }
+		else if (c == 405) { fprintf(stderr, "ERROR: --old-mem is not supported: mem runs the default algorithm only\n"); return 1; }
+		else if (c == '?') return 1;
+		else { fprintf(stderr, "ERROR: option not supported by mem (it belongs to sw or hapdiv)\n"); return 1; }
+	}
+	if (argc - optind < 2) {
+		fprintf(stdout, "Usage: ropebwt3-amd mem [options] <idx.fmr> <seq.fa> [...]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -l INT      min MEM length [%ld]\n", (long)min_len);
+		fprintf(stderr, "  -c INT      min interval size [%ld]\n", (long)min_occ);
+		fprintf(stderr, "  --gap=NUM   output regions >=NUM that are not covered by MEMs [%d]\n", (int)min_gap);
+		fprintf(stderr, "  --cov       output breadth of coverage\n");
+		fprintf(stderr, "  -t INT      number of threads [4]\n");
+		fprintf(stderr, "  -L          one sequence per line in the input\n");
+		fprintf(stderr, "  -K NUM      query batch size [100m]\n");
+		fprintf(stderr, "  -M          use mmap to load FMD\n");
+		return 0;
+	}
+	if (min_len < 1) { fprintf(stderr, "ERROR: the min MEM length (-l) must be at least 1\n"); return 1; }
+	if (min_occ < 1) { fprintf(stderr, "ERROR: the min interval size (-c) must be at least 1\n"); return 1; }
+	if (min_gap > 0) mode = RB3H_MEM_GAP; /* (before --cov, search.c:271-279) */
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	h = rb3gpu_create(&gopt);
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
+	if (load_index(h, argv[optind]) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	rb3gpu_get_acc(h, acc);
+	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded the index\n", __func__, rb3h_realtime(), rb3h_percent_cpu());
+	memset(&o, 0, sizeof(o));
+	o.fp = stdout, o.mode = mode, o.min_gap = min_gap;
+	for (j = optind + 1; j < argc && ret == 0; ++j) {
+		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
+		int eof = 0;
+		if (fp == 0) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
+			ret = 1;
+			break;
+		}
+		while (!eof && ret == 0) { /* a batch: records until their symbols reach -K (search.c:366-378) */
+			int64_t n_q = 0, l;
+			const uint8_t *s;
+			const char *name;
+			sym.l = names.l = 0;
+			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
+				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
+				if (n_q + 2 > m_q) {
+					m_q = m_q ? m_q * 2 : 1024;
+					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
+				}
+				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
+				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
+				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+				if (l > 0x7fffffffLL) { fprintf(stderr, "ERROR: a query of more than 2^31 - 1 symbols\n"); ret = 1; break; }
+				if (n_q == 0) off[0] = 0;
+				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
+				rb3h_char2nt6(l, sym.s + sym.l); /* search.c:91 */
+				sym.l += l, off[++n_q] = sym.l;
+				name_off[n_q - 1] = name ? names.l : -1;
+				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
+				if (sym.l >= batch_size || n_q >= 0x7fffffffLL) break;
+			}
+			if (l < 0) eof = 1;
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q > 0 && ret == 0) {
+				rb3gpu_mem_stats_t st;
+				int r;
+				o.off = off, o.name_off = name_off, o.names = (const char*)names.s, o.id0 = id, o.n_query = n_q, o.next_q = 0, o.n_pend = 0;
+				r = rb3gpu_mem(h, n_q, off, sym.s, min_len, min_occ, chunk, mem_sink, &o, &st);
+				if (r == 0 && !o.err) mem_advance(&o, n_q);
+				mem_flush(&o);
+				if (r != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to find the matches: %s\n", rb3gpu_strerror(r)); ret = 1; }
+				else if (o.err) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+				id += n_q, ++n_batches;
+				n_steps += st.n_steps, n_walkers += st.n_walkers, n_records += st.n_records, n_slices += st.n_slices, ms_walk += st.ms_walk, ms_engine += st.ms_total;
+				if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] processed %lld sequences\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_q);
+			}
+		}
+		rb3h_seq_close(fp);
+	}
+	if (fflush(stdout) != 0 && ret == 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (rb3h_verbose >= 3 && ret == 0)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld matches from %lld walkers in %lld slice(s), %lld extensions; %.3f ms in the engine, walkers' kernel %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_records, (long long)n_walkers, (long long)n_slices, (long long)n_steps, ms_engine, ms_walk);
+	free(o.out.s); free(o.pend); free(sym.s); free(names.s); free(off); free(name_off);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* recode: decode an FMD/FMR file on the host and write it back as plain text (default), FMD (-d)
  * or FMR (-b).  Host-only utility; also the CPU-side test bench of the two codecs. */
 typedef struct { int64_t cnt[6]; runvec_t rv; } recode_t;
@@ -1468,6 +1658,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    merge      merge BWTs (on an MI355X)\n");
 	fprintf(fp, "    ssa        generate sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    kount      count k-mers in one or more FM-indexes (on an MI355X)\n");
+	fprintf(fp, "    mem        find super-maximal exact matches of queries (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
 	fprintf(fp, "    plain2fmd  convert BWT in plain text to FMD (host only)\n");
 	fprintf(fp, "    version    print the version number\n");
@@ -1484,6 +1675,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "merge") == 0) ret = main_merge(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "ssa") == 0) ret = main_ssa(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "kount") == 0) ret = main_kount(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "mem") == 0) ret = main_mem(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "plain2fmd") == 0) ret = main_plain2fmd(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "version") == 0) { printf("%s\n", RB3H_VERSION); return 0; }

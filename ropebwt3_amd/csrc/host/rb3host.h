@@ -58,9 +58,19 @@ typedef void (*rb3h_free_f)(void *p);
 void rb3h_seq_set_batch_allocator(rb3h_alloc_f alloc, rb3h_free_f release);
 void rb3h_batch_free(void *p);
 int rb3h_seq_error(const rb3h_seqio_t *fp); /* != 0: a FASTX parsing error ended the file early (code as in kseq: -2 truncated quality, ...) */
+/* one record with its name (io.c:127-144): the query commands' reader; see seqio.c */
+int64_t rb3h_seq_read1(rb3h_seqio_t *fp, const uint8_t **seq, const char **name);
 int64_t rb3h_strand_pairs(int64_t len, const uint8_t *text, int64_t n_seq, int64_t max_pairs, int64_t *pair_start); /* record offsets of a both-strand batch */
 void rb3h_char2nt6(int64_t l, uint8_t *s);                                 /* io.c:23-28 */
 void rb3h_revcomp6(int64_t l, uint8_t *s);                                 /* io.c:30-40 */
+
+/* ---- the output of `mem` (write_per_seq, search.c:240-325) ---- */
+typedef struct { int64_t query, x0, size; int32_t st, en; } rb3h_mem_rec_t; /* = rb3gpu_mem_rec_t */
+#define RB3H_MEM_LINES 0   /* name, start, end, occurrences per match */
+#define RB3H_MEM_GAP   1   /* --gap=NUM: the stretches of at least min_gap symbols that no match covers: name, start, end, query length */
+#define RB3H_MEM_COV   2   /* --cov: name, query length, symbols covered; nothing for a query without cover */
+/* the lines of ONE query appended to `out` (grown with realloc): its n matches r[0..n) by start, its name (NULL: seq<id + 1>) and length; 0 or -1 (no memory) */
+int rb3h_mem_format(rb3h_buf_t *out, int mode, int64_t min_gap, const char *name, int64_t id, int64_t len, int64_t n, const rb3h_mem_rec_t *r);
 
 /* ---- FMD (rld0) writer / reader ---- */
 struct rb3h_fmdw_s;

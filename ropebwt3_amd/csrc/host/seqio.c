@@ -27,6 +27,8 @@ struct rb3h_seqio_s {
 	int beg, end;
 	uint8_t *buf;
 	rb3h_buf_t rec, qual;
+	rb3h_buf_t name;  /* keep_name: the name of the last FASTX record (rb3h_seq_read1) */
+	int keep_name;
 	int64_t buf_off;   /* file offset of buf[0] (plain files only: a byte range of a file, rb3h_seq_open_range) */
 	int64_t next_off;  /* file offset of the next fill */
 	int64_t range_end; /* > 0: records that start at or behind this file offset belong to somebody else */
@@ -317,7 +319,7 @@ void rb3h_seq_close(rb3h_seqio_t *fp)
 	if (fp == 0) return;
 	if (fp->fp) gzclose(fp->fp); /* (closes the descriptor it was opened on) */
 	else if (fp->fd >= 0) close(fp->fd);
-	free(fp->buf); free(fp->rec.s); free(fp->qual.s); free(fp);
+	free(fp->buf); free(fp->rec.s); free(fp->qual.s); free(fp->name.s); free(fp);
 }
 
 static int sio_fill(rb3h_seqio_t *fp)
@@ -391,6 +393,13 @@ static int64_t sio_read_fastx(rb3h_seqio_t *fp)
 	{
 		rb3h_buf_t *h = &fp->qual; /* scratch */
 		if (sio_getline(fp, h, 0) < 0) return -1;
+		if (fp->keep_name) { /* the name: up to the first white space of the header line (kseq.h) */
+			int64_t k = 0;
+			while (k < h->l && !(h->s[k] == ' ' || (h->s[k] >= '\t' && h->s[k] <= '\r'))) ++k;
+			if (buf_grow(&fp->name, k + 1) < 0) return -2;
+			memcpy(fp->name.s, h->s, (size_t)k);
+			fp->name.s[k] = 0, fp->name.l = k;
+		}
 		h->l = 0;
 	}
 	if (buf_grow(&fp->rec, 256) < 0) return -2;
@@ -472,6 +481,30 @@ int64_t rb3h_seq_read(rb3h_seqio_t *fp, rb3h_buf_t *seq, int64_t max_len, int is
 }
 
 int rb3h_seq_error(const rb3h_seqio_t *fp) { return fp->err; }
+
+/* one record with its name, as the query commands read them (rb3_seq_read1, io.c:127-144): the record's characters as they stand in
+ * the file (*seq, not 0-terminated, valid until the next call), its length returned; *name the FASTX name up to the first white space, or NULL
+ * for a file of lines.  Records and lines of no characters are records too (they count in the numbering of nameless queries).  -1: the end
+ * of the file, or a FASTX parsing error (rb3h_seq_error) or read error behind the records already returned. */
+int64_t rb3h_seq_read1(rb3h_seqio_t *fp, const uint8_t **seq, const char **name)
+{
+	int64_t ret;
+	*seq = 0;
+	if (name) *name = 0;
+	if (fp->err || fp->io_err) return -1;
+	if (fp->is_line) {
+		if (fp->beg >= fp->end && !fp->is_eof) sio_fill(fp); /* (so that the end of the file is not taken for an empty line) */
+		ret = sio_getline(fp, &fp->rec, 0);
+	} else {
+		fp->keep_name = 1;
+		ret = sio_read_fastx(fp);
+		if (ret < -1) fp->err = (int)ret;
+	}
+	if (ret < 0 || fp->io_err) return -1;
+	*seq = fp->rec.s;
+	if (name && !fp->is_line) *name = fp->name.s ? (const char*)fp->name.s : "";
+	return ret;
+}
 
 /* the records of a batch that was read with BOTH strands (rb3h_seq_read with is_for and is_rev: per record l symbols, 0, the reverse
  * complement, 0): pair_start[i] = offset of record i, for rb3gpu_sorter_upload_fwd.  Returns the number of records, or 0 if the

@@ -25,6 +25,7 @@
 #include "rb3gpu_planes.h"
 #include "rb3gpu_part.h"
 #include "rb3gpu_kount.h"
+#include "rb3gpu_mem.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
 		if (h && h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); \
@@ -146,6 +147,7 @@ struct Tune {
 	int sh_host_rounds = 0;  // rb3gpu_sh_merge with ONE interval: the host reads the split sizes back after every round, as with several (0: the rounds run back to back on the device)
 	int sh_block = 0;        // threads per block of k_sh_round at eight states per octet: 256 or 1024; 0: 1024 below 3 M chains
 	int sh_states = 0;       // states per octet of k_sh_round (1, 2, 4, 8); 0: by the number of chains
+	int64_t mem_slice = 0;   // rb3gpu_mem: query symbols whose matches one output slice holds (0: 8 M; a slice always takes at least one walker)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
 	int junction_check = 1;  // (round 6, last session: 1 = the events of EVERY stretch -- 16 before: every 16th; beside the rebuild the full check costs the 152-genome build 2.3 of 167 ms, every 2nd 0.4, every 4th nothing) ... and the LF relation at the junctions of the speculative walk (k_junction_check): wherever a walker met somebody's record -- all
 	                         // of them, always -- and at the drop-out events of every n-th stretch id (1: every event, ~10 ms per 152-genome build; 0: off)
@@ -653,6 +655,7 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "load_chunk")) t.load_chunk = v < 1 ? 1 : v;
 	else if (!strcmp(key, "lf_check")) t.lf_check = v < 0 ? 0 : v > (1 << 30) ? (1 << 30) : (int)v;
 	else if (!strcmp(key, "fmd_piece")) t.fmd_piece = v < 0 ? 0 : v;
+	else if (!strcmp(key, "mem_slice")) t.mem_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sh_host_rounds")) t.sh_host_rounds = v < 0 ? -1 : v != 0; // (-1: rounds on the device whatever the number of chains)
 	else if (!strcmp(key, "ev_blocks")) t.ev_blocks = v < 1 ? 1 : v > 65536 ? 65536 : (int)v;
 	else if (!strcmp(key, "cum_blocks")) t.cum_blocks = v < 1 ? 1 : v > 65536 ? 65536 : (int)v;
@@ -690,7 +693,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -4413,6 +4416,147 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 	harvest();
 	nodes = (unsigned long long)ws.h_small[0];
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_expand = ms_expand, st->n_nodes = (int64_t)nodes, st->n_out = n_out, st->n_slices = 1 + n_split;
+	return ret;
+}
+
+/* ---- mem: super-maximal exact matches of queries (rb3gpu_mem.h) ------------------------------- */
+
+#define RB3_MEM_CHUNK 2048                    // query symbols per walker unless the caller says otherwise (README: the measured knee)
+#define RB3_MEM_SLICE ((int64_t)1 << 23)      // query symbols per output slice (36 bytes of device memory each, and 32 per match)
+
+struct MemWs {
+	uint8_t *sym = nullptr;
+	int64_t *qoff = nullptr, *off = nullptr, *h_small = nullptr;
+	int32_t *wq = nullptr, *wa = nullptr;
+	unsigned long long *ctr = nullptr;
+	MemRaw *raw = nullptr;
+	uint32_t *flag = nullptr;
+	void *tmp = nullptr;
+	size_t tmp_bytes = 0;
+	MemOut *d_out = nullptr, *h_out = nullptr;
+	int64_t out_cap = 0;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	~MemWs()
+	{
+		void *dv[] = { sym, qoff, off, wq, wa, ctr, raw, flag, tmp, d_out };
+		for (void *p : dv) if (p) (void)hipFree(p);
+		if (h_out) (void)hipHostFree(h_out);
+		if (h_small) (void)hipHostFree(h_small);
+		if (e0) (void)hipEventDestroy(e0);
+		if (e1) (void)hipEventDestroy(e1);
+	}
+};
+
+int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk,
+		rb3gpu_mem_cb cb, void *ud, rb3gpu_mem_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || n_query < 0 || n_query > 0x7fffffffLL || !cb || min_len < 1 || min_occ < 1 || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
+	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
+	int64_t max_len = 0;
+	for (int64_t q = 0; q < n_query; ++q) {
+		const int64_t l = offsets[q + 1] - offsets[q];
+		if (l < 0 || l > 0x7fffffffLL) return RB3GPU_EINVAL;
+		max_len = std::max(max_len, l);
+	}
+	const int64_t total = n_query > 0 ? offsets[n_query] : 0;
+	if (total > 0 && !symbols) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	// both strands (rb3_fmi_is_symmetric, fm-index.h:135): the forward extension is a backward extension of the reverse complement
+	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE;
+	if (chunk <= 0) chunk = RB3_MEM_CHUNK;
+	if (chunk > 0x7fffffffLL) chunk = 0x7fffffffLL;
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	if (total == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
+	// the walkers: chunk after chunk of query after query, so that their chunks tile [0, total) in order
+	std::vector<int32_t> wq, wa;
+	{
+		int64_t nw = 0;
+		for (int64_t q = 0; q < n_query; ++q) nw += (offsets[q + 1] - offsets[q] + chunk - 1) / chunk;
+		wq.reserve((size_t)nw), wa.reserve((size_t)nw);
+		for (int64_t q = 0; q < n_query; ++q)
+			for (int64_t a = 0, l = offsets[q + 1] - offsets[q]; a < l; a += chunk) wq.push_back((int32_t)q), wa.push_back((int32_t)a);
+	}
+	const int64_t nw = (int64_t)wq.size();
+	auto w_beg = [&](int64_t w) { return offsets[wq[w]] + wa[w]; };
+	auto w_end = [&](int64_t w) { return std::min(offsets[wq[w]] + wa[w] + chunk, offsets[wq[w] + 1]); };
+	int64_t cap = h->tn.mem_slice > 0 ? h->tn.mem_slice : RB3_MEM_SLICE;
+	cap = std::min(total, std::max(cap, std::min(chunk, max_len)));
+	MemWs ws;
+	HIPCHK(hipMalloc(&ws.sym, (size_t)total + 64));
+	HIPCHK(hipMalloc(&ws.qoff, (size_t)(n_query + 1) * 8));
+	HIPCHK(hipMalloc(&ws.wq, (size_t)nw * 4));
+	HIPCHK(hipMalloc(&ws.wa, (size_t)nw * 4));
+	HIPCHK(hipMalloc(&ws.ctr, 64));
+	HIPCHK(hipMalloc(&ws.raw, (size_t)cap * sizeof(MemRaw)));
+	HIPCHK(hipMalloc(&ws.flag, (size_t)(cap + 1) * 4));
+	HIPCHK(hipMalloc(&ws.off, (size_t)(cap + 1) * 8));
+	HIPCHK(hipHostMalloc((void**)&ws.h_small, 64, hipHostMallocDefault));
+	HIPCHK(hipEventCreate(&ws.e0));
+	HIPCHK(hipEventCreate(&ws.e1));
+	{
+		const int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, cap + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
+	}
+	HIPCHK(hipMemcpyAsync(ws.sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(ws.qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(ws.wq, wq.data(), (size_t)nw * 4, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(ws.wa, wa.data(), (size_t)nw * 4, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(ws.ctr, 0, 64, h->st));
+	const IdxView ix = view_of(h);
+	Acc7 acc;
+	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	double ms_walk = 0;
+	int64_t n_rec = 0, n_slices = 0;
+	int ret = 0;
+	for (int64_t w0 = 0; w0 < nw && ret == 0; ++n_slices) {
+		const int64_t s0 = w_beg(w0);
+		int64_t w1 = w0 + 1;
+		while (w1 < nw && w_end(w1) - s0 <= cap) ++w1;
+		const int64_t ns = w_end(w1 - 1) - s0; // (<= cap: one walker's chunk is at most min(chunk, max_len) symbols)
+		if (ns < 1 || ns > cap) return RB3GPU_EINTERNAL;
+		HIPCHK(hipMemsetAsync(ws.flag, 0, (size_t)(ns + 1) * 4, h->st));
+		HIPCHK(hipMemsetAsync(ws.ctr, 0, 8, h->st));
+		const int64_t nb = std::min<int64_t>(((w1 - w0) * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(ws.e0, h->st));
+		hipLaunchKernelGGL(k_mem_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, acc, (const uint8_t*)ws.sym, (const int64_t*)ws.qoff, (const int32_t*)ws.wq, (const int32_t*)ws.wa,
+				w0, w1, chunk, min_len, min_occ, s0, ns, ws.raw, ws.flag, ws.ctr);
+		HIPCHK(hipEventRecord(ws.e1, h->st));
+		size_t tb = ws.tmp_bytes + 256;
+		const int r = rb3kount_scan(ws.tmp, &tb, ws.flag, ws.off, ns + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(hipMemcpyAsync(ws.h_small, ws.off + ns, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_walk += ev_ms(ws.e0, ws.e1);
+		const int64_t c = ws.h_small[0];
+		if (c < 0 || c > ns) return RB3GPU_EINTERNAL;
+		if (c > 0) {
+			if (c > ws.out_cap) {
+				const int64_t oc = std::max(c, std::min(cap, 2 * ws.out_cap));
+				if (ws.d_out) { HIPCHK(hipFree(ws.d_out)); ws.d_out = nullptr; }
+				if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
+				ws.out_cap = 0;
+				HIPCHK(hipMalloc(&ws.d_out, (size_t)oc * sizeof(MemOut)));
+				HIPCHK(hipHostMalloc((void**)&ws.h_out, (size_t)oc * sizeof(MemOut), hipHostMallocDefault));
+				ws.out_cap = oc;
+			}
+			hipLaunchKernelGGL(k_mem_gather, dim3((unsigned)std::min<int64_t>((ns + 255) / 256, 16384)), dim3(256), 0, h->st, (const MemRaw*)ws.raw, (const uint32_t*)ws.flag,
+					(const int64_t*)ws.off, ns, s0, (const int64_t*)ws.qoff, n_query, ws.d_out);
+			HIPCHK(hipMemcpyAsync(ws.h_out, ws.d_out, (size_t)c * sizeof(MemOut), hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			n_rec += c;
+			ret = cb(ud, c, (const rb3gpu_mem_rec_t*)ws.h_out);
+		}
+		w0 = w1;
+	}
+	HIPCHK(hipMemcpyAsync(ws.h_small, ws.ctr + 1, 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_steps = ws.h_small[0], st->n_walkers = nw, st->n_records = n_rec, st->n_slices = n_slices;
 	return ret;
 }
 

@@ -54,6 +54,16 @@ class KountStats(ctypes.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+MEM_REC = np.dtype([("query", "<i8"), ("x0", "<i8"), ("size", "<i8"), ("st", "<i4"), ("en", "<i4")])  # rb3gpu_mem_rec_t
+MEM_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
+
+
+class MemStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_steps", ctypes.c_int64), ("n_walkers", ctypes.c_int64), ("n_records", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
     "rb3gpu_opt_init": (None, [ctypes.POINTER(Opt)]),
@@ -159,6 +169,7 @@ SYMBOLS = {
     "rb3gpu_device_of": (ctypes.c_int, [ctypes.c_void_p]),
     "rb3gpu_kount": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, KOUNT_F, ctypes.c_void_p, ctypes.POINTER(KountStats)]),
     "rb3gpu_stream_of": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
 }
 
 # rb3gpu_comm_t (include/rb3gpu.h): the two collectives of the interval-sharded merge
@@ -675,6 +686,29 @@ class Rb3Gpu:
             return np.zeros((0, int(k)), dtype=np.uint8), np.zeros((0, len(hs)), dtype=np.int64)
         return np.concatenate(kms), np.concatenate(cts)
 
+    def mem(self, queries, min_len=19, min_occ=1, chunk=None, stats=None):
+        """rb3gpu_mem: the super-maximal exact matches of the queries (each a uint8 array of nt6 codes 0..5, or bytes / str of characters) of at
+        least min_len symbols and min_occ occurrences, as the reference's `mem` finds them: a structured array (MEM_REC: query, x0, size, st, en)
+        in the reference's output order.  chunk: query symbols per walker (None: the engine's default; the result does not depend on it);
+        stats: a dict that receives rb3gpu_mem_stats_t"""
+        qs = [nt6_of(q) for q in queries]
+        off = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            off[1:] = np.cumsum([q.size for q in qs])
+        sym = np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8)
+        sym = np.ascontiguousarray(sym, dtype=np.uint8)
+        got = []
+
+        def cb(_ud, n, recs):
+            got.append(np.frombuffer(ctypes.string_at(recs, n * MEM_REC.itemsize), dtype=MEM_REC).copy())
+            return 0
+        st = MemStats()
+        self._chk(self._lib.rb3gpu_mem(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, int(min_len), int(min_occ), 0 if chunk is None else int(chunk),
+                                       MEM_F(cb), None, ctypes.byref(st)), "rb3gpu_mem")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return np.concatenate(got) if got else np.zeros(0, dtype=MEM_REC)
+
     def sync(self):
         self._chk(self._lib.rb3gpu_sync(self._h), "rb3gpu_sync")
 
@@ -917,4 +951,32 @@ def kount_lines(kmers, counts):
     out = []
     for s, c in zip(lut[kmers], counts):
         out.append(s.tobytes() + b"".join(b"\t%d" % x for x in c) + b"\n")
+    return b"".join(out)
+
+
+_NT6 = np.full(256, 5, dtype=np.uint8)
+_NT6[:5] = np.arange(5)
+for _i, _c in enumerate(b"ACGT"):
+    _NT6[_c] = _NT6[_c + 32] = _i + 1
+
+
+def nt6_of(q):
+    """a query as nt6 codes: characters (bytes / str) through the reference's table (A C G T in either case 1..4, anything else 5); arrays as they are"""
+    if isinstance(q, str):
+        q = q.encode()
+    if isinstance(q, (bytes, bytearray)):
+        return _NT6[np.frombuffer(bytes(q), dtype=np.uint8)]
+    return np.ascontiguousarray(q, dtype=np.uint8)
+
+
+def mem_lines(recs, names=None, first_id=0):
+    """the reference's `mem` output for the records of Rb3Gpu.mem: name, start, end, occurrences per match (bytes); names[q] is the name of
+    query q (None, or a None entry: seq<first_id + q + 1>, as for queries without a name)"""
+    out = []
+    for r in recs:
+        q = int(r["query"])
+        nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
+        if isinstance(nm, str):
+            nm = nm.encode()
+        out.append(b"%s\t%d\t%d\t%d\n" % (nm, r["st"], r["en"], r["size"]))
     return b"".join(out)
