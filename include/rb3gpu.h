@@ -492,6 +492,40 @@ typedef struct { double ms_total, ms_walk; int64_t n_steps, n_walkers, n_records
 int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk,
 		rb3gpu_mem_cb cb, void *ud, rb3gpu_mem_stats_t *st);
 
+/* The sampled suffix array of the index in place, kept on the device for rb3gpu_locate / rb3gpu_mem_pos (8 bytes per string and per sample).
+ *   rb3gpu_ssa_set   upload host arrays as rb3_ssa_restore reads them from a .ssa file (ssa.c:215-241): r2i[m], ssa[n_ssa]; RB3GPU_EINVAL unless m, n_ssa
+ *                    and ms are what rb3gpu_ssa_dims gives for ssa_shift (m = acc[1]: the file belongs to this index)
+ *   rb3gpu_ssa_keep  build it on the device (the kernels of rb3gpu_ssa_gen) and keep it there: nothing crosses to the host
+ *   rb3gpu_ssa_drop  give it up; whatever replaces the index -- a merge, a load, a build -- does the same
+ *   rb3gpu_ssa_info  its sample rate and number of samples; RB3GPU_ESTATE without one */
+int rb3gpu_ssa_set(rb3gpu_t *h, int ssa_shift, int ms, int64_t m, int64_t n_ssa, const uint64_t *r2i, const uint64_t *ssa);
+int rb3gpu_ssa_keep(rb3gpu_t *h, int ssa_shift);
+int rb3gpu_ssa_drop(rb3gpu_t *h);
+int rb3gpu_ssa_info(const rb3gpu_t *h, int *ssa_shift, int64_t *n_ssa);
+
+/* where the rows of intervals lie in the indexed sequences (rb3_ssa_multi, ssa.c:158-192 of the reference, for a batch): for interval i = [lo[i], hi[i])
+ * up to min(max_pos, hi[i] - lo[i]) pairs -- sid: string (sequence sid >> 1, reverse strand if sid & 1), pos: offset of the row's suffix in that string --,
+ * the same pairs in the same order as the reference, whose traversal (sampled rows first, then the largest piece of a heap) also decides WHICH rows are
+ * reported when max_pos is below the size.  lo[i] >= hi[i]: no pairs.  Pairs reach cb slice by slice (host memory valid during the call only): the n
+ * intervals from i0 on, pair k of interval i0 + i at pos[off[i] + k], off[n] pairs in all.  A nonzero return from cb stops the call and is returned.
+ * An octet of lanes per interval; its heap lies in LDS (rb3gpu_tune "locate_heap" entries, default 32, at most 80) and an interval that needs more is run
+ * again with a heap in global memory, as many such intervals at a time as "locate_slice" bytes admit (default 256 MB).  RB3GPU_EINVAL for a non-empty
+ * interval with lo < acc[1] or hi > acc[6] (rows of sentinels: the reference reads in front of its array there), max_pos < 0 or a NULL callback;
+ * RB3GPU_ESTATE without an index or without a sampled suffix array; RB3GPU_EINTERNAL if a traversal ended with another number of pairs than it must.
+ * st (may be NULL): ms_total wall time, ms_locate the locate kernels alone (HIP events), n_pops pieces taken off a heap (a rank pair each), n_intervals,
+ * n_tier2 intervals run with a heap in global memory, max_heap most entries a heap held, n_pairs, n_slices */
+typedef struct { int64_t sid, pos; } rb3gpu_pos_t;
+typedef int (*rb3gpu_locate_cb)(void *ud, int64_t i0, int64_t n, const int64_t *off, const rb3gpu_pos_t *pos);
+typedef struct { double ms_total, ms_locate; int64_t n_pops, n_intervals, n_tier2, max_heap, n_pairs, n_slices; } rb3gpu_locate_stats_t;
+int rb3gpu_locate(rb3gpu_t *h, int64_t n, const int64_t *lo, const int64_t *hi, int64_t max_pos, rb3gpu_locate_cb cb, void *ud, rb3gpu_locate_stats_t *st);
+
+/* rb3gpu_mem with the positions of every match (`mem -p`): up to max_pos >= 1 pairs per record, those of rb3gpu_locate on [x0, x0 + size).  The records of
+ * a slice stay on the device between the search and the locate step; cb gets n records at a time with their pairs, pair k of record i at pos[off[i] + k].
+ * RB3GPU_ESTATE without a sampled suffix array on the handle; everything else as rb3gpu_mem and rb3gpu_locate.  lst (may be NULL): the locate step */
+typedef int (*rb3gpu_mem_pos_cb)(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs, const int64_t *off, const rb3gpu_pos_t *pos);
+int rb3gpu_mem_pos(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk, int64_t max_pos,
+		rb3gpu_mem_pos_cb cb, void *ud, rb3gpu_mem_stats_t *st, rb3gpu_locate_stats_t *lst);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -508,6 +542,7 @@ int rb3gpu_stream_sync(void *stream);
  *   spacing 2^S of the walker list the engine makes for the BWT-only entry points; -1 = by the size of the batch), "abs_limit" N (indexes
  *   of fewer than N symbols carry the LF base in their slot headers; at most 2^32, only before an index exists: RB3GPU_ESTATE after);
  *   "mem_slice" N (query symbols per output slice of rb3gpu_mem; 0 = 8 M);
+ *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c
  * Test hooks "force_fallback", "tent_limit", "text_mode" exist only in the test build of the library (compiled with
  * -DRB3GPU_TEST_HOOKS, librb3gpu_hooks.so); the release library answers RB3GPU_EUNSUP.  Unknown key: RB3GPU_EINVAL. */

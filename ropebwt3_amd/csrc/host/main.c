@@ -283,23 +283,65 @@ static int index_order(const char *fn)
 
 /* an existing index into HBM (build.c:172-184, rb3_fmi_restore): an FMD file is decoded on the device
  * (rb3gpu_from_fmd_words); an FMR file, a stream, or an FMD the device declined goes through the host decoder */
-static int load_index(rb3gpu_t *h, const char *fn)
+/* an index file in host memory, before a device has seen it: the undecoded words of an FMD file (z != NULL) or the runs of any index file */
+typedef struct { uint64_t *z; int64_t nw, mc[6]; runvec_t rv; } index_host_t;
+
+static void index_host_free(index_host_t *x)
 {
-	runvec_t rv = {0, 0, 0};
-	uint64_t *z = 0;
-	int64_t nw = 0, mc[6];
-	int r = g_host_fmd ? 1 : rb3h_fmd_read_words(fn, &z, &nw, mc);
+	free(x->z); free(x->rv.a);
+	x->z = 0, x->rv.a = 0, x->rv.n = x->rv.m = 0;
+}
+
+static int index_host_runs(const char *fn, index_host_t *x)
+{
+	if (rb3h_index_read_runs(fn, sink_runvec, &x->rv) < 0 || x->rv.n == 0) { index_host_free(x); return -1; }
+	return 0;
+}
+
+static int index_host_read(const char *fn, index_host_t *x)
+{
+	const int r = g_host_fmd ? 1 : rb3h_fmd_read_words(fn, &x->z, &x->nw, x->mc);
 	if (r < 0) return -1;
-	if (r == 0) {
-		r = rb3gpu_from_fmd_words(h, nw, z, mc);
-		free(z);
+	if (r != 0) x->z = 0;
+	return r == 0 ? 0 : index_host_runs(fn, x);
+}
+
+/* the number of sentinels (acc[1]) and of symbols (acc[6]) of the index that was read */
+static int64_t index_host_sentinels(const index_host_t *x, int64_t *n_sym)
+{
+	int64_t i, m = 0, n = 0;
+	if (x->z) {
+		for (i = 0; i < 6; ++i) n += x->mc[i];
+		m = x->mc[0];
+	} else for (i = 0; i < x->rv.n; ++i) {
+		n += (int64_t)(x->rv.a[i] >> 3);
+		if ((x->rv.a[i] & 7) == 0) m += (int64_t)(x->rv.a[i] >> 3);
+	}
+	*n_sym = n;
+	return m;
+}
+
+static int index_upload(rb3gpu_t *h, const char *fn, index_host_t *x)
+{
+	int r;
+	if (x->z) {
+		r = rb3gpu_from_fmd_words(h, x->nw, x->z, x->mc);
+		free(x->z), x->z = 0;
 		if (r == 0) return 0;
 		if (rb3h_verbose >= 2) fprintf(stderr, "[W::%s] the GPU did not decode '%s' (%s); decoding it on the host\n", __func__, fn, rb3gpu_strerror(r));
+		if (index_host_runs(fn, x) < 0) return -1;
 	}
-	if (rb3h_index_read_runs(fn, sink_runvec, &rv) < 0 || rv.n == 0) { free(rv.a); return -1; }
-	r = rb3gpu_from_runs(h, rv.n, rv.a);
-	free(rv.a);
+	r = rb3gpu_from_runs(h, x->rv.n, x->rv.a);
+	index_host_free(x);
 	return r < 0 ? -2 : 0;
+}
+
+static int load_index(rb3gpu_t *h, const char *fn)
+{
+	index_host_t x;
+	memset(&x, 0, sizeof(x));
+	if (index_host_read(fn, &x) < 0) return -1;
+	return index_upload(h, fn, &x);
 }
 
 /* ---- batches ----------------------------------------------------------------------------- */
@@ -1371,7 +1413,8 @@ static int main_kount(int argc, char *argv[])
 
 /* mem: the super-maximal exact matches of every query in the index (the reference's main_search for `mem`, search.c:443-582, with its
  * default algorithm), found on the GPU (rb3gpu_mem).  Queries are taken in batches of -K symbols; the lines of a batch are formatted
- * into one buffer (rb3h_mem_format) that is written in large pieces.  Differences, each a refusal with exit status 1: -p (positions),
+ * into one buffer (rb3h_mem_format) that is written in large pieces.  -p INT adds up to INT positions per match, located on the GPU
+ * through <index>.ssa, named through <index>.len.gz (rb3gpu_mem_pos, rb3h_mem_format_pos).  Differences, each a refusal with exit status 1:
  * --old-mem, -l or -c below 1, the options of `sw` and `hapdiv`; and every refusal exits 1 (the reference exits 0 on some). */
 typedef struct {
 	FILE *fp;
@@ -1382,6 +1425,9 @@ typedef struct {
 	const int64_t *off;         /* the batch: offsets of the queries' symbols, of their names in `names` (-1: none) */
 	const int64_t *name_off;
 	const char *names;
+	const rb3h_sid_t *sid;      /* not NULL: lines with positions; the positions of pend[i] are pend_pos[pend_off[i], pend_off[i + 1]) */
+	int64_t *pend_off, m_pos;
+	rb3h_pos_t *pend_pos;
 } mem_out_t;
 
 static void mem_flush(mem_out_t *o)
@@ -1396,13 +1442,15 @@ static void mem_advance(mem_out_t *o, int64_t q)
 	for (; o->next_q < q; ++o->next_q) {
 		const int64_t i = o->next_q, n = o->n_pend > 0 && o->pend_q == i ? o->n_pend : 0;
 		if (n == 0 && o->mode != RB3H_MEM_GAP) continue; /* (only --gap has something to say about a query without matches) */
-		if (rb3h_mem_format(&o->out, o->mode, o->min_gap, o->name_off[i] >= 0 ? o->names + o->name_off[i] : 0, o->id0 + i, o->off[i + 1] - o->off[i], n, o->pend) < 0) o->err = 1;
+		if (o->sid) {
+			if (rb3h_mem_format_pos(&o->out, o->name_off[i] >= 0 ? o->names + o->name_off[i] : 0, o->id0 + i, n, o->pend, o->pend_off, o->pend_pos, o->sid) < 0) o->err = 1;
+		} else if (rb3h_mem_format(&o->out, o->mode, o->min_gap, o->name_off[i] >= 0 ? o->names + o->name_off[i] : 0, o->id0 + i, o->off[i + 1] - o->off[i], n, o->pend) < 0) o->err = 1;
 		if (n > 0) o->n_pend = 0;
 		if (o->out.l > (1 << 20)) mem_flush(o);
 	}
 }
 
-static int mem_sink(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs)
+static int mem_sink_pos(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs, const int64_t *off, const rb3gpu_pos_t *pos)
 {
 	mem_out_t *o = (mem_out_t*)ud;
 	int64_t i = 0;
@@ -1415,14 +1463,36 @@ static int mem_sink(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs)
 		if (o->n_pend + (k - i) > o->m_pend) {
 			const int64_t m = (o->n_pend + (k - i)) * 2 + 256;
 			rb3h_mem_rec_t *t = (rb3h_mem_rec_t*)realloc(o->pend, (size_t)m * sizeof(*t));
+			int64_t *u;
 			if (t == 0) { o->err = 1; break; }
-			o->pend = t, o->m_pend = m;
+			o->pend = t;
+			u = (int64_t*)realloc(o->pend_off, (size_t)(m + 1) * 8);
+			if (u == 0) { o->err = 1; break; }
+			o->pend_off = u, o->m_pend = m;
 		}
 		memcpy(o->pend + o->n_pend, recs + i, (size_t)(k - i) * sizeof(*recs));
+		if (o->n_pend == 0) o->pend_off[0] = 0;
+		if (off) { /* the positions of these records behind those the query has already */
+			const int64_t base = o->pend_off[o->n_pend], np = off[k] - off[i];
+			int64_t x;
+			if (base + np > o->m_pos) {
+				const int64_t m = (base + np) * 2 + 1024;
+				rb3h_pos_t *t = (rb3h_pos_t*)realloc(o->pend_pos, (size_t)m * sizeof(*t));
+				if (t == 0) { o->err = 1; break; }
+				o->pend_pos = t, o->m_pos = m;
+			}
+			if (np > 0) memcpy(o->pend_pos + base, pos + off[i], (size_t)np * sizeof(*pos));
+			for (x = i; x < k; ++x) o->pend_off[o->n_pend + (x - i) + 1] = base + (off[x + 1] - off[i]);
+		} else {
+			int64_t x;
+			for (x = 0; x < k - i; ++x) o->pend_off[o->n_pend + x + 1] = o->pend_off[o->n_pend];
+		}
 		o->n_pend += k - i, i = k;
 	}
 	return o->err ? -1 : 0;
 }
+
+static int mem_sink(void *ud, int64_t n, const rb3gpu_mem_rec_t *recs) { return mem_sink_pos(ud, n, recs, 0, 0); }
 
 static const struct option mem_long_opts[] = {
 	{ "gap", required_argument, 0, 403 },
@@ -1439,7 +1509,11 @@ static const struct option mem_long_opts[] = {
 
 static int main_mem(int argc, char *argv[])
 {
-	int c, is_line = 0, device = 0, mode = RB3H_MEM_LINES, ret = 0, j;
+	int c, is_line = 0, device = 0, mode = RB3H_MEM_LINES, ret = 0, j, max_pos = 0;
+	rb3h_ssa_t *sa = 0;
+	rb3h_sid_t *sid = 0;
+	index_host_t ih;
+	rb3gpu_locate_stats_t lsum;
 	int64_t min_len = 19, min_occ = 1, batch_size = 100000000, min_gap = 0, chunk = 0, id = 0;
 	int64_t n_steps = 0, n_walkers = 0, n_records = 0, n_slices = 0, n_batches = 0;
 	double ms_walk = 0, ms_engine = 0;
@@ -1450,6 +1524,7 @@ static int main_mem(int argc, char *argv[])
 	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0};
 	int64_t *off = 0, *name_off = 0, m_q = 0;
 	_Static_assert(sizeof(rb3h_mem_rec_t) == sizeof(rb3gpu_mem_rec_t), "one record layout on both sides");
+	_Static_assert(sizeof(rb3h_pos_t) == sizeof(rb3gpu_pos_t), "one position layout on both sides");
 	optind = 1;
 	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", mem_long_opts, 0)) >= 0) {
 		if (c == 'L') is_line = 1;
@@ -1462,7 +1537,7 @@ static int main_mem(int argc, char *argv[])
 		else if (c == 301) device = atoi(optarg);
 		else if (c == 308) g_host_fmd = 1;
 		else if (c == 407) chunk = rb3h_parse_num(optarg);
-		else if (c == 'p') { fprintf(stderr, "ERROR: -p (positions of the matches) is not supported by this build of mem\n"); return 1; }
+		else if (c == 'p') max_pos = atoi(optarg);
 		else if (c == 405) { fprintf(stderr, "ERROR: --old-mem is not supported: mem runs the default algorithm only\n"); return 1; }
 		else if (c == '?') return 1;
 		else { fprintf(stderr, "ERROR: option not supported by mem (it belongs to sw or hapdiv)\n"); return 1; }
@@ -1482,25 +1557,59 @@ static int main_mem(int argc, char *argv[])
 	}
 	if (min_len < 1) { fprintf(stderr, "ERROR: the min MEM length (-l) must be at least 1\n"); return 1; }
 	if (min_occ < 1) { fprintf(stderr, "ERROR: the min interval size (-c) must be at least 1\n"); return 1; }
-	if (min_gap > 0) mode = RB3H_MEM_GAP; /* (before --cov, search.c:271-279) */
+	if (min_gap > 0) mode = RB3H_MEM_GAP, max_pos = 0; /* (before --cov, search.c:271-279; no positions beside gaps, search.c:494) */
+	memset(&lsum, 0, sizeof(lsum));
+	memset(&ih, 0, sizeof(ih));
+	if (max_pos > 0) { /* the two files beside the index (rb3_fmi_load_all, fm-index.c:606-640), read and held against the index before anything is asked of a
+	                    * device: files of another index are no files (fm-index.c:615, 633), and the refusal is the only line (search.c:555-559: before the check for both strands) */
+		const size_t l = strlen(argv[optind]);
+		char *fn = (char*)malloc(l + 8);
+		int64_t m, n_sym;
+		int ms;
+		if (fn) {
+			memcpy(fn, argv[optind], l);
+			strcpy(fn + l, ".ssa"), sa = rb3h_ssa_read(fn);
+			strcpy(fn + l, ".len.gz"), sid = sa ? rb3h_sid_read(fn) : 0;
+			free(fn);
+		}
+		if (sa == 0 || sid == 0) goto no_side;
+		if (index_host_read(argv[optind], &ih) < 0) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+			rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid);
+			return 1;
+		}
+		m = index_host_sentinels(&ih, &n_sym);
+		for (ms = 1; (1LL << ms) < m; ++ms) {} /* ssa.c:63-64: what a sampled suffix array of THIS index looks like */
+		if (sa->m != m || sid->n_seq * 2 != m || sa->ms != ms || sa->ss > 40 || sa->n_ssa != (n_sym - m + (1LL << sa->ss) - 1) >> sa->ss) goto no_side;
+	}
 	rb3gpu_opt_init(&gopt);
 	gopt.device = device, gopt.verbose = rb3h_verbose;
 	h = rb3gpu_create(&gopt);
-	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
-	if (load_index(h, argv[optind]) < 0) {
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid); index_host_free(&ih); return 1; }
+	if ((max_pos > 0 ? index_upload(h, argv[optind], &ih) : load_index(h, argv[optind])) < 0) {
 		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
 		rb3gpu_destroy(h);
+		rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid);
 		return 1;
 	}
 	rb3gpu_get_acc(h, acc);
+	if (max_pos > 0) { /* (the sample rate and the width of the string field must be those of this index as well) */
+		if (sa->m != acc[1] || sid->n_seq * 2 != acc[1] || rb3gpu_ssa_set(h, sa->ss, sa->ms, sa->m, sa->n_ssa, sa->r2i, sa->ssa) != 0) {
+			rb3gpu_destroy(h);
+			goto no_side;
+		}
+		rb3h_ssa_destroy(sa), sa = 0; /* (it lives on the device from here on) */
+	}
 	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
 		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
 		rb3gpu_destroy(h);
+		rb3h_sid_destroy(sid);
 		return 1;
 	}
 	if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded the index\n", __func__, rb3h_realtime(), rb3h_percent_cpu());
 	memset(&o, 0, sizeof(o));
 	o.fp = stdout, o.mode = mode, o.min_gap = min_gap;
+	if (max_pos > 0 && mode == RB3H_MEM_LINES) o.sid = sid; /* (--cov -p needs the files and prints no positions, search.c:279) */
 	for (j = optind + 1; j < argc && ret == 0; ++j) {
 		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
 		int eof = 0;
@@ -1538,7 +1647,12 @@ static int main_mem(int argc, char *argv[])
 				rb3gpu_mem_stats_t st;
 				int r;
 				o.off = off, o.name_off = name_off, o.names = (const char*)names.s, o.id0 = id, o.n_query = n_q, o.next_q = 0, o.n_pend = 0;
-				r = rb3gpu_mem(h, n_q, off, sym.s, min_len, min_occ, chunk, mem_sink, &o, &st);
+				if (o.sid) {
+					rb3gpu_locate_stats_t ls;
+					r = rb3gpu_mem_pos(h, n_q, off, sym.s, min_len, min_occ, chunk, max_pos, mem_sink_pos, &o, &st, &ls);
+					lsum.ms_locate += ls.ms_locate, lsum.n_pops += ls.n_pops, lsum.n_intervals += ls.n_intervals, lsum.n_tier2 += ls.n_tier2, lsum.n_pairs += ls.n_pairs;
+					lsum.max_heap = lsum.max_heap > ls.max_heap ? lsum.max_heap : ls.max_heap;
+				} else r = rb3gpu_mem(h, n_q, off, sym.s, min_len, min_occ, chunk, mem_sink, &o, &st);
 				if (r == 0 && !o.err) mem_advance(&o, n_q);
 				mem_flush(&o);
 				if (r != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to find the matches: %s\n", rb3gpu_strerror(r)); ret = 1; }
@@ -1554,9 +1668,18 @@ static int main_mem(int argc, char *argv[])
 	if (rb3h_verbose >= 3 && ret == 0)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld matches from %lld walkers in %lld slice(s), %lld extensions; %.3f ms in the engine, walkers' kernel %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_records, (long long)n_walkers, (long long)n_slices, (long long)n_steps, ms_engine, ms_walk);
-	free(o.out.s); free(o.pend); free(sym.s); free(names.s); free(off); free(name_off);
+	if (rb3h_verbose >= 3 && ret == 0 && o.sid)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld positions of %lld matches: %lld heap pops, %lld matches with a heap in global memory, largest heap %lld; locate kernels %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)lsum.n_pairs, (long long)lsum.n_intervals, (long long)lsum.n_pops, (long long)lsum.n_tier2, (long long)lsum.max_heap, lsum.ms_locate);
+	free(o.out.s); free(o.pend); free(o.pend_off); free(o.pend_pos); free(sym.s); free(names.s); free(off); free(name_off);
 	rb3gpu_destroy(h);
+	rb3h_sid_destroy(sid);
 	return ret;
+no_side:
+	index_host_free(&ih);
+	if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load suffix array samples or sequence names/lengths\n");
+	rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid);
+	return 1;
 }
 
 /* recode: decode an FMD/FMR file on the host and write it back as plain text (default), FMD (-d)

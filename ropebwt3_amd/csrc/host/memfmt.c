@@ -93,3 +93,39 @@ int rb3h_mem_format(rb3h_buf_t *out, int mode, int64_t min_gap, const char *name
 	}
 	return 0;
 }
+
+int rb3h_mem_format_pos(rb3h_buf_t *out, const char *name, int64_t id, int64_t n, const rb3h_mem_rec_t *r, const int64_t *off, const rb3h_pos_t *pos, const rb3h_sid_t *sid)
+{
+	const size_t l_name = name ? strlen(name) : 0;
+	int64_t i, k;
+	for (i = 0; i < n; ++i) { /* search.c:298-317 */
+		const int64_t np = off[i + 1] - off[i];
+		uint8_t *p;
+		if (fmt_reserve(out, (int64_t)l_name + 24 + 4 * 22 + 2) < 0) return -1;
+		p = fmt_name(out->s + out->l, name, l_name, id);
+		*p++ = '\t', p = fmt_num(p, r[i].st);
+		*p++ = '\t', p = fmt_num(p, r[i].en);
+		*p++ = '\t', p = fmt_num(p, r[i].size);
+		if (np > 0) *p++ = '\t', p = fmt_num(p, np);
+		out->l = p - out->s;
+		for (k = off[i]; k < off[i + 1]; ++k) {
+			const int64_t s = pos[k].sid >> 1;
+			const char *sn;
+			size_t l_sn;
+			int64_t x;
+			if (s < 0 || s >= sid->n_seq) return -2; /* (a string the name list does not know: the files do not belong together) */
+			sn = sid->name[s], l_sn = strlen(sn);
+			x = pos[k].sid & 1 ? sid->len[s] - (pos[k].pos + (r[i].en - r[i].st)) : pos[k].pos;
+			if (fmt_reserve(out, (int64_t)l_sn + 32) < 0) return -1;
+			p = out->s + out->l;
+			*p++ = '\t';
+			memcpy(p, sn, l_sn), p += l_sn;
+			*p++ = ':', *p++ = (uint8_t)"+-"[pos[k].sid & 1], *p++ = ':';
+			p = fmt_num(p, x);
+			out->l = p - out->s;
+		}
+		if (fmt_reserve(out, 1) < 0) return -1;
+		out->s[out->l++] = '\n';
+	}
+	return 0;
+}

@@ -72,6 +72,19 @@ typedef struct { int64_t query, x0, size; int32_t st, en; } rb3h_mem_rec_t; /* =
 /* the lines of ONE query appended to `out` (grown with realloc): its n matches r[0..n) by start, its name (NULL: seq<id + 1>) and length; 0 or -1 (no memory) */
 int rb3h_mem_format(rb3h_buf_t *out, int mode, int64_t min_gap, const char *name, int64_t id, int64_t len, int64_t n, const rb3h_mem_rec_t *r);
 
+/* the same lines with the positions of every match (`mem -p`, search.c:305-314): after the occurrences the number of positions and name:strand:position of each.
+ * The positions of r[i] are pos[off[i], off[i + 1]); a match without positions gets no extra column.  sid: the indexed sequences (rb3h_sid_read) */
+typedef struct { int64_t sid, pos; } rb3h_pos_t;                           /* = rb3gpu_pos_t */
+typedef struct { int64_t n_seq; char **name; int64_t *len; } rb3h_sid_t;
+int rb3h_mem_format_pos(rb3h_buf_t *out, const char *name, int64_t id, int64_t n, const rb3h_mem_rec_t *r, const int64_t *off, const rb3h_pos_t *pos, const rb3h_sid_t *sid);
+
+/* ---- the files beside an index that `mem -p` reads (sidefile.c) ---- */
+typedef struct { int32_t ss, ms; int64_t m, n_ssa; uint64_t *r2i, *ssa; } rb3h_ssa_t;
+rb3h_ssa_t *rb3h_ssa_read(const char *fn);                                 /* rb3_ssa_restore, ssa.c:215-241; NULL: no file, wrong magic, or it ends early */
+void rb3h_ssa_destroy(rb3h_ssa_t *sa);
+rb3h_sid_t *rb3h_sid_read(const char *fn);                                 /* rb3_sid_read, io.c:161-204 (gzip or plain) */
+void rb3h_sid_destroy(rb3h_sid_t *sl);
+
 /* ---- FMD (rld0) writer / reader ---- */
 struct rb3h_fmdw_s;
 typedef struct rb3h_fmdw_s rb3h_fmdw_t;

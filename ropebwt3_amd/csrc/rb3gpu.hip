@@ -26,6 +26,7 @@
 #include "rb3gpu_part.h"
 #include "rb3gpu_kount.h"
 #include "rb3gpu_mem.h"
+#include "rb3gpu_locate.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
 		if (h && h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); \
@@ -148,6 +149,8 @@ struct Tune {
 	int sh_block = 0;        // threads per block of k_sh_round at eight states per octet: 256 or 1024; 0: 1024 below 3 M chains
 	int sh_states = 0;       // states per octet of k_sh_round (1, 2, 4, 8); 0: by the number of chains
 	int64_t mem_slice = 0;   // rb3gpu_mem: query symbols whose matches one output slice holds (0: 8 M; a slice always takes at least one walker)
+	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
+	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
 	int junction_check = 1;  // (round 6, last session: 1 = the events of EVERY stretch -- 16 before: every 16th; beside the rebuild the full check costs the 152-genome build 2.3 of 167 ms, every 2nd 0.4, every 4th nothing) ... and the LF relation at the junctions of the speculative walk (k_junction_check): wherever a walker met somebody's record -- all
 	                         // of them, always -- and at the drop-out events of every n-th stretch id (1: every event, ~10 ms per 152-genome build; 0: off)
@@ -234,6 +237,9 @@ struct rb3gpu_s {
 	bool p0_live = false;            // p0b holds the sentinels' insertion points of the merge in progress (order_prepare): view_of hands them to the walkers
 	Buf p0b;                         // p0 of the batch being merged, the sentinels' text positions and a counter behind it
 	int64_t p0_n = 0;                // entries of p0
+	uint64_t *ssa_dev = nullptr;     // the sampled suffix array of the index in place (rb3gpu_ssa_set / _keep): r2i[ssa_m], then ssa[ssa_n]
+	int ssa_ss = 0, ssa_ms = 0;
+	int64_t ssa_m = 0, ssa_n = 0;
 	rb3order_ws *ows = nullptr;      // scratch of the string order (rb3gpu_order.hip), created on first use
 };
 
@@ -656,6 +662,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "lf_check")) t.lf_check = v < 0 ? 0 : v > (1 << 30) ? (1 << 30) : (int)v;
 	else if (!strcmp(key, "fmd_piece")) t.fmd_piece = v < 0 ? 0 : v;
 	else if (!strcmp(key, "mem_slice")) t.mem_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
+	else if (!strcmp(key, "locate_slice")) t.locate_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sh_host_rounds")) t.sh_host_rounds = v < 0 ? -1 : v != 0; // (-1: rounds on the device whatever the number of chains)
 	else if (!strcmp(key, "ev_blocks")) t.ev_blocks = v < 1 ? 1 : v > 65536 ? 65536 : (int)v;
 	else if (!strcmp(key, "cum_blocks")) t.cum_blocks = v < 1 ? 1 : v > 65536 ? 65536 : (int)v;
@@ -693,7 +701,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -732,8 +740,16 @@ rb3gpu_t *rb3gpu_create(const rb3gpu_opt_t *opt)
 	return h;
 }
 
+/* the sampled suffix array belongs to ONE index: whatever replaces the index gives it up */
+static void ssa_drop(rb3gpu_t *h)
+{
+	if (h->ssa_dev) dev_free(h, h->ssa_dev, (size_t)(h->ssa_m + h->ssa_n) * 8);
+	h->ssa_dev = nullptr, h->ssa_m = h->ssa_n = 0, h->ssa_ss = h->ssa_ms = 0;
+}
+
 static void index_drop(rb3gpu_t *h)
 {
+	ssa_drop(h);
 	h->grp = nullptr, h->slots = nullptr, h->n = h->ngrp = h->nslots = 0;
 	memset(h->acc, 0, sizeof(h->acc));
 	h->stt.bytes_index = 0;
@@ -1180,6 +1196,7 @@ static int build_index(rb3gpu_t *h, int64_t n2, const uint8_t *d_b2, const int64
 static void index_install(rb3gpu_t *h, int64_t ngrp, int64_t nslots, int64_t ntot, const int64_t acc[7])
 {
 	h->cur = 1 - h->cur;
+	ssa_drop(h);
 	if (RB3_ABS_HEADERS(ntot, h->tn.abs_limit) && (ntot >= RB3_ABS_LIMIT || h->tn.abs_table)) { // the LF bases every 2^31 symbols, from the directory the rebuild has just written (IdxView.sb)
 		auto &b = h->ib[h->cur]; // (ib_ensure made room for the table)
 		if (b.sbt && b.sbt_cap >= (size_t)(ntot >> RB3_SB_BITS) + 1) hipLaunchKernelGGL(k_sb_table, dim3((unsigned)((((ntot >> RB3_SB_BITS) + 1) * 8 + 63) / 64)), dim3(64), 0, h->st, (const uint64_t*)b.grp, (ntot >> RB3_SB_BITS) + 1, b.sbt);
@@ -3113,12 +3130,13 @@ int rb3gpu_ssa_dims(const rb3gpu_t *h, int ssa_shift, int64_t *m, int64_t *n_ssa
 	return 0;
 }
 
-int rb3gpu_ssa_gen(rb3gpu_t *h, int ssa_shift, uint64_t *r2i, uint64_t *ssa)
+/* the sampled suffix array of the index in place, to the host arrays (keep == false) or to a buffer that stays with the handle */
+static int ssa_build(rb3gpu_t *h, int ssa_shift, uint64_t *r2i, uint64_t *ssa, bool keep)
 {
 	int64_t m, n_ssa;
 	int ms, r;
-	if (!h || !r2i || (r = rb3gpu_ssa_dims(h, ssa_shift, &m, &n_ssa, &ms)) < 0) return h && r2i ? r : RB3GPU_EINVAL;
-	if (n_ssa > 0 && !ssa) return RB3GPU_EINVAL;
+	if (!h || (!keep && !r2i) || (r = rb3gpu_ssa_dims(h, ssa_shift, &m, &n_ssa, &ms)) < 0) return h && (keep || r2i) ? r : RB3GPU_EINVAL;
+	if (!keep && n_ssa > 0 && !ssa) return RB3GPU_EINVAL;
 	HIPCHK(hipSetDevice(h->dev));
 	// splitter spacing: the walk's longest sublist is about 2^S ln(number of splitters) steps, and every splitter
 	// costs a queue pull; the linking is pointer jumping, whose cost hardly depends on S
@@ -3154,9 +3172,19 @@ int rb3gpu_ssa_gen(rb3gpu_t *h, int ssa_shift, uint64_t *r2i, uint64_t *ssa)
 	HIPCHK(hipEventRecord(h->ev[2], h->st));
 	unsigned long long hm[4];
 	HIPCHK(hipMemcpyAsync(hm, misc, sizeof(hm), hipMemcpyDeviceToHost, h->st));
-	HIPCHK(hipMemcpyAsync(r2i, d_r2i, (size_t)m * 8, hipMemcpyDeviceToHost, h->st));
-	if (n_ssa > 0) HIPCHK(hipMemcpyAsync(ssa, d_ssa, (size_t)n_ssa * 8, hipMemcpyDeviceToHost, h->st));
+	uint64_t *kept = nullptr;
+	if (keep) { // (r2i and ssa lie side by side in the scratch: one copy, device to device)
+		if ((r = dev_malloc(h, (void**)&kept, (size_t)(m + n_ssa) * 8)) < 0) return r;
+		HIPCHK(hipMemcpyAsync(kept, d_r2i, (size_t)(m + n_ssa) * 8, hipMemcpyDeviceToDevice, h->st));
+	} else {
+		HIPCHK(hipMemcpyAsync(r2i, d_r2i, (size_t)m * 8, hipMemcpyDeviceToHost, h->st));
+		if (n_ssa > 0) HIPCHK(hipMemcpyAsync(ssa, d_ssa, (size_t)n_ssa * 8, hipMemcpyDeviceToHost, h->st));
+	}
 	HIPCHK(hipStreamSynchronize(h->st));
+	if (keep) {
+		if (hm[2] != 0 || hm[3] != 0) dev_free(h, kept, (size_t)(m + n_ssa) * 8);
+		else ssa_drop(h), h->ssa_dev = kept, h->ssa_m = m, h->ssa_n = n_ssa, h->ssa_ss = ssa_shift, h->ssa_ms = ms;
+	}
 	h->stt.ms_ssa += (now_s() - t0) * 1e3;
 	h->stt.ms_ssa_walk += ev_ms(h->ev[0], h->ev[1]);
 	if (hm[2] != 0 || hm[3] != 0) {
@@ -3166,6 +3194,46 @@ int rb3gpu_ssa_gen(rb3gpu_t *h, int ssa_shift, uint64_t *r2i, uint64_t *ssa)
 	if (h->opt.verbose >= 3)
 		fprintf(stderr, "[M::%s::%.3f] sampled suffix array: %lld strings, %lld samples, walk %.3f ms, link+final %.3f ms\n", __func__, now_s() - h->t0,
 				(long long)m, (long long)n_ssa, ev_ms(h->ev[0], h->ev[1]), ev_ms(h->ev[1], h->ev[2]));
+	return 0;
+}
+
+int rb3gpu_ssa_gen(rb3gpu_t *h, int ssa_shift, uint64_t *r2i, uint64_t *ssa) { return ssa_build(h, ssa_shift, r2i, ssa, false); }
+
+int rb3gpu_ssa_keep(rb3gpu_t *h, int ssa_shift) { return ssa_build(h, ssa_shift, nullptr, nullptr, true); }
+
+int rb3gpu_ssa_set(rb3gpu_t *h, int ssa_shift, int ms, int64_t m, int64_t n_ssa, const uint64_t *r2i, const uint64_t *ssa)
+{
+	int64_t m0, n0;
+	int ms0, r;
+	if (!h) return RB3GPU_EINVAL;
+	if ((r = rb3gpu_ssa_dims(h, ssa_shift, &m0, &n0, &ms0)) < 0) return r;
+	if (m != m0 || n_ssa != n0 || ms != ms0 || (m > 0 && !r2i) || (n_ssa > 0 && !ssa)) return RB3GPU_EINVAL;
+	HIPCHK(hipSetDevice(h->dev));
+	uint64_t *d = nullptr;
+	if ((r = dev_malloc(h, (void**)&d, (size_t)(m + n_ssa) * 8)) < 0) return r;
+	if (m > 0) HIPCHK(hipMemcpyAsync(d, r2i, (size_t)m * 8, hipMemcpyHostToDevice, h->st));
+	if (n_ssa > 0) HIPCHK(hipMemcpyAsync(d + m, ssa, (size_t)n_ssa * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	ssa_drop(h);
+	h->ssa_dev = d, h->ssa_m = m, h->ssa_n = n_ssa, h->ssa_ss = ssa_shift, h->ssa_ms = ms;
+	return 0;
+}
+
+int rb3gpu_ssa_drop(rb3gpu_t *h)
+{
+	if (!h) return RB3GPU_EINVAL;
+	HIPCHK(hipSetDevice(h->dev));
+	HIPCHK(hipStreamSynchronize(h->st));
+	ssa_drop(h);
+	return 0;
+}
+
+int rb3gpu_ssa_info(const rb3gpu_t *h, int *ssa_shift, int64_t *n_ssa)
+{
+	if (!h) return RB3GPU_EINVAL;
+	if (!h->ssa_dev) return RB3GPU_ESTATE;
+	if (ssa_shift) *ssa_shift = h->ssa_ss;
+	if (n_ssa) *n_ssa = h->ssa_n;
 	return 0;
 }
 
@@ -4419,6 +4487,219 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 	return ret;
 }
 
+/* ---- locate: the positions of the rows of intervals (rb3gpu_locate.h) --------------------------- */
+
+#define RB3_LOC_HEAP 32                            // entries of an octet's heap in LDS (24 bytes each, 32 octets per block: 24 KB)
+#define RB3_LOC_SLICE_IV ((int64_t)1 << 20)        // intervals per slice
+#define RB3_LOC_SLICE_PAIRS ((int64_t)1 << 21)     // pairs per slice (16 bytes each, on the device and page-locked on the host); one interval may exceed it
+#define RB3_LOC_T2_BYTES ((int64_t)256 << 20)      // bytes of global-memory heaps held at once
+
+struct LocWs {
+	int64_t n_cap = 0;
+	int64_t *src = nullptr, *iv = nullptr, *off = nullptr, *idx = nullptr, *hoff = nullptr;
+	uint32_t *cnt = nullptr, *flag = nullptr;
+	void *tmp = nullptr;
+	size_t tmp_bytes = 0;
+	unsigned long long *ctr = nullptr, *h_small = nullptr;
+	LocEnt *heap = nullptr;
+	int64_t heap_cap = 0, t2_cap = 0;
+	LocPair *d_pairs = nullptr, *h_pairs = nullptr;
+	int64_t pair_cap = 0;
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+	std::vector<uint32_t> h_flag;
+	std::vector<int64_t> h_size, h_off, h_idx, h_hoff; // of the slice: sizes (filled by the caller), places of the pairs; of a tier-2 slice: intervals, places of the heaps
+	double ms = 0;
+	int64_t pops = 0, n_iv = 0, n_t2 = 0, max_heap = 0, n_pairs = 0, n_slices = 0;
+	~LocWs()
+	{
+		void *dv[] = { src, iv, off, idx, hoff, cnt, flag, tmp, ctr, heap, d_pairs };
+		for (void *p : dv) if (p) (void)hipFree(p);
+		if (h_pairs) (void)hipHostFree(h_pairs);
+		if (h_small) (void)hipHostFree(h_small);
+		for (auto e : ev) if (e) (void)hipEventDestroy(e);
+	}
+};
+
+static int loc_init(rb3gpu_t *h, LocWs &ws, int64_t n_cap, bool own_src)
+{
+	if (n_cap < 1) n_cap = 1;
+	ws.n_cap = n_cap;
+	if (own_src) HIPCHK(hipMalloc(&ws.src, (size_t)n_cap * 16));
+	HIPCHK(hipMalloc(&ws.iv, (size_t)n_cap * 16));
+	HIPCHK(hipMalloc(&ws.off, (size_t)(n_cap + 1) * 8));
+	HIPCHK(hipMalloc(&ws.cnt, (size_t)(n_cap + 1) * 4));
+	HIPCHK(hipMalloc(&ws.flag, (size_t)n_cap * 4));
+	HIPCHK(hipMalloc(&ws.ctr, LOC_CTR_WORDS * 8));
+	HIPCHK(hipMemsetAsync(ws.ctr, 0, LOC_CTR_WORDS * 8, h->st));
+	HIPCHK(hipHostMalloc((void**)&ws.h_small, 128, hipHostMallocDefault));
+	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&ws.ev[i]));
+	const int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, n_cap + 1, h->st);
+	if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+	HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
+	return 0;
+}
+
+/* the end of the slice that starts at r0: at most n_cap intervals and RB3_LOC_SLICE_PAIRS pairs, but one interval at least */
+static int64_t loc_slice_end(const LocWs &ws, const int64_t *size, int64_t r0, int64_t n, int64_t max_pos)
+{
+	int64_t r1 = r0, tot = 0;
+	while (r1 < n && r1 - r0 < ws.n_cap) {
+		const int64_t c = std::min(size[r1], max_pos);
+		if (r1 > r0 && tot + c > RB3_LOC_SLICE_PAIRS) break;
+		tot += c, ++r1;
+	}
+	return r1;
+}
+
+/* the most entries the heap of an interval of `size` rows can hold: its pieces are disjoint and, empty ones aside, not empty, so there are no more
+ * of them than rows; a split pushes one empty piece at most and only after a pair it has written (at most min(P, size) of those); and an interval
+ * of (P + 1) * 2^ss rows or more has P sampled rows in its first split, which answers it without a pop */
+static int64_t loc_heap_bound(int64_t size, int64_t max_pos, int ss)
+{
+	const int64_t lim = max_pos + 1 > (INT64_MAX >> ss) ? INT64_MAX : (max_pos + 1) << ss;
+	return std::min(size, lim) + std::min(size, max_pos) + 1;
+}
+
+/* nn intervals whose bounds lie on the device (lo = d_src[i * stride], then the end or, with is_size, the size) and whose sizes the caller has put
+ * in ws.h_size: their pairs to ws.h_pairs, pair k of interval i at ws.h_off[i] + k */
+static int loc_slice(rb3gpu_t *h, LocWs &ws, int64_t nn, const int64_t *d_src, int stride, int is_size, int64_t max_pos)
+{
+	if (nn < 1 || nn > ws.n_cap) return RB3GPU_EINTERNAL;
+	ws.h_off.resize((size_t)nn + 1);
+	int64_t tot = 0;
+	for (int64_t i = 0; i < nn; ++i) ws.h_off[i] = tot, tot += std::min(std::max<int64_t>(ws.h_size[i], 0), max_pos);
+	ws.h_off[nn] = tot;
+	++ws.n_slices, ws.n_iv += nn, ws.n_pairs += tot;
+	if (tot == 0) return 0;
+	if (tot > ws.pair_cap) {
+		const int64_t pc = std::max(tot, std::min(RB3_LOC_SLICE_PAIRS, 2 * ws.pair_cap));
+		if (ws.d_pairs) { HIPCHK(hipFree(ws.d_pairs)); ws.d_pairs = nullptr; }
+		if (ws.h_pairs) { HIPCHK(hipHostFree(ws.h_pairs)); ws.h_pairs = nullptr; }
+		ws.pair_cap = 0;
+		HIPCHK(hipMalloc(&ws.d_pairs, (size_t)pc * sizeof(LocPair)));
+		HIPCHK(hipHostMalloc((void**)&ws.h_pairs, (size_t)pc * sizeof(LocPair), hipHostMallocDefault));
+		ws.pair_cap = pc;
+	}
+	const IdxView ix = view_of(h);
+	Acc7 acc;
+	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const uint64_t *r2i = h->ssa_dev, *ssa = h->ssa_dev + h->ssa_m;
+	const int64_t cap = h->tn.locate_heap > 0 ? h->tn.locate_heap : RB3_LOC_HEAP;
+	auto grid = [](int64_t octets) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((octets * 8 + 255) / 256, 2048)); };
+	hipLaunchKernelGGL(k_locate_prep, dim3((unsigned)std::min<int64_t>((nn + 256) / 256, 4096)), dim3(256), 0, h->st, d_src, stride, is_size, nn, max_pos, ws.iv, ws.cnt);
+	size_t tb = ws.tmp_bytes + 256;
+	const int r = rb3kount_scan(ws.tmp, &tb, ws.cnt, ws.off, nn + 1, h->st);
+	if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+	HIPCHK(hipMemsetAsync(ws.flag, 0, (size_t)nn * 4, h->st));
+	HIPCHK(hipMemsetAsync(ws.ctr, 0, LOC_CTR_WORDS * 8, h->st));
+	HIPCHK(hipEventRecord(ws.ev[0], h->st));
+	hipLaunchKernelGGL(k_locate, dim3(grid(nn)), dim3(256), (size_t)(32 * cap) * sizeof(LocEnt), h->st, ix, acc, h->ssa_ss, h->ssa_ms, ssa, h->ssa_n, r2i, nn, (const int64_t*)nullptr,
+			(const int64_t*)ws.iv, (const uint32_t*)ws.cnt, (const int64_t*)ws.off, (int64_t)0, ws.d_pairs, cap, (const int64_t*)nullptr, (LocEnt*)nullptr, ws.flag, ws.ctr);
+	HIPCHK(hipEventRecord(ws.ev[1], h->st));
+	HIPCHK(hipMemcpyAsync(ws.h_small, ws.ctr, LOC_CTR_WORDS * 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(ws.h_small + LOC_CTR_WORDS, ws.off + nn, 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipGetLastError());
+	ws.ms += ev_ms(ws.ev[0], ws.ev[1]);
+	if ((int64_t)ws.h_small[LOC_CTR_WORDS] != tot || ws.h_small[LOC_CTR_ERR] != 0) return RB3GPU_EINTERNAL;
+	const int64_t n_ovf = (int64_t)ws.h_small[LOC_CTR_OVF];
+	if (n_ovf > 0) { // tier 2: the flagged intervals once more, heaps in global memory, as many at a time as the cap admits
+		ws.h_flag.resize((size_t)nn);
+		HIPCHK(hipMemcpyAsync(ws.h_flag.data(), ws.flag, (size_t)nn * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		const int64_t budget = std::max<int64_t>(1, (h->tn.locate_slice > 0 ? h->tn.locate_slice : RB3_LOC_T2_BYTES) / (int64_t)sizeof(LocEnt));
+		int64_t seen = 0;
+		HIPCHK(hipEventRecord(ws.ev[2], h->st));
+		for (int64_t i = 0; i < nn;) {
+			ws.h_idx.clear(), ws.h_hoff.clear();
+			int64_t ent = 0;
+			for (; i < nn; ++i) {
+				if (!ws.h_flag[i]) continue;
+				const int64_t b = loc_heap_bound(ws.h_size[i], max_pos, h->ssa_ss);
+				if (!ws.h_idx.empty() && ent + b > budget) break;
+				ws.h_idx.push_back(i), ws.h_hoff.push_back(ent), ent += b;
+			}
+			const int64_t k = (int64_t)ws.h_idx.size();
+			if (k == 0) break;
+			ws.h_hoff.push_back(ent);
+			seen += k;
+			if (k > ws.t2_cap) {
+				if (ws.idx) { HIPCHK(hipFree(ws.idx)); ws.idx = nullptr; }
+				if (ws.hoff) { HIPCHK(hipFree(ws.hoff)); ws.hoff = nullptr; }
+				ws.t2_cap = 0;
+				HIPCHK(hipMalloc(&ws.idx, (size_t)k * 8));
+				HIPCHK(hipMalloc(&ws.hoff, (size_t)(k + 1) * 8));
+				ws.t2_cap = k;
+			}
+			if (ent > ws.heap_cap) {
+				if (ws.heap) { HIPCHK(hipFree(ws.heap)); ws.heap = nullptr; }
+				ws.heap_cap = 0;
+				HIPCHK(hipMalloc(&ws.heap, (size_t)ent * sizeof(LocEnt)));
+				ws.heap_cap = ent;
+			}
+			HIPCHK(hipMemcpyAsync(ws.idx, ws.h_idx.data(), (size_t)k * 8, hipMemcpyHostToDevice, h->st));
+			HIPCHK(hipMemcpyAsync(ws.hoff, ws.h_hoff.data(), (size_t)(k + 1) * 8, hipMemcpyHostToDevice, h->st));
+			HIPCHK(hipMemsetAsync(ws.ctr + LOC_CTR_NEXT, 0, 8, h->st));
+			hipLaunchKernelGGL(k_locate, dim3(grid(k)), dim3(256), 0, h->st, ix, acc, h->ssa_ss, h->ssa_ms, ssa, h->ssa_n, r2i, k, (const int64_t*)ws.idx,
+					(const int64_t*)ws.iv, (const uint32_t*)ws.cnt, (const int64_t*)ws.off, (int64_t)0, ws.d_pairs, (int64_t)0, (const int64_t*)ws.hoff, ws.heap, ws.flag, ws.ctr);
+			HIPCHK(hipStreamSynchronize(h->st)); // (the host lists and the heaps are reused by the next slice)
+			HIPCHK(hipGetLastError());
+		}
+		HIPCHK(hipEventRecord(ws.ev[3], h->st));
+		HIPCHK(hipMemcpyAsync(ws.h_small, ws.ctr, LOC_CTR_WORDS * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		ws.ms += ev_ms(ws.ev[2], ws.ev[3]);
+		if (seen != n_ovf || ws.h_small[LOC_CTR_ERR] != 0) return RB3GPU_EINTERNAL;
+		ws.n_t2 += n_ovf;
+	}
+	ws.pops += (int64_t)ws.h_small[LOC_CTR_POPS];
+	ws.max_heap = std::max(ws.max_heap, (int64_t)ws.h_small[LOC_CTR_MAXHEAP]);
+	HIPCHK(hipMemcpyAsync(ws.h_pairs, ws.d_pairs, (size_t)tot * sizeof(LocPair), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	return 0;
+}
+
+static void loc_stats(const LocWs &ws, double t0, rb3gpu_locate_stats_t *st)
+{
+	if (!st) return;
+	st->ms_total = (now_s() - t0) * 1e3, st->ms_locate = ws.ms, st->n_pops = ws.pops, st->n_intervals = ws.n_iv, st->n_tier2 = ws.n_t2, st->max_heap = ws.max_heap,
+	st->n_pairs = ws.n_pairs, st->n_slices = ws.n_slices;
+}
+
+int rb3gpu_locate(rb3gpu_t *h, int64_t n, const int64_t *lo, const int64_t *hi, int64_t max_pos, rb3gpu_locate_cb cb, void *ud, rb3gpu_locate_stats_t *st)
+{
+	static_assert(sizeof(LocPair) == sizeof(rb3gpu_pos_t), "one pair layout on both sides");
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || n < 0 || !cb || max_pos < 0 || (n > 0 && (!lo || !hi))) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr || h->ssa_dev == nullptr) return RB3GPU_ESTATE;
+	if (max_pos > 0x7fffffffLL) max_pos = 0x7fffffffLL; // (an int in the reference)
+	for (int64_t i = 0; i < n; ++i)
+		if (lo[i] < hi[i] && (lo[i] < h->acc[1] || hi[i] > h->acc[6])) return RB3GPU_EINVAL; // (rows of sentinels: the reference reads in front of ssa[])
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	if (n == 0) return 0;
+	LocWs ws;
+	int r;
+	if ((r = loc_init(h, ws, std::min(n, RB3_LOC_SLICE_IV), true)) < 0) return r;
+	std::vector<int64_t> size((size_t)n), pair;
+	for (int64_t i = 0; i < n; ++i) size[i] = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
+	int ret = 0;
+	for (int64_t r0 = 0; r0 < n && ret == 0;) {
+		const int64_t r1 = loc_slice_end(ws, size.data(), r0, n, max_pos), nn = r1 - r0;
+		pair.resize((size_t)nn * 2);
+		for (int64_t i = 0; i < nn; ++i) pair[2 * i] = lo[r0 + i], pair[2 * i + 1] = hi[r0 + i];
+		ws.h_size.assign(size.begin() + r0, size.begin() + r1);
+		HIPCHK(hipMemcpyAsync(ws.src, pair.data(), (size_t)nn * 16, hipMemcpyHostToDevice, h->st));
+		if ((r = loc_slice(h, ws, nn, ws.src, 2, 0, max_pos)) < 0) return r;
+		ret = cb(ud, r0, nn, ws.h_off.data(), (const rb3gpu_pos_t*)ws.h_pairs);
+		r0 = r1;
+	}
+	loc_stats(ws, t0, st);
+	return ret;
+}
+
 /* ---- mem: super-maximal exact matches of queries (rb3gpu_mem.h) ------------------------------- */
 
 #define RB3_MEM_CHUNK 2048                    // query symbols per walker unless the caller says otherwise (README: the measured knee)
@@ -4447,11 +4728,13 @@ struct MemWs {
 	}
 };
 
-int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk,
-		rb3gpu_mem_cb cb, void *ud, rb3gpu_mem_stats_t *st)
+/* max_pos > 0: the records of a slice stay on the device until their intervals are located, and reach cbp with their positions */
+static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk, int64_t max_pos,
+		rb3gpu_mem_cb cb, rb3gpu_mem_pos_cb cbp, void *ud, rb3gpu_mem_stats_t *st, rb3gpu_locate_stats_t *lst)
 {
 	if (st) memset(st, 0, sizeof(*st));
-	if (!h || n_query < 0 || n_query > 0x7fffffffLL || !cb || min_len < 1 || min_occ < 1 || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
+	if (lst) memset(lst, 0, sizeof(*lst));
+	if (!h || n_query < 0 || n_query > 0x7fffffffLL || (max_pos > 0 ? !cbp : !cb) || min_len < 1 || min_occ < 1 || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
 	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
 	int64_t max_len = 0;
 	for (int64_t q = 0; q < n_query; ++q) {
@@ -4464,6 +4747,8 @@ int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
 	// both strands (rb3_fmi_is_symmetric, fm-index.h:135): the forward extension is a backward extension of the reverse complement
 	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE;
+	if (max_pos > 0 && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
+	if (max_pos > 0x7fffffffLL) max_pos = 0x7fffffffLL;
 	if (chunk <= 0) chunk = RB3_MEM_CHUNK;
 	if (chunk > 0x7fffffffLL) chunk = 0x7fffffffLL;
 	HIPCHK(hipSetDevice(h->dev));
@@ -4486,6 +4771,11 @@ int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8
 	int64_t cap = h->tn.mem_slice > 0 ? h->tn.mem_slice : RB3_MEM_SLICE;
 	cap = std::min(total, std::max(cap, std::min(chunk, max_len)));
 	MemWs ws;
+	LocWs lws;
+	if (max_pos > 0) {
+		const int r = loc_init(h, lws, std::min(cap, RB3_LOC_SLICE_IV), false);
+		if (r < 0) return r;
+	}
 	HIPCHK(hipMalloc(&ws.sym, (size_t)total + 64));
 	HIPCHK(hipMalloc(&ws.qoff, (size_t)(n_query + 1) * 8));
 	HIPCHK(hipMalloc(&ws.wq, (size_t)nw * 4));
@@ -4550,14 +4840,40 @@ int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8
 			HIPCHK(hipMemcpyAsync(ws.h_out, ws.d_out, (size_t)c * sizeof(MemOut), hipMemcpyDeviceToHost, h->st));
 			HIPCHK(hipStreamSynchronize(h->st));
 			n_rec += c;
-			ret = cb(ud, c, (const rb3gpu_mem_rec_t*)ws.h_out);
+			if (max_pos > 0) { // the intervals of the records, read where k_mem_gather left them
+				for (int64_t r0 = 0; r0 < c && ret == 0;) {
+					const int64_t lim = std::min(c - r0, lws.n_cap);
+					lws.h_size.resize((size_t)lim);
+					for (int64_t i = 0; i < lim; ++i) lws.h_size[i] = ws.h_out[r0 + i].size;
+					const int64_t nn = loc_slice_end(lws, lws.h_size.data(), 0, lim, max_pos);
+					lws.h_size.resize((size_t)nn);
+					const int r = loc_slice(h, lws, nn, (const int64_t*)(ws.d_out + r0) + 1, (int)(sizeof(MemOut) / 8), 1, max_pos);
+					if (r < 0) return r;
+					ret = cbp(ud, nn, (const rb3gpu_mem_rec_t*)ws.h_out + r0, lws.h_off.data(), (const rb3gpu_pos_t*)lws.h_pairs);
+					r0 += nn;
+				}
+			} else ret = cb(ud, c, (const rb3gpu_mem_rec_t*)ws.h_out);
 		}
 		w0 = w1;
 	}
 	HIPCHK(hipMemcpyAsync(ws.h_small, ws.ctr + 1, 8, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_steps = ws.h_small[0], st->n_walkers = nw, st->n_records = n_rec, st->n_slices = n_slices;
+	if (max_pos > 0) loc_stats(lws, t0, lst);
 	return ret;
+}
+
+int rb3gpu_mem(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk,
+		rb3gpu_mem_cb cb, void *ud, rb3gpu_mem_stats_t *st)
+{
+	return mem_run(h, n_query, offsets, symbols, min_len, min_occ, chunk, 0, cb, nullptr, ud, st, nullptr);
+}
+
+int rb3gpu_mem_pos(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk, int64_t max_pos,
+		rb3gpu_mem_pos_cb cb, void *ud, rb3gpu_mem_stats_t *st, rb3gpu_locate_stats_t *lst)
+{
+	if (max_pos < 1) return RB3GPU_EINVAL;
+	return mem_run(h, n_query, offsets, symbols, min_len, min_occ, chunk, max_pos, nullptr, cb, ud, st, lst);
 }
 
 } // extern "C"

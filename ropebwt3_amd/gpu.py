@@ -64,6 +64,18 @@ class MemStats(ctypes.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+POS = np.dtype([("sid", "<i8"), ("pos", "<i8")])  # rb3gpu_pos_t
+LOCATE_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p)
+MEM_POS_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p)
+
+
+class LocateStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_locate", ctypes.c_double), ("n_pops", ctypes.c_int64), ("n_intervals", ctypes.c_int64), ("n_tier2", ctypes.c_int64),
+                ("max_heap", ctypes.c_int64), ("n_pairs", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
     "rb3gpu_opt_init": (None, [ctypes.POINTER(Opt)]),
@@ -169,6 +181,13 @@ SYMBOLS = {
     "rb3gpu_device_of": (ctypes.c_int, [ctypes.c_void_p]),
     "rb3gpu_kount": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, KOUNT_F, ctypes.c_void_p, ctypes.POINTER(KountStats)]),
     "rb3gpu_stream_of": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "rb3gpu_ssa_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "rb3gpu_ssa_keep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "rb3gpu_ssa_drop": (ctypes.c_int, [ctypes.c_void_p]),
+    "rb3gpu_ssa_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]),
+    "rb3gpu_locate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, LOCATE_F, ctypes.c_void_p, ctypes.POINTER(LocateStats)]),
+    "rb3gpu_mem_pos": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_POS_F, ctypes.c_void_p,
+                                      ctypes.POINTER(MemStats), ctypes.POINTER(LocateStats)]),
     "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
 }
 
@@ -686,11 +705,54 @@ class Rb3Gpu:
             return np.zeros((0, int(k)), dtype=np.uint8), np.zeros((0, len(hs)), dtype=np.int64)
         return np.concatenate(kms), np.concatenate(cts)
 
-    def mem(self, queries, min_len=19, min_occ=1, chunk=None, stats=None):
+    def set_ssa(self, ssa_shift, ms, r2i, ssa):
+        """rb3gpu_ssa_set: the sampled suffix array of the index as a .ssa file holds it (read_ssa), uploaded and kept on the device"""
+        r2i = np.ascontiguousarray(r2i, dtype=np.uint64)
+        ssa = np.ascontiguousarray(ssa, dtype=np.uint64)
+        self._chk(self._lib.rb3gpu_ssa_set(self._h, int(ssa_shift), int(ms), r2i.size, ssa.size, r2i.ctypes.data if r2i.size else None, ssa.ctypes.data if ssa.size else None), "rb3gpu_ssa_set")
+
+    def keep_ssa(self, ssa_shift):
+        """rb3gpu_ssa_keep: the sampled suffix array built on the device and kept there"""
+        self._chk(self._lib.rb3gpu_ssa_keep(self._h, int(ssa_shift)), "rb3gpu_ssa_keep")
+
+    def drop_ssa(self):
+        self._chk(self._lib.rb3gpu_ssa_drop(self._h), "rb3gpu_ssa_drop")
+
+    def ssa_info(self):
+        """(ssa_shift, n_ssa) of the sampled suffix array on the handle, None without one"""
+        ss, n = ctypes.c_int(), ctypes.c_int64()
+        return (ss.value, n.value) if self._lib.rb3gpu_ssa_info(self._h, ctypes.byref(ss), ctypes.byref(n)) == 0 else None
+
+    def locate(self, lo, hi, max_pos, stats=None):
+        """rb3gpu_locate: up to max_pos positions of the rows of every interval [lo[i], hi[i]), the reference's pairs in the reference's order:
+        (off, pos) with the pairs of interval i at pos[off[i]:off[i + 1]] (POS: sid, pos); stats: a dict that receives rb3gpu_locate_stats_t"""
+        lo = np.ascontiguousarray(lo, dtype=np.int64)
+        hi = np.ascontiguousarray(hi, dtype=np.int64)
+        if lo.shape != hi.shape or lo.ndim != 1:
+            raise ValueError("lo and hi must be one-dimensional and of one length")
+        offs, got = [np.zeros(1, dtype=np.int64)], []
+        base = [0]
+
+        def cb(_ud, _i0, n, off, pos):
+            o = np.ctypeslib.as_array(off, shape=(n + 1,)).copy()
+            got.append(np.frombuffer(ctypes.string_at(pos, int(o[n]) * POS.itemsize), dtype=POS).copy())
+            offs.append(o[1:] + base[0])
+            base[0] += int(o[n])
+            return 0
+        st = LocateStats()
+        self._chk(self._lib.rb3gpu_locate(self._h, lo.size, lo.ctypes.data if lo.size else None, hi.ctypes.data if hi.size else None, int(max_pos), LOCATE_F(cb), None, ctypes.byref(st)),
+                  "rb3gpu_locate")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return np.concatenate(offs), (np.concatenate(got) if got else np.zeros(0, dtype=POS))
+
+    def mem(self, queries, min_len=19, min_occ=1, chunk=None, stats=None, max_pos=0, locate_stats=None):
         """rb3gpu_mem: the super-maximal exact matches of the queries (each a uint8 array of nt6 codes 0..5, or bytes / str of characters) of at
         least min_len symbols and min_occ occurrences, as the reference's `mem` finds them: a structured array (MEM_REC: query, x0, size, st, en)
         in the reference's output order.  chunk: query symbols per walker (None: the engine's default; the result does not depend on it);
-        stats: a dict that receives rb3gpu_mem_stats_t"""
+        stats: a dict that receives rb3gpu_mem_stats_t.  max_pos > 0 (rb3gpu_mem_pos; the handle needs set_ssa / keep_ssa): returns (records, off, pos)
+        with up to max_pos positions per record, those of record i at pos[off[i]:off[i + 1]] (POS), as Rb3Gpu.locate gives them for [x0, x0 + size);
+        locate_stats: a dict that receives rb3gpu_locate_stats_t"""
         qs = [nt6_of(q) for q in queries]
         off = np.zeros(len(qs) + 1, dtype=np.int64)
         if qs:
@@ -703,6 +765,24 @@ class Rb3Gpu:
             got.append(np.frombuffer(ctypes.string_at(recs, n * MEM_REC.itemsize), dtype=MEM_REC).copy())
             return 0
         st = MemStats()
+        if max_pos > 0:
+            offs, pairs, base = [np.zeros(1, dtype=np.int64)], [], [0]
+
+            def cbp(_ud, n, recs, poff, pos):
+                o = np.ctypeslib.as_array(poff, shape=(n + 1,)).copy()
+                got.append(np.frombuffer(ctypes.string_at(recs, n * MEM_REC.itemsize), dtype=MEM_REC).copy())
+                pairs.append(np.frombuffer(ctypes.string_at(pos, int(o[n]) * POS.itemsize), dtype=POS).copy())
+                offs.append(o[1:] + base[0])
+                base[0] += int(o[n])
+                return 0
+            lst = LocateStats()
+            self._chk(self._lib.rb3gpu_mem_pos(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, int(min_len), int(min_occ), 0 if chunk is None else int(chunk),
+                                               int(max_pos), MEM_POS_F(cbp), None, ctypes.byref(st), ctypes.byref(lst)), "rb3gpu_mem_pos")
+            if stats is not None:
+                stats.update(st.as_dict())
+            if locate_stats is not None:
+                locate_stats.update(lst.as_dict())
+            return (np.concatenate(got) if got else np.zeros(0, dtype=MEM_REC)), np.concatenate(offs), (np.concatenate(pairs) if pairs else np.zeros(0, dtype=POS))
         self._chk(self._lib.rb3gpu_mem(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, int(min_len), int(min_occ), 0 if chunk is None else int(chunk),
                                        MEM_F(cb), None, ctypes.byref(st)), "rb3gpu_mem")
         if stats is not None:
@@ -969,10 +1049,42 @@ def nt6_of(q):
     return np.ascontiguousarray(q, dtype=np.uint8)
 
 
-def mem_lines(recs, names=None, first_id=0):
+def read_ssa(path):
+    """a .ssa file (rb3_ssa_dump, ssa.c:198-213): (ssa_shift, ms, r2i, ssa), the arrays uint64"""
+    with open(path, "rb") as f:
+        b = f.read()
+    if b[:4] != b"SSA\1" or len(b) < 28:
+        raise ValueError("not a sampled suffix array: %s" % path)
+    ss, ms = np.frombuffer(b, dtype="<u4", count=2, offset=4)
+    m, n = np.frombuffer(b, dtype="<i8", count=2, offset=12)
+    if len(b) < 28 + 8 * (int(m) + int(n)):
+        raise ValueError("truncated sampled suffix array: %s" % path)
+    return int(ss), int(ms), np.frombuffer(b, dtype="<u8", count=int(m), offset=28).copy(), np.frombuffer(b, dtype="<u8", count=int(n), offset=28 + 8 * int(m)).copy()
+
+
+def mem_lines(recs, names=None, first_id=0, positions=None, seq_names=None, lengths=None):
     """the reference's `mem` output for the records of Rb3Gpu.mem: name, start, end, occurrences per match (bytes); names[q] is the name of
-    query q (None, or a None entry: seq<first_id + q + 1>, as for queries without a name)"""
+    query q (None, or a None entry: seq<first_id + q + 1>, as for queries without a name).  positions = (off, pos) of Rb3Gpu.mem(max_pos=...)
+    with the names and lengths of the indexed sequences (seq_names, lengths: what <index>.len.gz holds) adds the `-p` columns"""
     out = []
+    if positions is not None:
+        off, pos = positions
+        for i, r in enumerate(recs):
+            q = int(r["query"])
+            nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
+            if isinstance(nm, str):
+                nm = nm.encode()
+            line = b"%s\t%d\t%d\t%d" % (nm, r["st"], r["en"], r["size"])
+            a, b = int(off[i]), int(off[i + 1])
+            if b > a:
+                line += b"\t%d" % (b - a)
+                for p in pos[a:b]:
+                    s = int(p["sid"]) >> 1
+                    sn = seq_names[s].encode() if isinstance(seq_names[s], str) else seq_names[s]
+                    x = int(lengths[s]) - (int(p["pos"]) + int(r["en"]) - int(r["st"])) if int(p["sid"]) & 1 else int(p["pos"])
+                    line += b"\t%s:%s:%d" % (sn, b"-" if int(p["sid"]) & 1 else b"+", x)
+            out.append(line + b"\n")
+        return b"".join(out)
     for r in recs:
         q = int(r["query"])
         nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
