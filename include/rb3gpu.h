@@ -526,6 +526,26 @@ typedef int (*rb3gpu_mem_pos_cb)(void *ud, int64_t n, const rb3gpu_mem_rec_t *re
 int rb3gpu_mem_pos(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t min_occ, int64_t chunk, int64_t max_pos,
 		rb3gpu_mem_pos_cb cb, void *ud, rb3gpu_mem_stats_t *st, rb3gpu_locate_stats_t *lst);
 
+/* haplotype diversity of windows (`ropebwt3 hapdiv`, search.c and the BWA-SW dynamic program sw_core, bwa-sw.c:329-526 of the reference, in its end-to-end
+ * mode on a linear query with end_len 1): window i = symbols[win_off[i], win_off[i] + k) (nt6 codes; the caller makes the windows of its queries, the CLI
+ * every -w symbols) is aligned end to end against the index, n_best cells kept per row as the reference keeps them, ties included.  Its record: n_al, the
+ * alignments of the last row that no better one contains, that end in a match or mismatch, score at least min_sc and lie within e2e_drop (< 0: off) of the
+ * best; max_ed, the largest edit distance among them; n_hap[min(ed, 6)], the occurrences by edit distance.  A window without an alignment is nine zeros.
+ * Records reach cb in window order, one piece per slice of rb3gpu_tune "hapdiv_slice" windows (default 64 K; host memory valid during the call only):
+ * the n windows from i0 on.  A nonzero return from cb stops the call and is returned.  A wave per window; the call holds the symbols, 36 bytes per window
+ * of a slice and, per window in flight (at most 2048, fewer where the free memory says so), 12 bytes per cell of (k + 1) * n_best and a candidate table
+ * for the windows whose table outgrows LDS ("hapdiv_table" slots, default and at most 256).  RB3GPU_EINVAL for k < 1, n_best < 1, (k + 1) * n_best of
+ * 2^32 or more, or a NULL callback; RB3GPU_ESTATE without an index or with one that does not hold both strands; RB3GPU_EINTERNAL if a window cannot be
+ * represented (a table or stack beyond its capacity, a backtrack into a gap whose column was not kept: the reference stops on an assertion there) --
+ * never a wrong record.  st (may be NULL): ms_total wall time, ms_dp the kernel alone (HIP events), n_ext extensions (a rank pair each), n_windows,
+ * n_tier2 windows whose table went to global memory, n_slices */
+typedef struct { int32_t n_best, min_sc, match, mis, gap_open, gap_ext, e2e_drop; } rb3gpu_hapdiv_opt_t;
+typedef struct { int32_t n_al, max_ed, n_hap[7]; } rb3gpu_hapdiv_rec_t;
+typedef int (*rb3gpu_hapdiv_cb)(void *ud, int64_t i0, int64_t n, const rb3gpu_hapdiv_rec_t *recs);
+typedef struct { double ms_total, ms_dp; int64_t n_ext, n_windows, n_tier2, n_slices; } rb3gpu_hapdiv_stats_t;
+int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint8_t *symbols, int32_t k, const rb3gpu_hapdiv_opt_t *opt,
+		rb3gpu_hapdiv_cb cb, void *ud, rb3gpu_hapdiv_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -542,6 +562,7 @@ int rb3gpu_stream_sync(void *stream);
  *   spacing 2^S of the walker list the engine makes for the BWT-only entry points; -1 = by the size of the batch), "abs_limit" N (indexes
  *   of fewer than N symbols carry the LF base in their slot headers; at most 2^32, only before an index exists: RB3GPU_ESTATE after);
  *   "mem_slice" N (query symbols per output slice of rb3gpu_mem; 0 = 8 M);
+ *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c
  * Test hooks "force_fallback", "tent_limit", "text_mode" exist only in the test build of the library (compiled with

@@ -1682,6 +1682,173 @@ no_side:
 	return 1;
 }
 
+/* hapdiv: the windows of every query (k symbols every w, search.c:384-393) through rb3gpu_hapdiv, batch by batch; the lines of write_hapdiv */
+typedef struct { int32_t *r; int64_t n; } hapdiv_out_t;
+
+static int hapdiv_sink(void *ud, int64_t i0, int64_t n, const rb3gpu_hapdiv_rec_t *recs)
+{
+	hapdiv_out_t *o = (hapdiv_out_t*)ud;
+	if (i0 < 0 || i0 + n > o->n) return -1;
+	memcpy(o->r + 9 * i0, recs, (size_t)n * 36);
+	return 0;
+}
+
+static const struct option hapdiv_long_opts[] = {
+	{ "gap", required_argument, 0, 403 },
+	{ "cov", no_argument, 0, 403 },
+	{ "old-mem", no_argument, 0, 403 },
+	{ "all-e2e", no_argument, 0, 403 },
+	{ "no-ssa", no_argument, 0, 406 },
+	{ "seq", no_argument, 0, 406 },
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_hapdiv(int argc, char *argv[])
+{
+	int c, is_line = 0, device = 0, ret = 0, j;
+	int64_t k = 101, w = 50, batch_size = 100000000, id = 0, n_win_all = 0, n_ext = 0, n_tier2 = 0, n_slices = 0, n_batches = 0;
+	double ms_dp = 0, ms_engine = 0;
+	rb3gpu_hapdiv_opt_t ho = { 25, 30, 1, 3, 5, 2, -1 };
+	rb3gpu_t *h;
+	rb3gpu_opt_t gopt;
+	int64_t acc[7];
+	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0}, out = {0, 0, 0};
+	int64_t *off = 0, *name_off = 0, m_q = 0, *win = 0, m_win = 0;
+	hapdiv_out_t o = { 0, 0 };
+	_Static_assert(sizeof(rb3gpu_hapdiv_rec_t) == 36, "nine numbers per window");
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", hapdiv_long_opts, 0)) >= 0) {
+		if (c == 'L') is_line = 1;
+		else if (c == 'a') k = atoi(optarg);
+		else if (c == 'w') w = atoi(optarg);
+		else if (c == 'N') ho.n_best = atoi(optarg);
+		else if (c == 'm') ho.min_sc = atoi(optarg);
+		else if (c == 'A') ho.match = atoi(optarg);
+		else if (c == 'B') ho.mis = atoi(optarg);
+		else if (c == 'O') ho.gap_open = atoi(optarg);
+		else if (c == 'E') ho.gap_ext = atoi(optarg);
+		else if (c == 'y') ho.e2e_drop = atoi(optarg);
+		else if (c == 'K') batch_size = rb3h_parse_num(optarg);
+		else if (c == 't' || c == 'C' || c == 'M') {} /* threads, the rank cache, the mmap loader: nothing to size here, and none changes an answer */
+		else if (c == 'e' || c == 'k' || c == 'b' || c == 'u' || c == 'j' || c == 'l' || c == 'c' || c == 406) {} /* hapdiv is end to end with end_len 1 whatever these say (search.c:498-505) */
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+		else if (c == '?') return 1;
+		else { fprintf(stderr, "ERROR: option not supported by hapdiv (it belongs to sw or mem)\n"); return 1; }
+	}
+	if (argc - optind < 2) {
+		fprintf(stdout, "Usage: ropebwt3-amd hapdiv [options] <idx.fmr> <seq.fa> [...]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -a INT      annotate sliding INT-mers [%ld]\n", (long)k);
+		fprintf(stderr, "  -w INT      k-mer step size for annotation [%ld]\n", (long)w);
+		fprintf(stderr, "  -N INT      keep up to INT hits per DAG node [%d]\n", ho.n_best);
+		fprintf(stderr, "  -A INT      match score [%d]\n", ho.match);
+		fprintf(stderr, "  -B INT      mismatch penalty [%d]\n", ho.mis);
+		fprintf(stderr, "  -O INT      gap open penalty [%d]\n", ho.gap_open);
+		fprintf(stderr, "  -E INT      gap extension penalty; a k-long gap costs O+k*E [%d]\n", ho.gap_ext);
+		fprintf(stderr, "  -m INT      min alignment score [%d]\n", ho.min_sc);
+		fprintf(stderr, "  -y INT      report alignments within INT of the best score (-1: all) [%d]\n", ho.e2e_drop);
+		fprintf(stderr, "  -L          one sequence per line in the input\n");
+		fprintf(stderr, "  -K NUM      query batch size [100m]\n");
+		return 0;
+	}
+	if (k < 1) { fprintf(stderr, "ERROR: the k-mer length (-a) must be at least 1\n"); return 1; }
+	if (w < 1) { fprintf(stderr, "ERROR: the step size (-w) must be at least 1\n"); return 1; }
+	if (ho.n_best < 1) { fprintf(stderr, "ERROR: the number of hits kept per row (-N) must be at least 1\n"); return 1; }
+	if (k > 0x7ffffffeLL || (k + 1) * (int64_t)ho.n_best >= 0xFFFFFFFFLL || ho.n_best >= (1 << 24)) { fprintf(stderr, "ERROR: -a times -N is too large\n"); return 1; }
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	h = rb3gpu_create(&gopt);
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
+	if (load_index(h, argv[optind]) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	rb3gpu_get_acc(h, acc);
+	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	for (j = optind + 1; j < argc && ret == 0; ++j) {
+		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
+		int eof = 0;
+		if (fp == 0) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
+			ret = 1;
+			break;
+		}
+		while (!eof && ret == 0) { /* a batch: whole records until their symbols reach -K (search.c:366-378) */
+			int64_t n_q = 0, l, n_win = 0, q, x;
+			const uint8_t *s;
+			const char *name;
+			sym.l = names.l = 0;
+			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
+				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
+				if (n_q + 2 > m_q) {
+					m_q = m_q ? m_q * 2 : 1024;
+					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
+				}
+				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
+				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
+				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+				if (n_q == 0) off[0] = 0;
+				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
+				rb3h_char2nt6(l, sym.s + sym.l);
+				sym.l += l, off[++n_q] = sym.l;
+				name_off[n_q - 1] = name ? names.l : -1;
+				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
+				if (sym.l >= batch_size || n_q >= 0x7fffffffLL) break;
+			}
+			if (l < 0) eof = 1;
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q == 0 || ret != 0) continue;
+			for (q = 0; q < n_q; ++q) {
+				const int64_t len = off[q + 1] - off[q];
+				n_win += len < k ? 0 : (len - k) / w + 1;
+			}
+			if (n_win > m_win) {
+				m_win = n_win + (n_win >> 1) + 64;
+				win = (int64_t*)realloc(win, (size_t)m_win * 8), o.r = (int32_t*)realloc(o.r, (size_t)m_win * 36);
+				if (win == 0 || o.r == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+			}
+			for (q = 0, n_win = 0; q < n_q; ++q)
+				for (x = 0; x + k <= off[q + 1] - off[q]; x += w) win[n_win++] = off[q] + x;
+			o.n = n_win;
+			if (n_win > 0) {
+				rb3gpu_hapdiv_stats_t st;
+				int64_t at = 0;
+				const int r = rb3gpu_hapdiv(h, n_win, win, sym.s, (int32_t)k, &ho, hapdiv_sink, &o, &st);
+				if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to align the windows: %s\n", rb3gpu_strerror(r)); ret = 1; break; }
+				for (q = 0; q < n_q && ret == 0; ++q) {
+					const int64_t len = off[q + 1] - off[q], nw = len < k ? 0 : (len - k) / w + 1;
+					if (nw > 0 && rb3h_hapdiv_format(&out, name_off[q] >= 0 ? (const char*)names.s + name_off[q] : 0, id + q, k, w, nw, o.r + 9 * at) < 0) ret = 1;
+					at += nw;
+					if (out.l > (1 << 20) || q == n_q - 1) {
+						if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) ret = 1;
+						out.l = 0;
+					}
+				}
+				if (ret) { fprintf(stderr, "ERROR: failed to write the output\n"); break; }
+				n_win_all += n_win, n_ext += st.n_ext, n_tier2 += st.n_tier2, n_slices += st.n_slices, ms_dp += st.ms_dp, ms_engine += st.ms_total;
+			}
+			id += n_q, ++n_batches;
+			if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] processed %lld sequences\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_q);
+		}
+		rb3h_seq_close(fp);
+	}
+	if (fflush(stdout) != 0 && ret == 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (rb3h_verbose >= 3 && ret == 0)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld windows in %lld slice(s), %lld extensions, %lld windows with a table in global memory; %.3f ms in the engine, the DP kernel %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_win_all, (long long)n_slices, (long long)n_ext, (long long)n_tier2, ms_engine, ms_dp);
+	free(out.s); free(o.r); free(win); free(sym.s); free(names.s); free(off); free(name_off);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* recode: decode an FMD/FMR file on the host and write it back as plain text (default), FMD (-d)
  * or FMR (-b).  Host-only utility; also the CPU-side test bench of the two codecs. */
 typedef struct { int64_t cnt[6]; runvec_t rv; } recode_t;
@@ -1782,6 +1949,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    ssa        generate sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    kount      count k-mers in one or more FM-indexes (on an MI355X)\n");
 	fprintf(fp, "    mem        find super-maximal exact matches of queries (on an MI355X)\n");
+	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
 	fprintf(fp, "    plain2fmd  convert BWT in plain text to FMD (host only)\n");
 	fprintf(fp, "    version    print the version number\n");
@@ -1799,6 +1967,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "ssa") == 0) ret = main_ssa(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "kount") == 0) ret = main_kount(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "mem") == 0) ret = main_mem(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "plain2fmd") == 0) ret = main_plain2fmd(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "version") == 0) { printf("%s\n", RB3H_VERSION); return 0; }

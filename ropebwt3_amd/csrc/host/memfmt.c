@@ -1,7 +1,7 @@
 /*
  * memfmt.c -- the text `mem` writes for one query (write_per_seq, search.c:240-325, and the gaps of worker_for_seq,
  * search.c:110-126), into a buffer that its caller writes out in large pieces: a printf per line is the whole wall
- * time of a command that prints millions of them.
+ * time of a command that prints millions of them.  And the lines of `hapdiv` (write_hapdiv, search.c:327-353).
  */
 #include <stdlib.h>
 #include <string.h>
@@ -126,6 +126,25 @@ int rb3h_mem_format_pos(rb3h_buf_t *out, const char *name, int64_t id, int64_t n
 		}
 		if (fmt_reserve(out, 1) < 0) return -1;
 		out->s[out->l++] = '\n';
+	}
+	return 0;
+}
+
+int rb3h_hapdiv_format(rb3h_buf_t *out, const char *name, int64_t id, int64_t k, int64_t w, int64_t n, const int32_t *r)
+{
+	const size_t l_name = name ? strlen(name) : 0;
+	int64_t i, j;
+	for (i = 0; i < n; i = j) {
+		uint8_t *p;
+		int e;
+		for (j = i + 1; j < n && memcmp(r + 9 * i, r + 9 * j, 36) == 0; ++j) {}
+		if (fmt_reserve(out, (int64_t)l_name + 24 + 11 * 22 + 2) < 0) return -1;
+		p = fmt_name(out->s + out->l, name, l_name, id);
+		*p++ = '\t', p = fmt_num(p, i * w);
+		*p++ = '\t', p = fmt_num(p, (j - 1) * w + k);
+		for (e = 0; e < 9; ++e) *p++ = '\t', p = fmt_num(p, r[9 * i + e]);
+		*p++ = '\n';
+		out->l = p - out->s;
 	}
 	return 0;
 }

@@ -77,6 +77,9 @@ int rb3h_mem_format(rb3h_buf_t *out, int mode, int64_t min_gap, const char *name
 typedef struct { int64_t sid, pos; } rb3h_pos_t;                           /* = rb3gpu_pos_t */
 typedef struct { int64_t n_seq; char **name; int64_t *len; } rb3h_sid_t;
 int rb3h_mem_format_pos(rb3h_buf_t *out, const char *name, int64_t id, int64_t n, const rb3h_mem_rec_t *r, const int64_t *off, const rb3h_pos_t *pos, const rb3h_sid_t *sid);
+/* the text `hapdiv` writes for one query (write_hapdiv, search.c:327-353): its n windows start every w symbols and are k long; r holds nine numbers per
+ * window (n_al, max_ed, n_hap[0..6]); consecutive windows with the same nine make one line: name, first start, last end, the nine */
+int rb3h_hapdiv_format(rb3h_buf_t *out, const char *name, int64_t id, int64_t k, int64_t w, int64_t n, const int32_t *r);
 
 /* ---- the files beside an index that `mem -p` reads (sidefile.c) ---- */
 typedef struct { int32_t ss, ms; int64_t m, n_ssa; uint64_t *r2i, *ssa; } rb3h_ssa_t;

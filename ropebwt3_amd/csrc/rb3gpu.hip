@@ -26,6 +26,7 @@
 #include "rb3gpu_part.h"
 #include "rb3gpu_kount.h"
 #include "rb3gpu_mem.h"
+#include "rb3gpu_hapdiv.h"
 #include "rb3gpu_locate.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -149,6 +150,8 @@ struct Tune {
 	int sh_block = 0;        // threads per block of k_sh_round at eight states per octet: 256 or 1024; 0: 1024 below 3 M chains
 	int sh_states = 0;       // states per octet of k_sh_round (1, 2, 4, 8); 0: by the number of chains
 	int64_t mem_slice = 0;   // rb3gpu_mem: query symbols whose matches one output slice holds (0: 8 M; a slice always takes at least one walker)
+	int64_t hapdiv_slice = 0;// rb3gpu_hapdiv: windows per launch and per piece of records handed to the callback (0: 64 K)
+	int64_t hapdiv_table = 0;// rb3gpu_hapdiv: slots of a window's candidate table in LDS (0: 256, at most 256); a table that needs more lies in global memory
 	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
 	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
@@ -662,6 +665,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "lf_check")) t.lf_check = v < 0 ? 0 : v > (1 << 30) ? (1 << 30) : (int)v;
 	else if (!strcmp(key, "fmd_piece")) t.fmd_piece = v < 0 ? 0 : v;
 	else if (!strcmp(key, "mem_slice")) t.mem_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "hapdiv_slice")) t.hapdiv_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "hapdiv_table")) t.hapdiv_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
 	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
 	else if (!strcmp(key, "locate_slice")) t.locate_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sh_host_rounds")) t.sh_host_rounds = v < 0 ? -1 : v != 0; // (-1: rounds on the device whatever the number of chains)
@@ -701,7 +706,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -4874,6 +4879,113 @@ int rb3gpu_mem_pos(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 {
 	if (max_pos < 1) return RB3GPU_EINVAL;
 	return mem_run(h, n_query, offsets, symbols, min_len, min_occ, chunk, max_pos, nullptr, cb, ud, st, lst);
+}
+
+/* ---- hapdiv: the end-to-end DP of sliding windows (rb3gpu_hapdiv.h) ----------------------------- */
+
+#define RB3_HD_SLICE ((int64_t)1 << 16)       // windows per launch
+#define RB3_HD_BLOCKS 2048                    // windows in flight at most: 8 single-wave blocks on each of 256 CUs (20 KB of LDS a block)
+
+struct HdHostWs {
+	std::vector<void*> dv;
+	int32_t *h_out = nullptr;
+	unsigned long long *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	~HdHostWs()
+	{
+		for (void *p : dv) if (p) (void)hipFree(p);
+		if (h_out) (void)hipHostFree(h_out);
+		if (h_ctr) (void)hipHostFree(h_ctr);
+		if (e0) (void)hipEventDestroy(e0);
+		if (e1) (void)hipEventDestroy(e1);
+	}
+};
+
+int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint8_t *symbols, int32_t k, const rb3gpu_hapdiv_opt_t *opt,
+		rb3gpu_hapdiv_cb cb, void *ud, rb3gpu_hapdiv_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || !opt || !cb || k < 1 || opt->n_best < 1 || n_win < 0 || (n_win > 0 && (!win_off || !symbols))) return RB3GPU_EINVAL;
+	// a cell of the backtrack matrix is named by row * n_best + column in 32 bits, and its F column has 24
+	if (opt->n_best >= (1 << 24) || ((int64_t)k + 1) * opt->n_best >= 0xFFFFFFFFLL) return RB3GPU_EINVAL;
+	int64_t total = 0;
+	for (int64_t i = 0; i < n_win; ++i) {
+		if (win_off[i] < 0) return RB3GPU_EINVAL;
+		total = std::max(total, win_off[i] + k);
+	}
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE; // both strands, as rb3gpu_mem
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	if (n_win == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
+	const int64_t N = opt->n_best;
+	const int64_t slice = std::min(n_win, h->tn.hapdiv_slice > 0 ? h->tn.hapdiv_slice : RB3_HD_SLICE);
+	const int lds_slots = h->tn.hapdiv_table > 0 ? (int)h->tn.hapdiv_table : HD_LDS_SLOTS;
+	int64_t cap0 = 4;
+	while (cap0 < 4 * N) cap0 *= 2;
+	HdWs ws;
+	memset(&ws, 0, sizeof(ws));
+	ws.bt_stride = ((int64_t)k + 1) * N * 3;
+	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
+	ws.stack_cap = 16 * N + 64;
+	ws.fpar_cap = 32 * N + 64;
+	const size_t per_block = (size_t)ws.bt_stride * 4 + (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(HdZ)
+		+ (size_t)ws.fpar_cap * 16 + 256;
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
+	const size_t fixed = (size_t)total + (size_t)n_win * 8 + (size_t)slice * 36 + ((size_t)64 << 20);
+	if (fr / 2 < fixed + per_block) return RB3GPU_ENOMEM;
+	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr / 2 - fixed) / per_block)); // the windows in flight: by the free memory
+	HdHostWs hw;
+	auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes + 64); if (e == hipSuccess) hw.dv.push_back(*p); return e; };
+	uint8_t *d_sym = nullptr;
+	int64_t *d_off = nullptr;
+	int32_t *d_out = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	HIPCHK(dalloc((void**)&d_sym, (size_t)total));
+	HIPCHK(dalloc((void**)&d_off, (size_t)n_win * 8));
+	HIPCHK(dalloc((void**)&d_out, (size_t)slice * 36));
+	HIPCHK(dalloc((void**)&d_ctr, 64));
+	HIPCHK(dalloc((void**)&ws.bt, (size_t)nb * ws.bt_stride * 4));
+	HIPCHK(dalloc((void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
+	HIPCHK(dalloc((void**)&ws.heap, (size_t)nb * N * 4));
+	HIPCHK(dalloc((void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ)));
+	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
+	HIPCHK(hipHostMalloc((void**)&hw.h_out, (size_t)slice * 36, hipHostMallocDefault));
+	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
+	HIPCHK(hipEventCreate(&hw.e0));
+	HIPCHK(hipEventCreate(&hw.e1));
+	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_off, win_off, (size_t)n_win * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+	const IdxView ix = view_of(h);
+	Acc7 acc;
+	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	HdOpt o;
+	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = opt->e2e_drop, o.k = k;
+	double ms_dp = 0;
+	int64_t n_slices = 0;
+	int ret = 0;
+	for (int64_t w0 = 0; w0 < n_win && ret == 0; ++n_slices) {
+		const int64_t w1 = std::min(n_win, w0 + slice);
+		HIPCHK(hipEventRecord(hw.e0, h->st));
+		hipLaunchKernelGGL(k_hapdiv, dim3((unsigned)std::min(nb, w1 - w0)), dim3(64), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_off, w0, w1, o, ws, lds_slots, d_out, d_ctr);
+		HIPCHK(hipEventRecord(hw.e1, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_out, d_out, (size_t)(w1 - w0) * 36, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_dp += ev_ms(hw.e0, hw.e1);
+		if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a window could not be represented: no record of this slice goes out
+		ret = cb(ud, w0, w1 - w0, (const rb3gpu_hapdiv_rec_t*)hw.h_out);
+		w0 = w1;
+	}
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->n_ext = (int64_t)hw.h_ctr[0], st->n_windows = n_win, st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
+	return ret;
 }
 
 } // extern "C"

@@ -64,6 +64,20 @@ class MemStats(ctypes.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+HAPDIV_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
+
+
+class HapdivOpt(ctypes.Structure):
+    _fields_ = [("n_best", ctypes.c_int32), ("min_sc", ctypes.c_int32), ("match", ctypes.c_int32), ("mis", ctypes.c_int32), ("gap_open", ctypes.c_int32),
+                ("gap_ext", ctypes.c_int32), ("e2e_drop", ctypes.c_int32)]
+
+
+class HapdivStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_dp", ctypes.c_double), ("n_ext", ctypes.c_int64), ("n_windows", ctypes.c_int64), ("n_tier2", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
 POS = np.dtype([("sid", "<i8"), ("pos", "<i8")])  # rb3gpu_pos_t
 LOCATE_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p)
 MEM_POS_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p)
@@ -188,6 +202,8 @@ SYMBOLS = {
     "rb3gpu_locate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, LOCATE_F, ctypes.c_void_p, ctypes.POINTER(LocateStats)]),
     "rb3gpu_mem_pos": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_POS_F, ctypes.c_void_p,
                                       ctypes.POINTER(MemStats), ctypes.POINTER(LocateStats)]),
+    "rb3gpu_hapdiv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(HapdivOpt), HAPDIV_F, ctypes.c_void_p,
+                                     ctypes.POINTER(HapdivStats)]),
     "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
 }
 
@@ -789,6 +805,33 @@ class Rb3Gpu:
             stats.update(st.as_dict())
         return np.concatenate(got) if got else np.zeros(0, dtype=MEM_REC)
 
+    def hapdiv(self, queries, k=101, w=50, n_best=25, min_sc=30, match=1, mis=3, gap_open=5, gap_ext=2, e2e_drop=-1, stats=None):
+        """rb3gpu_hapdiv on the windows of the queries (k symbols every w, as the reference's `hapdiv` cuts them; queries as for mem): an (n, 9) int32
+        array, a row of n_al, max_ed, n_hap[0..6] per window in query order, and -- second value -- the (query, offset) of every window as an (n, 2)
+        int64 array.  stats: a dict that receives rb3gpu_hapdiv_stats_t"""
+        if k < 1 or w < 1:
+            raise ValueError("k and w must be at least 1")
+        qs = [nt6_of(q) for q in queries]
+        off = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            off[1:] = np.cumsum([q.size for q in qs])
+        sym = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        where = [(i, x) for i, q in enumerate(qs) for x in range(0, q.size - k + 1, w)]
+        where = np.array(where, dtype=np.int64).reshape(-1, 2)
+        win = np.ascontiguousarray(off[where[:, 0]] + where[:, 1], dtype=np.int64)
+        out = np.zeros((win.size, 9), dtype=np.int32)
+
+        def cb(_ud, i0, n, recs):
+            out[i0:i0 + n] = np.frombuffer(ctypes.string_at(recs, n * 36), dtype=np.int32).reshape(n, 9)
+            return 0
+        st = HapdivStats()
+        opt = HapdivOpt(int(n_best), int(min_sc), int(match), int(mis), int(gap_open), int(gap_ext), int(e2e_drop))
+        self._chk(self._lib.rb3gpu_hapdiv(self._h, win.size, win.ctypes.data if win.size else None, sym.ctypes.data if sym.size else None, int(k), ctypes.byref(opt),
+                                          HAPDIV_F(cb), None, ctypes.byref(st)), "rb3gpu_hapdiv")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return out, where
+
     def sync(self):
         self._chk(self._lib.rb3gpu_sync(self._h), "rb3gpu_sync")
 
@@ -1091,4 +1134,21 @@ def mem_lines(recs, names=None, first_id=0, positions=None, seq_names=None, leng
         if isinstance(nm, str):
             nm = nm.encode()
         out.append(b"%s\t%d\t%d\t%d\n" % (nm, r["st"], r["en"], r["size"]))
+    return b"".join(out)
+
+
+def hapdiv_lines(recs, where, k, names=None, first_id=0):
+    """the reference's `hapdiv` output for the windows of Rb3Gpu.hapdiv (recs, where as it returns them): consecutive windows of one query with the
+    same nine numbers make one line -- name, first offset, last offset + k, n_al, max_ed, n_hap[0..6] (bytes); names as for mem_lines"""
+    out, i, n = [], 0, len(recs)
+    while i < n:
+        j = i + 1
+        while j < n and where[j][0] == where[i][0] and np.array_equal(recs[j], recs[i]):
+            j += 1
+        q = int(where[i][0])
+        nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
+        if isinstance(nm, str):
+            nm = nm.encode()
+        out.append(nm + b"\t%d\t%d" % (int(where[i][1]), int(where[j - 1][1]) + k) + b"".join(b"\t%d" % int(x) for x in recs[i]) + b"\n")
+        i = j
     return b"".join(out)
