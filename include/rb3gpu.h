@@ -546,6 +546,32 @@ typedef struct { double ms_total, ms_dp; int64_t n_ext, n_windows, n_tier2, n_sl
 int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint8_t *symbols, int32_t k, const rb3gpu_hapdiv_opt_t *opt,
 		rb3gpu_hapdiv_cb cb, void *ud, rb3gpu_hapdiv_stats_t *st);
 
+/* end-to-end alignments of whole queries with their alignment and positions (`ropebwt3 sw -e`, `--all-e2e`, `-g`: rb3_sw, bwa-sw.c:532-560 of the reference, in
+ * its end-to-end mode): query q = symbols[offsets[q], offsets[q + 1]) (nt6 codes) is aligned end to end against the index by the dynamic program of
+ * rb3gpu_hapdiv, but mismatches and gaps are allowed only once end_len symbols are aligned (-k; -e sets 1).  Its hits are the cells of the last row that
+ * no better one contains, that end in a match or mismatch, score at least min_sc and lie within e2e_drop (< 0: off) of the best, in the reference's
+ * order.  A hit: its interval [lo, hi), its score, the symbols of the query (qlen) and of the index (rlen) it spans, and its alignment, n_steps bytes
+ * from steps[step_off]: one byte per step from query position 0 on, (op << 4 | base) with op 0 `=`, 1 `X`, 2 `I`, 3 `D` and base 1..5 the symbol of the
+ * index at that step (an `I` carries the base of the cell it leaves; `=` is "the base is the query's symbol", so N against N is `=`).  cigar, cs, rs,
+ * matching and block length are functions of the bytes.  max_pos >= 0: positions through the sampled suffix array of the handle (rb3gpu_ssa_set /
+ * rb3gpu_ssa_keep), as rb3_sw asks for them: hit k of a query gets n_pos = min(rest > 0 ? rest : 1, hi - lo) pairs from pos[pos_off], rest = max_pos at
+ * the first hit and less n_pos after each -- so max_pos 0 is one position per hit.  The intervals go from the alignment step to the locate step on
+ * the device; every hit is located at the largest cap a hit can have, max(max_pos, 1), and cut: the traversal's pairs at a smaller cap are a prefix of
+ * those at a larger.  max_pos < 0: no positions (--no-ssa).  cb gets the queries slice by slice in query order (host memory valid during the call only):
+ * the nq queries from q0 on, n_hit[i] hits of query q0 + i, their records one after another in hits[].  A nonzero return stops the call and is returned.
+ * A slice is at most rb3gpu_tune "sw_slice" queries (default 16 K), fewer where its backtrack matrices, 12 bytes per cell of (len + 1) * n_best for
+ * every query of the slice, would not fit; "sw_table" as "hapdiv_table".  A query of length 0 has no hits.  RB3GPU_EINVAL for n_best < 1, end_len < 1,
+ * (len + 1) * n_best of 2^32 or more for any query, or a NULL callback; RB3GPU_ESTATE without an index, with one that does not hold both strands, or
+ * when positions are asked for without a sampled suffix array; RB3GPU_EINTERNAL if a query cannot be represented (as rb3gpu_hapdiv) -- never a wrong
+ * record.  st (may be NULL): ms_total wall time, ms_dp the rows and the counting walk, ms_backtrack the writing walk (HIP events), n_ext extensions,
+ * n_hits, n_steps, n_tier2 queries whose table went to global memory, n_slices; lst (may be NULL): the locate step */
+typedef struct { int32_t n_best, min_sc, match, mis, gap_open, gap_ext, e2e_drop, end_len; int64_t max_pos; } rb3gpu_sw_opt_t;
+typedef struct { int64_t lo, hi; int32_t score, qlen, rlen, n_steps; int64_t step_off, pos_off, n_pos; } rb3gpu_sw_hit_t;
+typedef int (*rb3gpu_sw_cb)(void *ud, int64_t q0, int64_t nq, const int32_t *n_hit, const rb3gpu_sw_hit_t *hits, const uint8_t *steps, const rb3gpu_pos_t *pos);
+typedef struct { double ms_total, ms_dp, ms_backtrack; int64_t n_ext, n_hits, n_steps, n_tier2, n_slices; } rb3gpu_sw_stats_t;
+int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud,
+		rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -563,6 +589,7 @@ int rb3gpu_stream_sync(void *stream);
  *   of fewer than N symbols carry the LF base in their slot headers; at most 2^32, only before an index exists: RB3GPU_ESTATE after);
  *   "mem_slice" N (query symbols per output slice of rb3gpu_mem; 0 = 8 M);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
+ *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e; 0 = 16 K), "sw_table" N (as "hapdiv_table", for rb3gpu_sw_e2e);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c
  * Test hooks "force_fallback", "tent_limit", "text_mode" exist only in the test build of the library (compiled with

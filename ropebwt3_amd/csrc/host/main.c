@@ -1849,6 +1849,260 @@ static int main_hapdiv(int argc, char *argv[])
 	return ret;
 }
 
+/* sw: the end-to-end alignments of every query (the reference's main_search for `sw` with -e, --all-e2e or -g, search.c:443-582) through rb3gpu_sw_e2e, batch by
+ * batch; the PAF of write_paf or the blocks of write_all_hits (swfmt.c).  <index>.ssa and <index>.len.gz are loaded when they are there and belong to the index
+ * (rb3_fmi_load_all, fm-index.c:606-640) unless --no-ssa, --all-e2e or -g says otherwise; with the first a hit gets positions, with the second they get names.
+ * Differences, each a refusal with exit status 1 and nothing on stdout: the local mode (no -e), -j above the end length (the reference's MEM pre-filter),
+ * -N or -k below 1, and the options of `mem` and `hapdiv`. */
+typedef struct {
+	int32_t *n_hit; int64_t m_q;
+	rb3h_sw_hit_t *hits; int64_t n_hits, m_hits;
+	uint8_t *steps; int64_t n_steps, m_steps;
+	rb3h_pos_t *pos; int64_t n_pos, m_pos;
+	int err;
+} sw_out_t;
+
+static int sw_sink(void *ud, int64_t q0, int64_t nq, const int32_t *n_hit, const rb3gpu_sw_hit_t *hits, const uint8_t *steps, const rb3gpu_pos_t *pos)
+{
+	sw_out_t *o = (sw_out_t*)ud;
+	int64_t i, nh = 0, ns = 0, np = 0;
+	if (q0 < 0 || q0 + nq > o->m_q) return o->err = 2, -1;
+	for (i = 0; i < nq; ++i) o->n_hit[q0 + i] = n_hit[i], nh += n_hit[i];
+	for (i = 0; i < nh; ++i) {
+		if (hits[i].step_off + hits[i].n_steps > ns) ns = hits[i].step_off + hits[i].n_steps;
+		if (hits[i].n_pos > 0 && hits[i].pos_off + hits[i].n_pos > np) np = hits[i].pos_off + hits[i].n_pos;
+	}
+	if (o->hits == 0 || o->n_hits + nh > o->m_hits) {
+		o->m_hits = (o->n_hits + nh) * 2 + 256;
+		o->hits = (rb3h_sw_hit_t*)realloc(o->hits, (size_t)o->m_hits * sizeof(*o->hits));
+	}
+	if (o->steps == 0 || o->n_steps + ns > o->m_steps) o->m_steps = (o->n_steps + ns) * 2 + 4096, o->steps = (uint8_t*)realloc(o->steps, (size_t)o->m_steps);
+	if (o->pos == 0 || o->n_pos + np > o->m_pos) o->m_pos = (o->n_pos + np) * 2 + 256, o->pos = (rb3h_pos_t*)realloc(o->pos, (size_t)o->m_pos * sizeof(*o->pos));
+	if (o->hits == 0 || o->steps == 0 || o->pos == 0) return o->err = 1, -1;
+	if (ns > 0) memcpy(o->steps + o->n_steps, steps, (size_t)ns);
+	if (np > 0) memcpy(o->pos + o->n_pos, pos, (size_t)np * sizeof(*pos));
+	for (i = 0; i < nh; ++i) {
+		rb3h_sw_hit_t *d = o->hits + o->n_hits + i;
+		memcpy(d, hits + i, sizeof(*d));
+		d->step_off += o->n_steps, d->pos_off += o->n_pos;
+	}
+	o->n_hits += nh, o->n_steps += ns, o->n_pos += np;
+	return 0;
+}
+
+static const struct option sw_long_opts[] = {
+	{ "gap", required_argument, 0, 403 },
+	{ "cov", no_argument, 0, 403 },
+	{ "old-mem", no_argument, 0, 403 },
+	{ "no-ssa", no_argument, 0, 401 },
+	{ "seq", no_argument, 0, 402 },
+	{ "all-e2e", no_argument, 0, 406 },
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_sw(int argc, char *argv[])
+{
+	int c, is_line = 0, device = 0, ret = 0, j, e2e = 0, no_ssa = 0, write_all = 0, both = 0, unmapped = 0, with_rs = 0, max_pos = 0, min_mem_len = 0;
+	int64_t batch_size = 100000000, id = 0, max_all_out = 0, n_ext = 0, n_hits = 0, n_tier2 = 0, n_slices = 0, n_batches = 0;
+	double ms_dp = 0, ms_bt = 0, ms_engine = 0, ms_locate = 0;
+	rb3gpu_sw_opt_t so = { 25, 30, 1, 3, 5, 2, -1, 11, 0 };
+	rb3gpu_t *h;
+	rb3gpu_opt_t gopt;
+	rb3h_ssa_t *sa = 0;
+	rb3h_sid_t *sid = 0;
+	int have_ssa = 0;
+	int64_t acc[7];
+	rb3h_buf_t sym = {0, 0, 0}, rev = {0, 0, 0}, names = {0, 0, 0}, out = {0, 0, 0};
+	int64_t *off = 0, *name_off = 0, m_q = 0;
+	sw_out_t o[2];
+	_Static_assert(sizeof(rb3h_sw_hit_t) == sizeof(rb3gpu_sw_hit_t), "one hit layout on both sides");
+	_Static_assert(sizeof(rb3h_pos_t) == sizeof(rb3gpu_pos_t), "one position layout on both sides");
+	memset(o, 0, sizeof(o));
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", sw_long_opts, 0)) >= 0) { /* the order of -e, -k, -g matters as in search.c:452-492 */
+		if (c == 'L') is_line = 1;
+		else if (c == 'g') max_all_out = atol(optarg), write_all = 1, e2e = 1, so.end_len = 1, no_ssa = 1;
+		else if (c == 406) write_all = 1, e2e = 1, so.end_len = 1, no_ssa = 1;
+		else if (c == 'e') e2e = 1, so.end_len = 1;
+		else if (c == 'k') so.end_len = atoi(optarg);
+		else if (c == 'j') min_mem_len = atoi(optarg);
+		else if (c == 'N') so.n_best = atoi(optarg);
+		else if (c == 'm') so.min_sc = atoi(optarg);
+		else if (c == 'A') so.match = atoi(optarg);
+		else if (c == 'B') so.mis = atoi(optarg);
+		else if (c == 'O') so.gap_open = atoi(optarg);
+		else if (c == 'E') so.gap_ext = atoi(optarg);
+		else if (c == 'y') so.e2e_drop = atoi(optarg);
+		else if (c == 'p') max_pos = atoi(optarg);
+		else if (c == 'K') batch_size = rb3h_parse_num(optarg);
+		else if (c == 'u') unmapped = 1;
+		else if (c == 'b') both = 1;
+		else if (c == 401) no_ssa = 1;
+		else if (c == 402) with_rs = 1;
+		else if (c == 't' || c == 'C' || c == 'M') {} /* threads, the rank cache, the mmap loader: nothing to size here, and none changes an answer */
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+		else if (c == '?') return 1;
+		else { fprintf(stderr, "ERROR: option not supported by sw (it belongs to mem or hapdiv)\n"); return 1; }
+	}
+	if (argc - optind < 2) {
+		fprintf(stdout, "Usage: ropebwt3-amd sw [options] <idx.fmr> <seq.fa> [...]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -e          end-to-end mode (forcing -k to 1); required: the local mode is not implemented\n");
+		fprintf(stderr, "  -N INT      keep up to INT hits per row [%d]\n", so.n_best);
+		fprintf(stderr, "  -m INT      min alignment score [%d]\n", so.min_sc);
+		fprintf(stderr, "  -A INT      match score [%d]\n", so.match);
+		fprintf(stderr, "  -B INT      mismatch penalty [%d]\n", so.mis);
+		fprintf(stderr, "  -O INT      gap open penalty [%d]\n", so.gap_open);
+		fprintf(stderr, "  -E INT      gap extension penalty; a k-long gap costs O+k*E [%d]\n", so.gap_ext);
+		fprintf(stderr, "  -y INT      ignore secondary hits scored INT lower than the best [%d]\n", so.e2e_drop);
+		fprintf(stderr, "  -k INT      require INT-mer match at the end of alignment [%d]\n", so.end_len);
+		fprintf(stderr, "  -b          align both strands (effective with --all-e2e)\n");
+		fprintf(stderr, "  -u          write unmapped queries to PAF\n");
+		fprintf(stderr, "  --seq       write reference sequence to the rs tag\n");
+		fprintf(stderr, "  --all-e2e   write all end-to-end hits in a compact format (forcing -e)\n");
+		fprintf(stderr, "  -g INT      cap the number of --all-e2e output to INT (forcing --all-e2e)\n");
+		fprintf(stderr, "  --no-ssa    ignore the sampled suffix array\n");
+		fprintf(stderr, "  -p INT      output up to INT positions [%d]\n", max_pos);
+		fprintf(stderr, "  -L          one sequence per line in the input\n");
+		fprintf(stderr, "  -K NUM      query batch size [100m]\n");
+		return 0;
+	}
+	if (!e2e) { fprintf(stderr, "ERROR: local mode is not implemented: use -e\n"); return 1; }
+	if (so.n_best < 1) { fprintf(stderr, "ERROR: the number of hits kept per row (-N) must be at least 1\n"); return 1; }
+	if (so.end_len < 1) { fprintf(stderr, "ERROR: the end length (-k) must be at least 1\n"); return 1; }
+	if (so.n_best >= (1 << 24)) { fprintf(stderr, "ERROR: -N is too large\n"); return 1; }
+	if (min_mem_len > 0 && min_mem_len > so.end_len) { fprintf(stderr, "ERROR: -j above the end length asks for the MEM pre-filter, which is not implemented\n"); return 1; }
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	h = rb3gpu_create(&gopt);
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
+	if (load_index(h, argv[optind]) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	rb3gpu_get_acc(h, acc);
+	if (!no_ssa) { /* the two files beside the index, each only if it is there and belongs to this index */
+		const size_t l = strlen(argv[optind]);
+		char *fn = (char*)malloc(l + 8);
+		if (fn) {
+			memcpy(fn, argv[optind], l);
+			strcpy(fn + l, ".ssa"), sa = rb3h_ssa_read(fn);
+			strcpy(fn + l, ".len.gz"), sid = rb3h_sid_read(fn);
+			free(fn);
+		}
+		if (sa && (sa->m != acc[1] || rb3gpu_ssa_set(h, sa->ss, sa->ms, sa->m, sa->n_ssa, sa->r2i, sa->ssa) != 0)) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: number of sequences do not match between BWT and sampled suffix array\n");
+		} else if (sa) have_ssa = 1;
+		rb3h_ssa_destroy(sa), sa = 0; /* (it lives on the device from here on) */
+		if (sid && sid->n_seq * 2 != acc[1]) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: number of sequences do not match between BWT and the sequence list\n");
+			rb3h_sid_destroy(sid), sid = 0;
+		}
+	}
+	if (max_pos > 0 && (!have_ssa || sid == 0)) { /* search.c:555-559 */
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load suffix array samples or sequence names/lengths\n");
+		rb3gpu_destroy(h);
+		rb3h_sid_destroy(sid);
+		return 1;
+	}
+	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+		rb3gpu_destroy(h);
+		rb3h_sid_destroy(sid);
+		return 1;
+	}
+	so.max_pos = have_ssa ? max_pos : -1;
+	if (write_all) fputs("CC\tQS  queryName  queryLen  numHap\nCC\tQH  refCount   score     editDist   cs   strand   nOut   totAln\nCC\n", stdout);
+	for (j = optind + 1; j < argc && ret == 0; ++j) {
+		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
+		int eof = 0;
+		if (fp == 0) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
+			break; /* (the reference stops here and exits 0, search.c:570-576) */
+		}
+		while (!eof && ret == 0) { /* a batch: whole records until their symbols reach -K (search.c:366-378) */
+			int64_t n_q = 0, l, q, at[2] = { 0, 0 };
+			const uint8_t *s;
+			const char *name;
+			int pass;
+			sym.l = names.l = 0;
+			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
+				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
+				if (n_q + 2 > m_q) {
+					m_q = m_q ? m_q * 2 : 1024;
+					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
+					o[0].n_hit = (int32_t*)realloc(o[0].n_hit, (size_t)m_q * 4), o[1].n_hit = (int32_t*)realloc(o[1].n_hit, (size_t)m_q * 4);
+				}
+				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
+				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
+				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0 || o[0].n_hit == 0 || o[1].n_hit == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+				if (l > 0x7ffffffeLL || (l + 1) * (int64_t)so.n_best >= 0xFFFFFFFFLL) { fprintf(stderr, "ERROR: a query times -N is too large\n"); ret = 1; break; }
+				if (n_q == 0) off[0] = 0;
+				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
+				rb3h_char2nt6(l, sym.s + sym.l); /* search.c:91 */
+				sym.l += l, off[++n_q] = sym.l;
+				name_off[n_q - 1] = name ? names.l : -1;
+				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
+				if (sym.l >= batch_size || n_q >= 0x7fffffffLL) break;
+			}
+			if (l < 0) eof = 1;
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q == 0 || ret != 0) continue;
+			for (pass = 0; pass < (write_all && both ? 2 : 1) && ret == 0; ++pass) { /* the second pass: every query reverse-complemented in place (search.c:94-98) */
+				rb3gpu_sw_stats_t st;
+				rb3gpu_locate_stats_t ls;
+				const uint8_t *codes = sym.s;
+				int r;
+				if (pass == 1) {
+					if (rev.m < sym.l + 1) rev.m = sym.l + 1, rev.s = (uint8_t*)realloc(rev.s, (size_t)rev.m);
+					if (rev.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+					memcpy(rev.s, sym.s, (size_t)sym.l);
+					for (q = 0; q < n_q; ++q) rb3h_revcomp6(off[q + 1] - off[q], rev.s + off[q]);
+					codes = rev.s;
+				}
+				o[pass].m_q = n_q, o[pass].n_hits = o[pass].n_steps = o[pass].n_pos = 0, o[pass].err = 0;
+				r = rb3gpu_sw_e2e(h, n_q, off, codes, &so, sw_sink, &o[pass], &st, &ls);
+				if (r != 0 && o[pass].err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+				else if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to align the queries: %s\n", rb3gpu_strerror(r)); ret = 1; }
+				n_ext += st.n_ext, n_hits += st.n_hits, n_tier2 += st.n_tier2, n_slices += st.n_slices, ms_dp += st.ms_dp, ms_bt += st.ms_backtrack, ms_engine += st.ms_total, ms_locate += ls.ms_locate;
+			}
+			for (q = 0; q < n_q && ret == 0; ++q) {
+				const char *nm = name_off[q] >= 0 ? (const char*)names.s + name_off[q] : 0;
+				const int64_t len = off[q + 1] - off[q];
+				int r;
+				if (write_all) {
+					r = rb3h_sw_format_all(&out, nm, id + q, len, sym.s + off[q], o[0].n_hit[q], o[0].hits + at[0], o[0].steps, '+', max_all_out);
+					if (r == 0 && both) r = rb3h_sw_format_all(&out, nm, id + q, len, rev.s + off[q], o[1].n_hit[q], o[1].hits + at[1], o[1].steps, '-', max_all_out), at[1] += o[1].n_hit[q];
+				} else r = rb3h_sw_format_paf(&out, nm, id + q, len, sym.s + off[q], o[0].n_hit[q], o[0].hits + at[0], o[0].steps, o[0].pos, sid, unmapped, with_rs);
+				at[0] += o[0].n_hit[q];
+				if (r == -2) { fprintf(stderr, "ERROR: a position names a sequence that the name list does not have\n"); ret = 1; break; }
+				if (r < 0) ret = 1;
+				if (out.l > (1 << 20) || q == n_q - 1) {
+					if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) ret = 1;
+					out.l = 0;
+				}
+				if (ret) fprintf(stderr, "ERROR: failed to write the output\n");
+			}
+			id += n_q, ++n_batches;
+			if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] processed %lld sequences\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_q);
+		}
+		rb3h_seq_close(fp);
+	}
+	if (fflush(stdout) != 0 && ret == 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (rb3h_verbose >= 3 && ret == 0)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld hits in %lld slice(s), %lld extensions, %lld queries with a table in global memory; %.3f ms in the engine, the DP kernel %.3f ms, the backtrack %.3f ms, the locate kernels %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_hits, (long long)n_slices, (long long)n_ext, (long long)n_tier2, ms_engine, ms_dp, ms_bt, ms_locate);
+	for (j = 0; j < 2; ++j) { free(o[j].n_hit); free(o[j].hits); free(o[j].steps); free(o[j].pos); }
+	free(out.s); free(sym.s); free(rev.s); free(names.s); free(off); free(name_off);
+	rb3gpu_destroy(h);
+	rb3h_sid_destroy(sid);
+	return ret;
+}
+
 /* recode: decode an FMD/FMR file on the host and write it back as plain text (default), FMD (-d)
  * or FMR (-b).  Host-only utility; also the CPU-side test bench of the two codecs. */
 typedef struct { int64_t cnt[6]; runvec_t rv; } recode_t;
@@ -1950,6 +2204,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    kount      count k-mers in one or more FM-indexes (on an MI355X)\n");
 	fprintf(fp, "    mem        find super-maximal exact matches of queries (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
+	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
 	fprintf(fp, "    plain2fmd  convert BWT in plain text to FMD (host only)\n");
 	fprintf(fp, "    version    print the version number\n");
@@ -1968,6 +2223,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "kount") == 0) ret = main_kount(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "mem") == 0) ret = main_mem(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "plain2fmd") == 0) ret = main_plain2fmd(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "version") == 0) { printf("%s\n", RB3H_VERSION); return 0; }

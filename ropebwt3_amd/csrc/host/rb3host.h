@@ -81,7 +81,18 @@ int rb3h_mem_format_pos(rb3h_buf_t *out, const char *name, int64_t id, int64_t n
  * window (n_al, max_ed, n_hap[0..6]); consecutive windows with the same nine make one line: name, first start, last end, the nine */
 int rb3h_hapdiv_format(rb3h_buf_t *out, const char *name, int64_t id, int64_t k, int64_t w, int64_t n, const int32_t *r);
 
-/* ---- the files beside an index that `mem -p` reads (sidefile.c) ---- */
+/* ---- the output of `sw` in end-to-end mode (swfmt.c) ---- */
+typedef struct { int64_t lo, hi; int32_t score, qlen, rlen, n_steps; int64_t step_off, pos_off, n_pos; } rb3h_sw_hit_t; /* = rb3gpu_sw_hit_t */
+/* the PAF lines of ONE query (write_paf, search.c:175-216): its n hits with their step bytes (one per step from query position 0 on, op << 4 | base with op
+ * 0 = 1 X 2 I 3 D) and positions (hit i: pos[pos_off, pos_off + n_pos)); seq: its nt6 codes.  sid NULL: positions as string number and offset.  unmapped: the -u
+ * line of a query without a hit; with_rs: the rs tag of --seq.  0, -1 (no memory) or -2 (a position names a string the name list does not have) */
+int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
+		const rb3h_pos_t *pos, const rb3h_sid_t *sid, int unmapped, int with_rs);
+/* the QS / QH / // block of ONE query and strand (write_all_hits, search.c:218-238); seq: the codes that were aligned; max_out <= 0: no cap */
+int rb3h_sw_format_all(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
+		char strand, int64_t max_out);
+
+/* ---- the files beside an index that `mem -p` and `sw` read (sidefile.c) ---- */
 typedef struct { int32_t ss, ms; int64_t m, n_ssa; uint64_t *r2i, *ssa; } rb3h_ssa_t;
 rb3h_ssa_t *rb3h_ssa_read(const char *fn);                                 /* rb3_ssa_restore, ssa.c:215-241; NULL: no file, wrong magic, or it ends early */
 void rb3h_ssa_destroy(rb3h_ssa_t *sa);

@@ -27,6 +27,7 @@
 #include "rb3gpu_kount.h"
 #include "rb3gpu_mem.h"
 #include "rb3gpu_hapdiv.h"
+#include "rb3gpu_sw.h"
 #include "rb3gpu_locate.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -152,6 +153,8 @@ struct Tune {
 	int64_t mem_slice = 0;   // rb3gpu_mem: query symbols whose matches one output slice holds (0: 8 M; a slice always takes at least one walker)
 	int64_t hapdiv_slice = 0;// rb3gpu_hapdiv: windows per launch and per piece of records handed to the callback (0: 64 K)
 	int64_t hapdiv_table = 0;// rb3gpu_hapdiv: slots of a window's candidate table in LDS (0: 256, at most 256); a table that needs more lies in global memory
+	int64_t sw_slice = 0;    // rb3gpu_sw_e2e: queries per launch and per piece handed to the callback (0: 16 K; fewer where the backtrack matrices of a slice would not fit)
+	int64_t sw_table = 0;    // rb3gpu_sw_e2e: slots of a query's candidate table in LDS (0: 256, at most 256), as hapdiv_table
 	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
 	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
@@ -667,6 +670,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "mem_slice")) t.mem_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "hapdiv_slice")) t.hapdiv_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "hapdiv_table")) t.hapdiv_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
+	else if (!strcmp(key, "sw_slice")) t.sw_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "sw_table")) t.sw_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
 	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
 	else if (!strcmp(key, "locate_slice")) t.locate_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sh_host_rounds")) t.sh_host_rounds = v < 0 ? -1 : v != 0; // (-1: rounds on the device whatever the number of chains)
@@ -706,7 +711,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -4985,6 +4990,240 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 		w0 = w1;
 	}
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->n_ext = (int64_t)hw.h_ctr[0], st->n_windows = n_win, st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
+	return ret;
+}
+
+/* ---- sw: end-to-end alignments of whole queries with their alignment and positions (rb3gpu_sw.h) -- */
+
+#define RB3_SW_SLICE ((int64_t)1 << 14)       // queries per launch
+#define RB3_SW_SLOTS ((int64_t)1 << 22)       // columns of a slice (n_best per query; 52 bytes of device memory each)
+#define RB3_SW_BT_BYTES ((int64_t)4 << 30)    // backtrack matrices of a slice at most (less where the free memory says so; one query may need what it needs)
+
+struct SwHostWs {
+	std::vector<void*> dv;
+	SwRaw *d_hits = nullptr, *h_hits = nullptr;
+	uint8_t *d_steps = nullptr, *h_steps = nullptr;
+	int64_t hit_cap = 0, step_cap = 0;
+	int32_t *h_nhit = nullptr;
+	unsigned long long *h_ctr = nullptr;
+	int64_t *h_tot = nullptr;
+	hipEvent_t e[4] = { nullptr, nullptr, nullptr, nullptr };
+	~SwHostWs()
+	{
+		for (void *p : dv) if (p) (void)hipFree(p);
+		if (d_hits) (void)hipFree(d_hits);
+		if (d_steps) (void)hipFree(d_steps);
+		void *hv[] = { h_hits, h_steps, h_nhit, h_ctr, h_tot };
+		for (void *p : hv) if (p) (void)hipHostFree(p);
+		for (auto x : e) if (x) (void)hipEventDestroy(x);
+	}
+};
+
+int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud,
+		rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst)
+{
+	static_assert(sizeof(SwRaw) == 40, "the locate step reads (lo, hi) with a stride of five words");
+	if (st) memset(st, 0, sizeof(*st));
+	if (lst) memset(lst, 0, sizeof(*lst));
+	if (!h || !opt || !cb || opt->n_best < 1 || opt->end_len < 1 || n_query < 0 || n_query > 0x7fffffffLL || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
+	if (opt->n_best >= (1 << 24)) return RB3GPU_EINVAL; // (the F column of a cell has 24 bits)
+	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
+	const int64_t N = opt->n_best;
+	for (int64_t q = 0; q < n_query; ++q) {
+		const int64_t l = offsets[q + 1] - offsets[q];
+		if (l < 0 || l > 0x7ffffffeLL || (l + 1) * N >= 0xFFFFFFFFLL) return RB3GPU_EINVAL; // a cell of the backtrack matrix is named by row * n_best + column in 32 bits
+	}
+	const int64_t total = n_query > 0 ? offsets[n_query] : 0;
+	if (total > 0 && !symbols) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE; // both strands, as rb3gpu_mem
+	const bool with_pos = opt->max_pos >= 0;
+	if (with_pos && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
+	const int64_t loc_cap = std::max<int64_t>(1, opt->max_pos); // every hit is located at the largest cap one can have (rb3_sw: rest > 0 ? rest : 1) and cut to its own
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	if (n_query == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
+	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
+	int64_t cap0 = 4;
+	while (cap0 < 4 * N) cap0 *= 2;
+	HdWs ws;
+	memset(&ws, 0, sizeof(ws));
+	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
+	ws.stack_cap = 16 * N + 64;
+	ws.fpar_cap = 32 * N + 64;
+	const size_t per_block = (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(HdZ) + (size_t)ws.fpar_cap * 16 + 256;
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
+	// the slices: at most sw_slice queries, RB3_SW_SLOTS columns and bt_budget bytes of matrices, but one query at least; bt_off[q]: the first cell of query q in its slice
+	const int64_t max_q = std::max<int64_t>(1, std::min(h->tn.sw_slice > 0 ? h->tn.sw_slice : RB3_SW_SLICE, RB3_SW_SLOTS / N));
+	const int64_t bt_budget = std::max<int64_t>((int64_t)1 << 20, std::min<int64_t>(RB3_SW_BT_BYTES, (int64_t)(fr / 4))) / 12;
+	std::vector<int64_t> bt_off((size_t)n_query), cuts(1, 0);
+	int64_t max_cells = 0;
+	{
+		int64_t cells = 0;
+		for (int64_t q = 0; q < n_query; ++q) {
+			const int64_t c = (offsets[q + 1] - offsets[q] + 1) * N;
+			if (q > cuts.back() && (q - cuts.back() >= max_q || cells + c > bt_budget)) cuts.push_back(q), cells = 0;
+			bt_off[q] = cells, cells += c;
+			max_cells = std::max(max_cells, cells);
+		}
+		cuts.push_back(n_query);
+	}
+	int64_t slice = 0;
+	for (size_t i = 0; i + 1 < cuts.size(); ++i) slice = std::max(slice, cuts[i + 1] - cuts[i]);
+	const int64_t n_slot_cap = slice * N;
+	const size_t fixed = (size_t)total + (size_t)n_query * 16 + (size_t)max_cells * 12 + (size_t)n_slot_cap * 64 + ((size_t)64 << 20);
+	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
+	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
+	SwHostWs hw;
+	LocWs lws;
+	if (with_pos) {
+		const int r = loc_init(h, lws, std::min<int64_t>(n_slot_cap, RB3_LOC_SLICE_IV), false);
+		if (r < 0) return r;
+	}
+	auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes + 64); if (e == hipSuccess) hw.dv.push_back(*p); return e; };
+	uint8_t *d_sym = nullptr;
+	int64_t *d_off = nullptr, *d_btoff = nullptr, *d_hoff = nullptr, *d_soff = nullptr;
+	uint32_t *d_flag = nullptr, *d_cnt = nullptr;
+	SwRaw *d_raw = nullptr;
+	int32_t *d_nhit = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	void *d_tmp = nullptr;
+	size_t tmp_bytes = 0;
+	HIPCHK(dalloc((void**)&d_sym, (size_t)total));
+	HIPCHK(dalloc((void**)&d_off, (size_t)(n_query + 1) * 8));
+	HIPCHK(dalloc((void**)&d_btoff, (size_t)n_query * 8));
+	HIPCHK(dalloc((void**)&d_flag, (size_t)(n_slot_cap + 1) * 4));
+	HIPCHK(dalloc((void**)&d_cnt, (size_t)(n_slot_cap + 1) * 4));
+	HIPCHK(dalloc((void**)&d_hoff, (size_t)(n_slot_cap + 1) * 8));
+	HIPCHK(dalloc((void**)&d_soff, (size_t)(n_slot_cap + 1) * 8));
+	HIPCHK(dalloc((void**)&d_raw, (size_t)n_slot_cap * sizeof(SwRaw)));
+	HIPCHK(dalloc((void**)&d_nhit, (size_t)slice * 4));
+	HIPCHK(dalloc((void**)&d_ctr, 64));
+	HIPCHK(dalloc((void**)&ws.bt, (size_t)max_cells * 12));
+	HIPCHK(dalloc((void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
+	HIPCHK(dalloc((void**)&ws.heap, (size_t)nb * N * 4));
+	HIPCHK(dalloc((void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ)));
+	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
+	{
+		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, n_slot_cap + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
+	}
+	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 4, hipHostMallocDefault));
+	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
+	HIPCHK(hipHostMalloc((void**)&hw.h_tot, 64, hipHostMallocDefault));
+	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&hw.e[i]));
+	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_off, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_btoff, bt_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+	const IdxView ix = view_of(h);
+	Acc7 acc;
+	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	HdOpt o;
+	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = opt->e2e_drop, o.k = 0;
+	double ms_dp = 0, ms_bt = 0;
+	int64_t n_hits = 0, n_steps = 0, n_slices = 0;
+	std::vector<rb3gpu_sw_hit_t> hits;
+	std::vector<rb3gpu_pos_t> pairs;
+	int ret = 0;
+	for (size_t ci = 0; ci + 1 < cuts.size() && ret == 0; ++ci, ++n_slices) {
+		const int64_t q0 = cuts[ci], q1 = cuts[ci + 1], nq = q1 - q0, n_slot = nq * N;
+		HIPCHK(hipMemsetAsync(d_flag + n_slot, 0, 4, h->st)); // (the scans are exclusive: their last element is the total)
+		HIPCHK(hipMemsetAsync(d_cnt + n_slot, 0, 4, h->st));
+		HIPCHK(hipEventRecord(hw.e[0], h->st));
+		hipLaunchKernelGGL(k_sw_fill, dim3((unsigned)std::min(nb, nq)), dim3(64), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_off, (const int64_t*)d_btoff, q0, q1, o,
+				(int)std::min<int64_t>(opt->end_len, 0x7fffffff), ws, lds_slots, d_flag, d_cnt, d_raw, d_nhit, d_ctr);
+		HIPCHK(hipEventRecord(hw.e[1], h->st));
+		size_t tb = tmp_bytes + 256;
+		int r = rb3kount_scan(d_tmp, &tb, d_flag, d_hoff, n_slot + 1, h->st);
+		if (r == 0) tb = tmp_bytes + 256, r = rb3kount_scan(d_tmp, &tb, d_cnt, d_soff, n_slot + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(hipMemcpyAsync(hw.h_tot, d_hoff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, d_soff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_nhit, d_nhit, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_dp += ev_ms(hw.e[0], hw.e[1]);
+		if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a query could not be represented: no record of this slice goes out
+		const int64_t nh = hw.h_tot[0], ns = hw.h_tot[1];
+		if (nh < 0 || nh > n_slot || ns < 0) return RB3GPU_EINTERNAL;
+		hits.resize((size_t)nh);
+		pairs.clear();
+		if (nh > 0) {
+			if (nh > hw.hit_cap) {
+				const int64_t c = std::max(nh, std::min(n_slot_cap, 2 * hw.hit_cap));
+				if (hw.d_hits) { HIPCHK(hipFree(hw.d_hits)); hw.d_hits = nullptr; }
+				if (hw.h_hits) { HIPCHK(hipHostFree(hw.h_hits)); hw.h_hits = nullptr; }
+				hw.hit_cap = 0;
+				HIPCHK(hipMalloc(&hw.d_hits, (size_t)c * sizeof(SwRaw)));
+				HIPCHK(hipHostMalloc((void**)&hw.h_hits, (size_t)c * sizeof(SwRaw), hipHostMallocDefault));
+				hw.hit_cap = c;
+			}
+			if (ns > hw.step_cap) {
+				const int64_t c = std::max(ns, 2 * hw.step_cap);
+				if (hw.d_steps) { HIPCHK(hipFree(hw.d_steps)); hw.d_steps = nullptr; }
+				if (hw.h_steps) { HIPCHK(hipHostFree(hw.h_steps)); hw.h_steps = nullptr; }
+				hw.step_cap = 0;
+				HIPCHK(hipMalloc(&hw.d_steps, (size_t)c + 64));
+				HIPCHK(hipHostMalloc((void**)&hw.h_steps, (size_t)c + 64, hipHostMallocDefault));
+				hw.step_cap = c;
+			}
+			HIPCHK(hipEventRecord(hw.e[2], h->st));
+			hipLaunchKernelGGL(k_sw_emit, dim3((unsigned)std::min<int64_t>((n_slot + 255) / 256, 16384)), dim3(256), 0, h->st, (const uint8_t*)d_sym, (const int64_t*)d_off, (const int64_t*)d_btoff,
+					q0, (int)N, (const uint32_t*)ws.bt, n_slot, (const uint32_t*)d_flag, (const SwRaw*)d_raw, (const int64_t*)d_hoff, (const int64_t*)d_soff, hw.d_hits, hw.d_steps, d_ctr);
+			HIPCHK(hipEventRecord(hw.e[3], h->st));
+			HIPCHK(hipMemcpyAsync(hw.h_hits, hw.d_hits, (size_t)nh * sizeof(SwRaw), hipMemcpyDeviceToHost, h->st));
+			if (ns > 0) HIPCHK(hipMemcpyAsync(hw.h_steps, hw.d_steps, (size_t)ns, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_bt += ev_ms(hw.e[2], hw.e[3]);
+			if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL;
+			for (int64_t i = 0; i < nh; ++i) {
+				const SwRaw &x = hw.h_hits[i];
+				rb3gpu_sw_hit_t &y = hits[(size_t)i];
+				y.lo = x.lo, y.hi = x.hi, y.score = x.score, y.qlen = x.qlen, y.rlen = x.rlen, y.n_steps = x.n_steps, y.step_off = x.step_off, y.pos_off = 0, y.n_pos = 0;
+			}
+			if (with_pos) { // the intervals of the hits, read where k_sw_emit left them; every hit at loc_cap, then cut to what rb3_sw gives it
+				for (int64_t r0 = 0; r0 < nh;) {
+					const int64_t lim = std::min(nh - r0, lws.n_cap);
+					lws.h_size.resize((size_t)lim);
+					for (int64_t i = 0; i < lim; ++i) lws.h_size[i] = hits[(size_t)(r0 + i)].hi - hits[(size_t)(r0 + i)].lo;
+					const int64_t nn = loc_slice_end(lws, lws.h_size.data(), 0, lim, loc_cap);
+					lws.h_size.resize((size_t)nn);
+					const int lr = loc_slice(h, lws, nn, (const int64_t*)(hw.d_hits + r0), (int)(sizeof(SwRaw) / 8), 0, loc_cap);
+					if (lr < 0) return lr;
+					const int64_t base = (int64_t)pairs.size(), np = lws.h_off[(size_t)nn];
+					if (np > 0) pairs.insert(pairs.end(), (const rb3gpu_pos_t*)lws.h_pairs, (const rb3gpu_pos_t*)lws.h_pairs + np);
+					for (int64_t i = 0; i < nn; ++i) hits[(size_t)(r0 + i)].pos_off = base + lws.h_off[(size_t)i];
+					r0 += nn;
+				}
+				int64_t at = 0;
+				for (int64_t q = 0; q < nq; ++q) { // bwa-sw.c:547-556
+					int64_t rest = opt->max_pos;
+					for (int32_t k = 0; k < hw.h_nhit[q]; ++k, ++at) {
+						if (at >= nh) return RB3GPU_EINTERNAL;
+						rb3gpu_sw_hit_t &y = hits[(size_t)at];
+						y.n_pos = std::min<int64_t>(rest > 0 ? rest : 1, y.hi - y.lo);
+						rest -= y.n_pos;
+					}
+				}
+				if (at != nh) return RB3GPU_EINTERNAL;
+			}
+		}
+		n_hits += nh, n_steps += ns;
+		ret = cb(ud, q0, nq, hw.h_nhit, hits.data(), hw.h_steps, pairs.data());
+	}
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->ms_backtrack = ms_bt, st->n_ext = (int64_t)hw.h_ctr[0], st->n_hits = n_hits, st->n_steps = n_steps,
+		st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
+	if (with_pos) loc_stats(lws, t0, lst);
 	return ret;
 }
 

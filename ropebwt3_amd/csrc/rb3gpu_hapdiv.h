@@ -202,6 +202,202 @@ __device__ __forceinline__ void hd_heap_put(int32_t *heap, int &sz, int N, int32
 	}
 }
 
+/* The rows of one query q[0, k) (steps 1-5 of the header comment) and the marking of the contained cells of the last row: the part that
+ * `hapdiv` and `sw -e` share.  Mismatches, gaps of the index side and the F phase start at row end_len + 1 (every cell of row i has
+ * consumed i symbols, its parent i - 1: the reference's tests on qlen, bwa-sw.c:405, 417, 445, all read i - 1 >= end_len); `hapdiv` has
+ * end_len 1.  BASES: bits 5-7 of a cell's third word hold its base (1..5) instead of "differs from the query", for a backtrack that
+ * writes the alignment out.  All lanes of the one wave call it; returns the cells of the last row (0: the alignment does not reach the
+ * end, or -- done == false -- something could not be represented); best_sc: the best score of any row; the dedup ran if both allow it */
+struct HdLds { HdCell *tab; HdTab *T; int32_t *err; };
+
+template<bool BASES>
+__device__ static int hd_rows(const IdxView &ix, const Acc7 &acc, const uint8_t *q, int k, int end_len, const HdOpt &o, const HdWs &ws, HdCell *gtab, HdCell *row, HdExt *ext,
+		int32_t *heap, HdZ *stack, int64_t *fpar, uint32_t *bt, const HdLds &L, int lds_slots, int bits0, unsigned long long &n_ext, int &best_sc, bool &done)
+{
+	const int lane = threadIdx.x, j = lane & 7, oct = lane >> 3;
+	const int N = o.N;
+	HdCell *const s_tab = L.tab;
+	HdTab &s_T = *L.T;
+	int32_t &s_err = *L.err;
+	__syncthreads();
+	if (lane == 0) {
+		HdTab T;
+		T.bits = bits0, T.count = 0, T.ub = HD_USED_A;
+		T.tier = (1 << bits0) > lds_slots ? 1 : 0;
+		T.t = T.tier ? gtab : s_tab;
+		s_T = T, s_err = 0;
+		HdCell r;
+		r.lo = 0, r.hi = acc.a[6], r.lo_rc = 0, r.H = r.E = r.F = 0, r.H_pos = r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 0, r.pad = 0;
+		row[0] = r;
+	}
+	if (lane < 3) bt[lane] = lane < 2 ? HD_NONE : 0u;
+	__syncthreads();
+	int n = 1;
+	best_sc = 0, done = true;
+	for (int i = 1; i <= k; ++i) {
+		const int cq = min((int)q[k - i], 5);
+		const bool inner = i > end_len;
+		{ // an empty table of the capacity it has grown to
+			HdCell *t = s_T.t;
+			const uint32_t cap = 1u << s_T.bits;
+			for (uint32_t s = lane; s < cap; s += 64) t[s].fl = 0;
+		}
+		for (int c0 = 0; c0 < n; c0 += 8) { // 1. the extensions of the row before
+			const int col = c0 + oct;
+			const bool act = col < n;
+			const int64_t lo = act ? row[col].lo : 0, hi = act ? row[col].hi : 0, rc = act ? row[col].lo_rc : 0;
+			HdExt e[5];
+			hd_extend(ix, lo, hi, rc, j, e);
+			if (act && j < 5) {
+				HdExt v = e[0];
+#pragma unroll
+				for (int c = 1; c < 5; ++c) v = j == c ? e[c] : v;
+				ext[col * 5 + j] = v;
+			}
+		}
+		__syncthreads();
+		if (lane == 0) { // 2. the candidates in the reference's order
+			HdTab T = s_T;
+			T.count = 0;
+			bool ok = true;
+			int ch;
+			for (int col = 0; col < n && ok; ++col) {
+				const HdCell p = row[col];
+				const uint32_t pos = (uint32_t)(i - 1) * (uint32_t)N + (uint32_t)col;
+				int64_t last_rc = 0;
+				HdCell r;
+				r.E = r.F = 0, r.H_pos = pos, r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 0, r.pad = 0;
+				for (int c = 1; c < 6 && ok; ++c) {
+					const HdExt e = ext[col * 5 + c - 1];
+					const int sc = c == cq && c != 5 ? o.ma : -o.mi;
+					if (e.hi == e.lo || p.H + sc <= 0 || (c != cq && !inner)) continue;
+					last_rc = e.rc;
+					r.lo = e.lo, r.hi = e.hi, r.lo_rc = e.rc, r.H = p.H + sc;
+					ok = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots) != nullptr;
+				}
+				int32_t ev = p.H - o.go > p.E ? p.H - o.go : p.E;
+				const uint32_t ef = p.H - o.go > p.E ? 0u : 4u;
+				ev -= o.ge;
+				if (ev > 0 && inner && ok) { // (the other strand's start of the gap cell: that of the last candidate made above, as in the reference)
+					r.lo = p.lo, r.hi = p.hi, r.lo_rc = last_rc, r.H = r.E = ev, r.F = 0, r.H_pos = HD_NONE, r.E_pos = pos, r.fl = 1u | ef;
+					ok = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots) != nullptr;
+				}
+			}
+			n_ext += n;
+			if (!ok) s_err = 1;
+			s_T = T;
+		}
+		__syncthreads();
+		if (s_err) { done = false; break; }
+		if (s_T.count == 0) { n = 0; break; }
+		n = hd_top(s_T.t, 1u << s_T.bits, s_T.ub, N, row, lane); // 3.
+		__syncthreads();
+		int n_fpar = 0;
+		if (inner) { // 4. the F phase
+			HdTab T = s_T; // (used by lane 0)
+			int hsz = 0, next = 0, sp = 0;
+			bool ok = true;
+			if (lane == 0) for (int t = n - 1; t >= 0; --t) hd_heap_put(heap, hsz, N, row[t].H);
+			for (;;) {
+				HdZ z = {0, 0, 0, 0, 0};
+				int32_t f = 0, low = 0;
+				uint32_t ff = 0;
+				int go_on = 0;
+				if (lane == 0) {
+					while (ok) { // the next cell of the stack whose gap extension beats the N-th best score
+						if (sp > 0) z = stack[--sp];
+						else if (next < n) {
+							const HdCell c = row[next++];
+							if (c.H <= o.go + o.ge) continue;
+							z.lo = c.lo, z.hi = c.hi, z.lo_rc = c.lo_rc, z.H = c.H, z.F = c.F;
+						} else break;
+						low = hsz < N ? 0 : heap[0];
+						f = z.H - o.go > z.F ? z.H - o.go : z.F;
+						ff = z.H - o.go > z.F ? 0u : 8u;
+						f -= o.ge;
+						if (f > low) { go_on = 1; break; }
+					}
+				}
+				go_on = __shfl(go_on, 0);
+				if (!go_on) break;
+				const int64_t zlo = hd_shfl64(z.lo, 0), zhi = hd_shfl64(z.hi, 0), zrc = hd_shfl64(z.lo_rc, 0);
+				HdExt e[5];
+				hd_extend(ix, zlo, zhi, zrc, j, e);
+				if (lane == 0) {
+					++n_ext;
+					for (int c = 0; c < 5 && ok; ++c) {
+						if (e[c].hi == e[c].lo) continue;
+						HdCell r;
+						r.lo = e[c].lo, r.hi = e[c].hi, r.lo_rc = e[c].rc, r.H = r.F = f, r.E = 0, r.H_pos = r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 2u | ff, r.pad = 0;
+						int ch;
+						HdCell *qc = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots);
+						if (qc == nullptr) { ok = false; break; }
+						if (!(ch & 4)) continue;
+						hd_heap_put(heap, hsz, N, f);
+						if (n_fpar >= ws.fpar_cap || n_fpar >= (int)HD_UNSET) { ok = false; break; }
+						fpar[2 * n_fpar] = z.lo, fpar[2 * n_fpar + 1] = z.hi;
+						qc->fl = (qc->fl & ~8u) | ff, qc->fpar = (uint32_t)n_fpar++;
+						if (f - o.ge > low) {
+							if (sp >= ws.stack_cap) { ok = false; break; }
+							HdZ y;
+							y.lo = qc->lo, y.hi = qc->hi, y.lo_rc = qc->lo_rc, y.H = qc->H, y.F = qc->F;
+							stack[sp++] = y;
+						}
+					}
+				}
+			}
+			if (lane == 0) {
+				s_T = T;
+				if (!ok) s_err = 1;
+			}
+			n_fpar = __shfl(n_fpar, 0);
+			__syncthreads();
+			if (s_err) { done = false; break; }
+			if (n_fpar > 0) {
+				n = hd_top(s_T.t, 1u << s_T.bits, s_T.ub, N, row, lane);
+				__syncthreads();
+				for (int c = lane; c < n; c += 64) { // the F parents: from intervals to columns of the row; a parent that fell out leaves F unset
+					if (row[c].F == 0 || row[c].fpar == HD_UNSET) continue;
+					const int64_t plo = fpar[2 * row[c].fpar], phi = fpar[2 * row[c].fpar + 1];
+					int at = -1;
+					for (int d = 0; d < n && at < 0; ++d)
+						if (row[d].lo == plo && row[d].hi == phi) at = d;
+					if (at >= 0) row[c].fpar = (uint32_t)at, row[c].fl |= HD_FSET;
+					else row[c].fpar = HD_UNSET;
+				}
+				__syncthreads();
+			}
+		}
+		best_sc = max(best_sc, row[0].H);
+		for (int c = lane; c < n; c += 64) { // 5. what the backtrack needs
+			const HdCell x = row[c];
+			int base = 0;
+#pragma unroll
+			for (int a = 1; a < 6; ++a) base = acc.a[a] <= x.lo ? a : base;
+			const uint32_t m = (x.fl & 15u) | (x.F != 0 && (x.fl & HD_FSET) ? 16u : 0u) | (BASES ? (uint32_t)base << 5 : base != cq ? 32u : 0u) | (x.fpar & 0xFFFFFFu) << 8;
+			uint32_t *d = bt + ((size_t)i * N + c) * 3;
+			d[0] = x.H_pos, d[1] = x.E_pos, d[2] = m;
+		}
+		__syncthreads();
+	}
+	if (done && n > 0 && best_sc >= o.min_sc) {
+		if (lane == 0) { // cells contained, on either strand, in a cell ranked before them that was kept
+			for (int c = 1; c < n; ++c) {
+				const HdCell p = row[c];
+				bool in = false;
+				for (int d = 0; d < c && !in; ++d) {
+					const HdCell x = row[d];
+					if (x.fl & HD_FLT) continue;
+					in = (x.lo_rc <= p.lo_rc && x.lo_rc + (x.hi - x.lo) >= p.lo_rc + (p.hi - p.lo)) || (x.lo <= p.lo && x.hi >= p.hi);
+				}
+				if (in) row[c].fl |= HD_FLT;
+			}
+		}
+		__syncthreads();
+	}
+	return n;
+}
+
 /* windows [w0, w1): window w is sym[win_off[w], win_off[w] + k); out: 9 numbers per window of the slice.
  * ctr[0] += extensions, ctr[1] += windows whose table went to global memory, ctr[2] != 0: something could not be represented */
 __global__ void __launch_bounds__(64) k_hapdiv(IdxView ix, Acc7 acc, const uint8_t *sym, const int64_t *win_off, int64_t w0, int64_t w1, HdOpt o, HdWs ws,
@@ -214,7 +410,7 @@ __global__ void __launch_bounds__(64) k_hapdiv(IdxView ix, Acc7 acc, const uint8
 	__shared__ HdTab s_T;
 	__shared__ int32_t s_res[9];
 	__shared__ int32_t s_err;
-	const int lane = threadIdx.x, j = lane & 7, oct = lane >> 3;
+	const int lane = threadIdx.x;
 	const int N = o.N, k = o.k;
 	const int64_t b = blockIdx.x;
 	uint32_t *bt = ws.bt + b * ws.bt_stride;
@@ -229,185 +425,15 @@ __global__ void __launch_bounds__(64) k_hapdiv(IdxView ix, Acc7 acc, const uint8
 	int bits0 = 2;
 	while ((1 << bits0) < 4 * N) ++bits0;
 	unsigned long long n_ext = 0, n_t2 = 0;
+	const HdLds L = { s_tab, &s_T, &s_err };
 
 	for (int64_t w = w0 + b; w < w1; w += gridDim.x) {
 		const uint8_t *q = sym + win_off[w];
-		__syncthreads();
-		if (lane == 0) {
-			HdTab T;
-			T.bits = bits0, T.count = 0, T.ub = HD_USED_A;
-			T.tier = (1 << bits0) > lds_slots ? 1 : 0;
-			T.t = T.tier ? gtab : s_tab;
-			s_T = T, s_err = 0;
-			HdCell r;
-			r.lo = 0, r.hi = acc.a[6], r.lo_rc = 0, r.H = r.E = r.F = 0, r.H_pos = r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 0, r.pad = 0;
-			row[0] = r;
-		}
 		if (lane < 9) s_res[lane] = 0;
-		if (lane < 3) bt[lane] = lane < 2 ? HD_NONE : 0u;
-		__syncthreads();
-		int n = 1, best_sc = 0;
+		int best_sc = 0;
 		bool done = true;
-		for (int i = 1; i <= k; ++i) {
-			const int cq = min((int)q[k - i], 5);
-			const bool inner = i > 1;
-			{ // an empty table of the capacity it has grown to
-				HdCell *t = s_T.t;
-				const uint32_t cap = 1u << s_T.bits;
-				for (uint32_t s = lane; s < cap; s += 64) t[s].fl = 0;
-			}
-			for (int c0 = 0; c0 < n; c0 += 8) { // 1. the extensions of the row before
-				const int col = c0 + oct;
-				const bool act = col < n;
-				const int64_t lo = act ? row[col].lo : 0, hi = act ? row[col].hi : 0, rc = act ? row[col].lo_rc : 0;
-				HdExt e[5];
-				hd_extend(ix, lo, hi, rc, j, e);
-				if (act && j < 5) {
-					HdExt v = e[0];
-#pragma unroll
-					for (int c = 1; c < 5; ++c) v = j == c ? e[c] : v;
-					ext[col * 5 + j] = v;
-				}
-			}
-			__syncthreads();
-			if (lane == 0) { // 2. the candidates in the reference's order
-				HdTab T = s_T;
-				T.count = 0;
-				bool ok = true;
-				int ch;
-				for (int col = 0; col < n && ok; ++col) {
-					const HdCell p = row[col];
-					const uint32_t pos = (uint32_t)(i - 1) * (uint32_t)N + (uint32_t)col;
-					int64_t last_rc = 0;
-					HdCell r;
-					r.E = r.F = 0, r.H_pos = pos, r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 0, r.pad = 0;
-					for (int c = 1; c < 6 && ok; ++c) {
-						const HdExt e = ext[col * 5 + c - 1];
-						const int sc = c == cq && c != 5 ? o.ma : -o.mi;
-						if (e.hi == e.lo || p.H + sc <= 0 || (c != cq && !inner)) continue;
-						last_rc = e.rc;
-						r.lo = e.lo, r.hi = e.hi, r.lo_rc = e.rc, r.H = p.H + sc;
-						ok = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots) != nullptr;
-					}
-					int32_t ev = p.H - o.go > p.E ? p.H - o.go : p.E;
-					const uint32_t ef = p.H - o.go > p.E ? 0u : 4u;
-					ev -= o.ge;
-					if (ev > 0 && inner && ok) { // (the other strand's start of the gap cell: that of the last candidate made above, as in the reference)
-						r.lo = p.lo, r.hi = p.hi, r.lo_rc = last_rc, r.H = r.E = ev, r.F = 0, r.H_pos = HD_NONE, r.E_pos = pos, r.fl = 1u | ef;
-						ok = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots) != nullptr;
-					}
-				}
-				n_ext += n;
-				if (!ok) s_err = 1;
-				s_T = T;
-			}
-			__syncthreads();
-			if (s_err) { done = false; break; }
-			if (s_T.count == 0) { n = 0; break; }
-			n = hd_top(s_T.t, 1u << s_T.bits, s_T.ub, N, row, lane); // 3.
-			__syncthreads();
-			int n_fpar = 0;
-			if (inner) { // 4. the F phase
-				HdTab T = s_T; // (used by lane 0)
-				int hsz = 0, next = 0, sp = 0;
-				bool ok = true;
-				if (lane == 0) for (int t = n - 1; t >= 0; --t) hd_heap_put(heap, hsz, N, row[t].H);
-				for (;;) {
-					HdZ z = {0, 0, 0, 0, 0};
-					int32_t f = 0, low = 0;
-					uint32_t ff = 0;
-					int go_on = 0;
-					if (lane == 0) {
-						while (ok) { // the next cell of the stack whose gap extension beats the N-th best score
-							if (sp > 0) z = stack[--sp];
-							else if (next < n) {
-								const HdCell c = row[next++];
-								if (c.H <= o.go + o.ge) continue;
-								z.lo = c.lo, z.hi = c.hi, z.lo_rc = c.lo_rc, z.H = c.H, z.F = c.F;
-							} else break;
-							low = hsz < N ? 0 : heap[0];
-							f = z.H - o.go > z.F ? z.H - o.go : z.F;
-							ff = z.H - o.go > z.F ? 0u : 8u;
-							f -= o.ge;
-							if (f > low) { go_on = 1; break; }
-						}
-					}
-					go_on = __shfl(go_on, 0);
-					if (!go_on) break;
-					const int64_t zlo = hd_shfl64(z.lo, 0), zhi = hd_shfl64(z.hi, 0), zrc = hd_shfl64(z.lo_rc, 0);
-					HdExt e[5];
-					hd_extend(ix, zlo, zhi, zrc, j, e);
-					if (lane == 0) {
-						++n_ext;
-						for (int c = 0; c < 5 && ok; ++c) {
-							if (e[c].hi == e[c].lo) continue;
-							HdCell r;
-							r.lo = e[c].lo, r.hi = e[c].hi, r.lo_rc = e[c].rc, r.H = r.F = f, r.E = 0, r.H_pos = r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 2u | ff, r.pad = 0;
-							int ch;
-							HdCell *qc = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots);
-							if (qc == nullptr) { ok = false; break; }
-							if (!(ch & 4)) continue;
-							hd_heap_put(heap, hsz, N, f);
-							if (n_fpar >= ws.fpar_cap || n_fpar >= (int)HD_UNSET) { ok = false; break; }
-							fpar[2 * n_fpar] = z.lo, fpar[2 * n_fpar + 1] = z.hi;
-							qc->fl = (qc->fl & ~8u) | ff, qc->fpar = (uint32_t)n_fpar++;
-							if (f - o.ge > low) {
-								if (sp >= ws.stack_cap) { ok = false; break; }
-								HdZ y;
-								y.lo = qc->lo, y.hi = qc->hi, y.lo_rc = qc->lo_rc, y.H = qc->H, y.F = qc->F;
-								stack[sp++] = y;
-							}
-						}
-					}
-				}
-				if (lane == 0) {
-					s_T = T;
-					if (!ok) s_err = 1;
-				}
-				n_fpar = __shfl(n_fpar, 0);
-				__syncthreads();
-				if (s_err) { done = false; break; }
-				if (n_fpar > 0) {
-					n = hd_top(s_T.t, 1u << s_T.bits, s_T.ub, N, row, lane);
-					__syncthreads();
-					for (int c = lane; c < n; c += 64) { // the F parents: from intervals to columns of the row; a parent that fell out leaves F unset
-						if (row[c].F == 0 || row[c].fpar == HD_UNSET) continue;
-						const int64_t plo = fpar[2 * row[c].fpar], phi = fpar[2 * row[c].fpar + 1];
-						int at = -1;
-						for (int d = 0; d < n && at < 0; ++d)
-							if (row[d].lo == plo && row[d].hi == phi) at = d;
-						if (at >= 0) row[c].fpar = (uint32_t)at, row[c].fl |= HD_FSET;
-						else row[c].fpar = HD_UNSET;
-					}
-					__syncthreads();
-				}
-			}
-			best_sc = max(best_sc, row[0].H);
-			for (int c = lane; c < n; c += 64) { // 5. what the backtrack needs
-				const HdCell x = row[c];
-				int base = 0;
-#pragma unroll
-				for (int a = 1; a < 6; ++a) base = acc.a[a] <= x.lo ? a : base;
-				const uint32_t m = (x.fl & 15u) | (x.F != 0 && (x.fl & HD_FSET) ? 16u : 0u) | (base != cq ? 32u : 0u) | (x.fpar & 0xFFFFFFu) << 8;
-				uint32_t *d = bt + ((size_t)i * N + c) * 3;
-				d[0] = x.H_pos, d[1] = x.E_pos, d[2] = m;
-			}
-			__syncthreads();
-		}
+		const int n = hd_rows<false>(ix, acc, q, k, 1, o, ws, gtab, row, ext, heap, stack, fpar, bt, L, lds_slots, bits0, n_ext, best_sc, done);
 		if (done && n > 0 && best_sc >= o.min_sc) {
-			if (lane == 0) { // cells contained, on either strand, in a cell ranked before them that was kept
-				for (int c = 1; c < n; ++c) {
-					const HdCell p = row[c];
-					bool in = false;
-					for (int d = 0; d < c && !in; ++d) {
-						const HdCell x = row[d];
-						if (x.fl & HD_FLT) continue;
-						in = (x.lo_rc <= p.lo_rc && x.lo_rc + (x.hi - x.lo) >= p.lo_rc + (p.hi - p.lo)) || (x.lo <= p.lo && x.hi >= p.hi);
-					}
-					if (in) row[c].fl |= HD_FLT;
-				}
-			}
-			__syncthreads();
 			const int32_t h0 = row[0].H;
 			const uint32_t limit = (uint32_t)(k + 1) * ((uint32_t)min(N, 1 << 20) + 1u);
 			for (int c = lane; c < n; c += 64) {

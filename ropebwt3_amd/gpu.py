@@ -65,6 +65,23 @@ class MemStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 HAPDIV_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p)
+SW_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+SW_HIT = np.dtype([("lo", "<i8"), ("hi", "<i8"), ("score", "<i4"), ("qlen", "<i4"), ("rlen", "<i4"), ("n_steps", "<i4"), ("step_off", "<i8"), ("pos_off", "<i8"),
+                   ("n_pos", "<i8")])  # rb3gpu_sw_hit_t
+SW_OPS = b"=XID"   # the operation of a step byte is its high nibble, the base of the index (1..5) its low one
+
+
+class SwOpt(ctypes.Structure):
+    _fields_ = [("n_best", ctypes.c_int32), ("min_sc", ctypes.c_int32), ("match", ctypes.c_int32), ("mis", ctypes.c_int32), ("gap_open", ctypes.c_int32),
+                ("gap_ext", ctypes.c_int32), ("e2e_drop", ctypes.c_int32), ("end_len", ctypes.c_int32), ("max_pos", ctypes.c_int64)]
+
+
+class SwStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_dp", ctypes.c_double), ("ms_backtrack", ctypes.c_double), ("n_ext", ctypes.c_int64), ("n_hits", ctypes.c_int64),
+                ("n_steps", ctypes.c_int64), ("n_tier2", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class HapdivOpt(ctypes.Structure):
@@ -204,6 +221,8 @@ SYMBOLS = {
                                       ctypes.POINTER(MemStats), ctypes.POINTER(LocateStats)]),
     "rb3gpu_hapdiv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(HapdivOpt), HAPDIV_F, ctypes.c_void_p,
                                      ctypes.POINTER(HapdivStats)]),
+    "rb3gpu_sw_e2e": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SwOpt), SW_F, ctypes.c_void_p, ctypes.POINTER(SwStats),
+                                     ctypes.POINTER(LocateStats)]),
     "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
 }
 
@@ -832,6 +851,44 @@ class Rb3Gpu:
             stats.update(st.as_dict())
         return out, where
 
+    def sw_e2e(self, queries, n_best=25, min_sc=30, match=1, mis=3, gap_open=5, gap_ext=2, e2e_drop=-1, end_len=1, max_pos=None, stats=None, locate_stats=None):
+        """rb3gpu_sw_e2e: the end-to-end alignments of the queries (as for mem) as the reference's `sw -e` finds them (end_len: its -k).  Returns a
+        list with one entry per query: the list of its hits in the reference's order, each a dict of lo, hi, score, qlen, rlen, steps (bytes, one
+        per step from query position 0 on: SW_OPS[b >> 4] and the base b & 15) and pos (a POS array; empty without positions).  max_pos None: no
+        positions; 0 or more (the handle needs set_ssa / keep_ssa): what `sw -p max_pos` gives every hit, one position each at 0.
+        stats / locate_stats: dicts that receive rb3gpu_sw_stats_t / rb3gpu_locate_stats_t"""
+        qs = [nt6_of(q) for q in queries]
+        off = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            off[1:] = np.cumsum([q.size for q in qs])
+        sym = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        out = [None] * len(qs)
+
+        def cb(_ud, q0, nq, n_hit, hits, steps, pos):
+            nh = np.frombuffer(ctypes.string_at(n_hit, nq * 4), dtype=np.int32)
+            tot = int(nh.sum())
+            hs = np.frombuffer(ctypes.string_at(hits, tot * SW_HIT.itemsize), dtype=SW_HIT) if tot else np.zeros(0, dtype=SW_HIT)
+            at = 0
+            for i in range(nq):
+                mine = []
+                for r in hs[at:at + int(nh[i])]:
+                    st_b = ctypes.string_at(steps + int(r["step_off"]), int(r["n_steps"])) if r["n_steps"] else b""
+                    n_pos = int(r["n_pos"])
+                    pp = np.frombuffer(ctypes.string_at(pos + int(r["pos_off"]) * POS.itemsize, n_pos * POS.itemsize), dtype=POS).copy() if n_pos else np.zeros(0, dtype=POS)
+                    mine.append(dict(lo=int(r["lo"]), hi=int(r["hi"]), score=int(r["score"]), qlen=int(r["qlen"]), rlen=int(r["rlen"]), steps=st_b, pos=pp))
+                out[q0 + i] = mine
+                at += int(nh[i])
+            return 0
+        st, lst = SwStats(), LocateStats()
+        opt = SwOpt(int(n_best), int(min_sc), int(match), int(mis), int(gap_open), int(gap_ext), int(e2e_drop), int(end_len), -1 if max_pos is None else int(max_pos))
+        self._chk(self._lib.rb3gpu_sw_e2e(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, ctypes.byref(opt), SW_F(cb), None, ctypes.byref(st),
+                                          ctypes.byref(lst)), "rb3gpu_sw_e2e")
+        if stats is not None:
+            stats.update(st.as_dict())
+        if locate_stats is not None:
+            locate_stats.update(lst.as_dict())
+        return out
+
     def sync(self):
         self._chk(self._lib.rb3gpu_sync(self._h), "rb3gpu_sync")
 
@@ -1152,3 +1209,122 @@ def hapdiv_lines(recs, where, k, names=None, first_id=0):
         out.append(nm + b"\t%d\t%d" % (int(where[i][1]), int(where[j - 1][1]) + k) + b"".join(b"\t%d" % int(x) for x in recs[i]) + b"\n")
         i = j
     return b"".join(out)
+
+
+def sw_cigar(steps):
+    """(cigar string, matching length, block length) of the step bytes of a hit"""
+    runs = []
+    for b in steps:
+        if runs and runs[-1][1] == b >> 4:
+            runs[-1][0] += 1
+        else:
+            runs.append([1, b >> 4])
+    return "".join("%d%s" % (n, "=XID"[op]) for n, op in runs), sum(n for n, op in runs if op == 0), len(steps)
+
+
+def sw_cs(steps, query):
+    """the cs string of a hit: query is the nt6 codes that were aligned"""
+    out, y, i, n = [], 0, 0, len(steps)
+    while i < n:
+        j, op = i, steps[i] >> 4
+        while j < n and steps[j] >> 4 == op:
+            j += 1
+        if op == 0:
+            out.append(":%d" % (j - i))
+        elif op == 1:
+            out.extend("*%s%s" % ("$acgtn"[min(int(query[y + t - i]), 5)], "$acgtn"[steps[t] & 15]) for t in range(i, j))
+        elif op == 2:
+            out.append("+" + "".join("$acgtn"[min(int(query[y + t]), 5)] for t in range(j - i)))
+        else:
+            out.append("-" + "".join("$acgtn"[steps[t] & 15] for t in range(i, j)))
+        if op != 3:
+            y += j - i
+        i = j
+    return "".join(out)
+
+
+def sw_rs(steps):
+    """the aligned symbols of the index (the rs tag of --seq)"""
+    return "".join("$ACGTN"[b & 15] for b in steps if b >> 4 != 2)
+
+
+def sw_lines(queries, hits, names=None, first_id=0, seq_names=None, lengths=None, unmapped=False, with_rs=False):
+    """the reference's PAF (`sw -e`) for the hits of Rb3Gpu.sw_e2e (bytes).  queries: what was aligned; names as for mem_lines; seq_names and lengths
+    (what <index>.len.gz holds) name the positions -- without them a position is written as string number and offset, and a hit without a position
+    has stars.  unmapped: the -u lines; with_rs: the rs tag of --seq"""
+    out = []
+    for q, (query, mine) in enumerate(zip(queries, hits)):
+        query = nt6_of(query)
+        nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
+        if isinstance(nm, bytes):
+            nm = nm.decode()
+        if not mine and unmapped:
+            out.append("%s\t%d\t*\t*\t*\t*\t*\t*\t*\t0\t0\t0\n" % (nm, query.size))
+        for h in mine:
+            rlen, pos = h["rlen"], h["pos"]
+            cg, mlen, blen = sw_cigar(h["steps"])
+
+            def stranded(p):
+                clen, x = int(lengths[int(p["sid"]) >> 1]), int(p["pos"])
+                return (clen, x, x + rlen) if int(p["sid"]) & 1 == 0 else (clen, clen - (x + rlen), clen - x)
+            f = [nm, str(query.size), "0", str(h["qlen"])]
+            if len(pos) > 0:
+                sid = int(pos[0]["sid"])
+                if seq_names is not None:
+                    clen, st, en = stranded(pos[0])
+                    f += ["+-"[sid & 1], seq_names[sid >> 1], str(clen), str(st), str(en)]
+                else:
+                    f += ["+", str(sid), "*", str(int(pos[0]["pos"])), str(int(pos[0]["pos"]) + rlen)]
+            else:
+                f += ["*", "*", str(rlen), "*", "*"]
+            f += [str(mlen), str(blen), "0", "AS:i:%d" % h["score"], "qh:i:1", "rh:i:%d" % (h["hi"] - h["lo"]), "cg:Z:" + cg, "cs:Z:" + sw_cs(h["steps"], query)]
+            if with_rs:
+                f.append("rs:Z:" + sw_rs(h["steps"]))
+            if len(pos) > 1:
+                if seq_names is not None:
+                    f.append("ap:Z:" + "".join("%s,%s,%d;" % (seq_names[int(p["sid"]) >> 1], "+-"[int(p["sid"]) & 1], stranded(p)[1]) for p in pos[1:]))
+                else:
+                    f.append("aq:Z:" + "".join("%d,%d;" % (int(p["sid"]), int(p["pos"])) for p in pos[1:]))
+            out.append("\t".join(f) + "\n")
+    return "".join(out).encode()
+
+
+SW_ALL_HEADER = b"CC\tQS  queryName  queryLen  numHap\nCC\tQH  refCount   score     editDist   cs   strand   nOut   totAln\nCC\n"
+
+
+def sw_all_lines(queries, hits, names=None, first_id=0, max_out=0, hits_rev=None):
+    """the reference's compact format (`sw --all-e2e`, `-g max_out`) without its three header lines (SW_ALL_HEADER): a QS line, the QH lines and // per
+    query; hits_rev: the hits of the reverse-complemented queries (-b), written as the `-` block behind each `+` block"""
+    out = []
+    cap = max_out if max_out > 0 else 1 << 62
+    for q, query in enumerate(queries):
+        query = nt6_of(query)
+        nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
+        if isinstance(nm, bytes):
+            nm = nm.decode()
+        for strand, mine in (("+", hits[q]),) + ((("-", hits_rev[q]),) if hits_rev is not None else ()):
+            seq = query if strand == "+" else revcomp6(query)
+            tot = sum(h["hi"] - h["lo"] for h in mine)
+            n_out = 0
+            for h in mine:
+                n_out += h["hi"] - h["lo"]
+                if n_out >= cap:
+                    break
+            out.append("QS\t%s\t%d\t%d\t%s\t%d\t%d\n" % (nm, query.size, len(mine), strand, n_out, tot))
+            n_out = 0
+            for h in mine:
+                _, mlen, blen = sw_cigar(h["steps"])
+                out.append("QH\t%d\t%d\t%d\t%s\n" % (h["hi"] - h["lo"], h["score"], blen - mlen, sw_cs(h["steps"], seq)))
+                n_out += h["hi"] - h["lo"]
+                if n_out >= cap:
+                    break
+            out.append("//\n")
+    return "".join(out).encode()
+
+
+def revcomp6(q):
+    """the reverse complement of nt6 codes (rb3_revcomp6: 1..4 are complemented, everything else stays)"""
+    q = np.asarray(q, dtype=np.uint8)[::-1].copy()
+    m = (q >= 1) & (q <= 4)
+    q[m] = 5 - q[m]
+    return q
