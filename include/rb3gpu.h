@@ -572,6 +572,33 @@ typedef struct { double ms_total, ms_dp, ms_backtrack; int64_t n_ext, n_hits, n_
 int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud,
 		rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst);
 
+/* the longest suffix of every query that occurs in the index, and how often (`ropebwt3 suffix`, main.c:167-217 of the reference: the one-sided backward
+ * extension rb3_fmi_extend1, fm-index.h:140-147, from the last symbol of the query leftwards until the interval is empty): query q = symbols[offsets[q],
+ * offsets[q + 1]) (nt6 codes 0..5 as for rb3gpu_mem; n_query + 1 offsets, offsets[0] = 0) gets out[q]: start, where that suffix begins in the query (0: the whole
+ * query occurs; the query's length: not even its last symbol does), and size, its occurrences (0 where start is the length).  A query of no symbols is
+ * (0, 0).  Any index serves, one strand or both.  An octet of lanes per query, a rank pair of one symbol per step; rb3gpu_tune "suffix_slice" queries per
+ * launch (default 4 M).  The call holds the symbols, 8 bytes per query and 16 per query of a slice on the device.  RB3GPU_EINVAL for a query of 2^31
+ * symbols or more (it is not walked); RB3GPU_ESTATE for a handle without an index.  st (may be NULL): ms_total wall time of the call, ms_walk the kernel
+ * alone (HIP events), n_steps extensions (a rank pair each), n_queries, n_symbols, n_slices */
+typedef struct { int64_t start, size; } rb3gpu_suffix_rec_t;
+typedef struct { double ms_total, ms_walk; int64_t n_queries, n_symbols, n_steps, n_slices; } rb3gpu_suffix_stats_t;
+int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, rb3gpu_suffix_rec_t *out, rb3gpu_suffix_stats_t *st);
+
+/* the indexed strings spelled out (`ropebwt3 get`, rb3_fmi_retrieve, fm-index.c:552-567 of the reference): from row rows[i] the LF walk until the row whose
+ * symbol is the sentinel; the symbols met, reversed, are the string in front of the suffix of that row -- for a sentinel's row k < acc[1] the whole of
+ * string k -- and the row the walk ends at is what rb3_fmi_retrieve returns.  A row outside [0, acc[6]) has no string and end row -1; such rows never
+ * reach the device.  The answers reach cb in the order asked, duplicates included, a slice at a time (host memory valid during the call only): the n rows
+ * from i0 on, their end rows, and the string of row i0 + i at symbols[off[i], off[i + 1]) (nt6 codes, text order; n + 1 offsets, off[0] = 0).  A nonzero
+ * return from cb stops the call and is returned.  An octet of lanes per row; the walk is made twice -- once for the lengths, once, after an exclusive
+ * scan of the lengths of a slice, to write the symbols where they belong -- and a slice is as many consecutive rows as rb3gpu_tune "get_slice" symbols
+ * admit (default 64 M; a longer string is a slice of its own), so the output held on the device is bounded by that budget or the longest string, not by
+ * the request.  One string is one dependent chain of LF steps: a single long string runs at the latency of a rank.  RB3GPU_EINVAL for a NULL callback;
+ * RB3GPU_ESTATE without an index; RB3GPU_EUNSUP for a string of 2^32 symbols or more; RB3GPU_EINTERNAL for a walk that does not end (not an index).
+ * st (may be NULL): ms_total wall time, ms_count and ms_emit the two walks (HIP events), n_steps LF steps of both, n_rows, n_symbols, n_slices */
+typedef int (*rb3gpu_retrieve_cb)(void *ud, int64_t i0, int64_t n, const int64_t *end_row, const int64_t *off, const uint8_t *symbols);
+typedef struct { double ms_total, ms_count, ms_emit; int64_t n_rows, n_symbols, n_steps, n_slices; } rb3gpu_retrieve_stats_t;
+int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_retrieve_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -590,6 +617,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "mem_slice" N (query symbols per output slice of rb3gpu_mem; 0 = 8 M);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
  *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e; 0 = 16 K), "sw_table" N (as "hapdiv_table", for rb3gpu_sw_e2e);
+ *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c
  * Test hooks "force_fallback", "tent_limit", "text_mode" exist only in the test build of the library (compiled with

@@ -1682,6 +1682,195 @@ no_side:
 	return 1;
 }
 
+/* suffix <idx> <seq.fa> [...] (main_suffix, main.c:167-217 of the reference): per query the longest suffix that occurs in the index -- where it starts,
+ * the query's length, its occurrences --, found on the GPU (rb3gpu_suffix).  The queries come through the reader of `mem`, in batches of a fixed number
+ * of symbols, and a line has the shape of a line of `mem`, so it goes through its formatter.  Any index serves, one strand or both.  Options the command
+ * does not know are passed over, as the reference's option loop does.  Difference: a query file that cannot be opened is one line and exit status 1 behind
+ * the answers of the files before it (the reference reads through a null pointer there). */
+#define SUFFIX_BATCH 100000000 /* query symbols per call of the engine */
+
+static const struct option walk_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_suffix(int argc, char *argv[])
+{
+	int c, is_line = 0, device = 0, ret = 0, j;
+	int64_t id = 0, n_steps = 0, n_slices = 0, n_batches = 0, n_sym = 0;
+	double ms_walk = 0, ms_engine = 0;
+	rb3gpu_t *h;
+	rb3gpu_opt_t gopt;
+	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0}, out = {0, 0, 0};
+	int64_t *off = 0, *name_off = 0, m_q = 0, m_rec = 0;
+	rb3gpu_suffix_rec_t *rec = 0;
+	optind = 1, opterr = 0;
+	while ((c = getopt_long(argc, argv, "L", walk_long_opts, 0)) >= 0) {
+		if (c == 'L') is_line = 1;
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+	}
+	if (argc - optind < 2) {
+		fprintf(stdout, "Usage: ropebwt3-amd suffix [options] <idx.fmr> <seq.fa> [...]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -L        one sequence per line in the input\n");
+		return 0;
+	}
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	h = rb3gpu_create(&gopt);
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
+	if (load_index(h, argv[optind]) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded the index\n", __func__, rb3h_realtime(), rb3h_percent_cpu());
+	for (j = optind + 1; j < argc && ret == 0; ++j) {
+		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
+		int eof = 0;
+		if (fp == 0) {
+			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
+			ret = 1;
+			break;
+		}
+		while (!eof && ret == 0) { /* a batch: records until their symbols reach SUFFIX_BATCH */
+			int64_t n_q = 0, l, i;
+			const uint8_t *s;
+			const char *name;
+			sym.l = names.l = 0;
+			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
+				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
+				if (n_q + 2 > m_q) {
+					m_q = m_q ? m_q * 2 : 1024;
+					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
+				}
+				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
+				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
+				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+				if (l > 0x7fffffffLL) { fprintf(stderr, "ERROR: a query of more than 2^31 - 1 symbols\n"); ret = 1; break; }
+				if (n_q == 0) off[0] = 0;
+				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
+				rb3h_char2nt6(l, sym.s + sym.l); /* main.c:200-202: the nt6 table, anything from 128 on is 5 */
+				sym.l += l, off[++n_q] = sym.l;
+				name_off[n_q - 1] = name ? names.l : -1;
+				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
+				if (sym.l >= SUFFIX_BATCH) break;
+			}
+			if (l < 0) eof = 1;
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q > 0 && ret == 0) {
+				rb3gpu_suffix_stats_t st;
+				int r, werr = 0;
+				if (n_q > m_rec) {
+					m_rec = n_q + (n_q >> 1) + 256;
+					rec = (rb3gpu_suffix_rec_t*)realloc(rec, (size_t)m_rec * sizeof(*rec));
+					if (rec == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+				}
+				r = rb3gpu_suffix(h, n_q, off, sym.s, rec, &st);
+				if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to find the suffixes: %s\n", rb3gpu_strerror(r)); ret = 1; break; }
+				for (i = 0; i < n_q && !werr; ++i) { /* name, start, length, occurrences: a line of `mem` (main.c:207-209; seq<N> counts every record) */
+					rb3h_mem_rec_t t;
+					t.query = i, t.x0 = 0, t.size = rec[i].size, t.st = (int32_t)rec[i].start, t.en = (int32_t)(off[i + 1] - off[i]);
+					if (rb3h_mem_format(&out, RB3H_MEM_LINES, 0, name_off[i] >= 0 ? (const char*)names.s + name_off[i] : 0, id + i, off[i + 1] - off[i], 1, &t) < 0) werr = 1;
+					if (out.l > (1 << 20) || i + 1 == n_q) {
+						if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) werr = 1;
+						out.l = 0;
+					}
+				}
+				if (werr) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+				id += n_q, ++n_batches, n_sym += sym.l;
+				n_steps += st.n_steps, n_slices += st.n_slices, ms_walk += st.ms_walk, ms_engine += st.ms_total;
+				if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] processed %lld sequences\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_q);
+			}
+		}
+		rb3h_seq_close(fp);
+	}
+	if (fflush(stdout) != 0 && ret == 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (rb3h_verbose >= 3 && ret == 0)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries of %lld symbols in %lld batch(es) and %lld slice(s): %lld extensions; %.3f ms in the engine, walk kernel %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_sym, (long long)n_batches, (long long)n_slices, (long long)n_steps, ms_engine, ms_walk);
+	free(out.s); free(sym.s); free(names.s); free(off); free(name_off); free(rec);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
+/* get <idx> <int> [...] (main_get, main.c:135-165 of the reference): for every argument, read with atol, the string in front of the suffix of that row --
+ * for a sentinel's row the whole indexed string -- as `>row end_row` and a line of $ACGTN letters; rows outside the index print nothing.  All rows of the
+ * command line go through ONE call of rb3gpu_retrieve.  Arguments that begin with `-` are options nobody knows and are passed over, wherever they stand. */
+typedef struct { const int64_t *rows; rb3h_buf_t out; int err; } get_out_t;
+
+static int get_sink(void *ud, int64_t i0, int64_t n, const int64_t *end_row, const int64_t *off, const uint8_t *symbols)
+{
+	get_out_t *o = (get_out_t*)ud;
+	int64_t i, k;
+	for (i = 0; i < n && !o->err; ++i) {
+		const int64_t l = off[i + 1] - off[i], need = l + 64;
+		uint8_t *p;
+		if (end_row[i] < 0) continue; /* main.c:157: no such row */
+		if (o->out.l + need > o->out.m) {
+			const int64_t m = (o->out.l + need) * 2;
+			uint8_t *t = (uint8_t*)realloc(o->out.s, (size_t)m);
+			if (t == 0) { o->err = 1; break; }
+			o->out.s = t, o->out.m = m;
+		}
+		p = o->out.s + o->out.l;
+		p += sprintf((char*)p, ">%ld %ld\n", (long)o->rows[i0 + i], (long)end_row[i]);
+		for (k = 0; k < l; ++k) *p++ = (uint8_t)"$ACGTN"[symbols[off[i] + k] < 6 ? symbols[off[i] + k] : 5];
+		*p++ = '\n';
+		o->out.l = p - o->out.s;
+		if (o->out.l > (1 << 20)) {
+			if (fwrite(o->out.s, 1, (size_t)o->out.l, stdout) != (size_t)o->out.l) o->err = 1;
+			o->out.l = 0;
+		}
+	}
+	return o->err ? -1 : 0;
+}
+
+static int main_get(int argc, char *argv[])
+{
+	int c, device = 0, ret = 0, i;
+	int64_t *rows, n = 0;
+	rb3gpu_t *h;
+	rb3gpu_opt_t gopt;
+	rb3gpu_retrieve_stats_t st;
+	get_out_t o;
+	optind = 1, opterr = 0;
+	while ((c = getopt_long(argc, argv, "", walk_long_opts, 0)) >= 0) {
+		if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+	}
+	if (argc - optind < 2) {
+		fprintf(stdout, "Usage: ropebwt3-amd get <idx.fmr> <int> [...]\n");
+		return 0;
+	}
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	h = rb3gpu_create(&gopt);
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
+	if (load_index(h, argv[optind]) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+		rb3gpu_destroy(h);
+		return 1;
+	}
+	rows = (int64_t*)malloc((size_t)(argc - optind) * 8);
+	if (rows == 0) { fprintf(stderr, "ERROR: out of memory\n"); rb3gpu_destroy(h); return 1; }
+	for (i = optind + 1; i < argc; ++i) rows[n++] = atol(argv[i]); /* main.c:155: `abc` is row 0 */
+	memset(&o, 0, sizeof(o));
+	o.rows = rows;
+	c = rb3gpu_retrieve(h, n, rows, get_sink, &o, &st);
+	if (c == 0 && !o.err && o.out.l > 0 && fwrite(o.out.s, 1, (size_t)o.out.l, stdout) != (size_t)o.out.l) o.err = 1;
+	if (c != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to retrieve the sequences: %s\n", rb3gpu_strerror(c)); ret = 1; }
+	else if (o.err || fflush(stdout) != 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (rb3h_verbose >= 3 && ret == 0)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld rows, %lld symbols in %lld slice(s): %lld LF steps; %.3f ms in the engine, counting walk %.3f ms, writing walk %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_rows, (long long)st.n_symbols, (long long)st.n_slices, (long long)st.n_steps, st.ms_total, st.ms_count, st.ms_emit);
+	free(o.out.s); free(rows);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* hapdiv: the windows of every query (k symbols every w, search.c:384-393) through rb3gpu_hapdiv, batch by batch; the lines of write_hapdiv */
 typedef struct { int32_t *r; int64_t n; } hapdiv_out_t;
 
@@ -2203,6 +2392,8 @@ static int usage(FILE *fp)
 	fprintf(fp, "    ssa        generate sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    kount      count k-mers in one or more FM-indexes (on an MI355X)\n");
 	fprintf(fp, "    mem        find super-maximal exact matches of queries (on an MI355X)\n");
+	fprintf(fp, "    suffix     find the longest matching suffix of queries (on an MI355X)\n");
+	fprintf(fp, "    get        retrieve the i-th sequence from a BWT (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
@@ -2222,6 +2413,8 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "ssa") == 0) ret = main_ssa(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "kount") == 0) ret = main_kount(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "mem") == 0) ret = main_mem(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "suffix") == 0) ret = main_suffix(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "get") == 0) ret = main_get(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);

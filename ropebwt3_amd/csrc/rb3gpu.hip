@@ -26,6 +26,7 @@
 #include "rb3gpu_part.h"
 #include "rb3gpu_kount.h"
 #include "rb3gpu_mem.h"
+#include "rb3gpu_walk.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
 #include "rb3gpu_locate.h"
@@ -155,6 +156,8 @@ struct Tune {
 	int64_t hapdiv_table = 0;// rb3gpu_hapdiv: slots of a window's candidate table in LDS (0: 256, at most 256); a table that needs more lies in global memory
 	int64_t sw_slice = 0;    // rb3gpu_sw_e2e: queries per launch and per piece handed to the callback (0: 16 K; fewer where the backtrack matrices of a slice would not fit)
 	int64_t sw_table = 0;    // rb3gpu_sw_e2e: slots of a query's candidate table in LDS (0: 256, at most 256), as hapdiv_table
+	int64_t suffix_slice = 0;// rb3gpu_suffix: queries per launch (0: 4 M)
+	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
 	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
 	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
@@ -672,6 +675,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "hapdiv_table")) t.hapdiv_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
 	else if (!strcmp(key, "sw_slice")) t.sw_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sw_table")) t.sw_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
+	else if (!strcmp(key, "suffix_slice")) t.suffix_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
 	else if (!strcmp(key, "locate_slice")) t.locate_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sh_host_rounds")) t.sh_host_rounds = v < 0 ? -1 : v != 0; // (-1: rounds on the device whatever the number of chains)
@@ -711,7 +716,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -5224,6 +5229,199 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->ms_backtrack = ms_bt, st->n_ext = (int64_t)hw.h_ctr[0], st->n_hits = n_hits, st->n_steps = n_steps,
 		st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
 	if (with_pos) loc_stats(lws, t0, lst);
+	return ret;
+}
+
+/* ---- suffix and get: the two plain walks (rb3gpu_walk.h) ----------------------------------------- */
+
+#define RB3_SUFFIX_SLICE ((int64_t)1 << 22)   // queries per launch
+#define RB3_GET_SLICE ((int64_t)1 << 26)      // symbols of an emit slice (a byte of device and of page-locked host memory each)
+
+struct WalkWs {
+	std::vector<void*> dv;
+	void *h_out = nullptr;
+	unsigned long long *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	~WalkWs()
+	{
+		for (void *p : dv) if (p) (void)hipFree(p);
+		if (h_out) (void)hipHostFree(h_out);
+		if (h_ctr) (void)hipHostFree(h_ctr);
+		if (e0) (void)hipEventDestroy(e0);
+		if (e1) (void)hipEventDestroy(e1);
+	}
+};
+
+int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, rb3gpu_suffix_rec_t *out, rb3gpu_suffix_stats_t *st)
+{
+	static_assert(sizeof(SuffixOut) == sizeof(rb3gpu_suffix_rec_t), "one record layout on both sides");
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || n_query < 0 || (n_query > 0 && (!offsets || !out))) return RB3GPU_EINVAL;
+	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
+	for (int64_t q = 0; q < n_query; ++q) { // the kernel keeps a position in 32 bits
+		const int64_t l = offsets[q + 1] - offsets[q];
+		if (l < 0 || l > 0x7fffffffLL) return RB3GPU_EINVAL;
+	}
+	const int64_t total = n_query > 0 ? offsets[n_query] : 0;
+	if (total > 0 && !symbols) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	if (st) st->n_queries = n_query, st->n_symbols = total;
+	if (total == 0) { // nothing but queries of no symbols
+		if (n_query > 0) memset(out, 0, (size_t)n_query * sizeof(*out));
+		if (st) st->ms_total = (now_s() - t0) * 1e3;
+		return 0;
+	}
+	const int64_t slice = std::min(n_query, h->tn.suffix_slice > 0 ? h->tn.suffix_slice : RB3_SUFFIX_SLICE);
+	WalkWs ws;
+	uint8_t *d_sym = nullptr;
+	int64_t *d_qoff = nullptr;
+	SuffixOut *d_out = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+	HIPCHK(dalloc(&d_sym, (size_t)total + 64));
+	HIPCHK(dalloc(&d_qoff, (size_t)(n_query + 1) * 8));
+	HIPCHK(dalloc(&d_out, (size_t)slice * sizeof(SuffixOut)));
+	HIPCHK(dalloc(&d_ctr, 64));
+	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 64, hipHostMallocDefault));
+	HIPCHK(hipEventCreate(&ws.e0));
+	HIPCHK(hipEventCreate(&ws.e1));
+	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+	const IdxView ix = view_of(h);
+	Acc7 acc;
+	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	double ms_walk = 0;
+	int64_t n_slices = 0;
+	for (int64_t q0 = 0; q0 < n_query; ++n_slices) {
+		const int64_t q1 = std::min(n_query, q0 + slice);
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
+		const int64_t nb = std::min<int64_t>(((q1 - q0) * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(ws.e0, h->st));
+		hipLaunchKernelGGL(k_suffix_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_qoff, q0, q1, d_out, d_ctr);
+		HIPCHK(hipEventRecord(ws.e1, h->st));
+		HIPCHK(hipMemcpyAsync(out + q0, d_out, (size_t)(q1 - q0) * sizeof(SuffixOut), hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_walk += ev_ms(ws.e0, ws.e1);
+		q0 = q1;
+	}
+	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_steps = (int64_t)ws.h_ctr[1], st->n_slices = n_slices;
+	return 0;
+}
+
+int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_retrieve_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || n < 0 || !cb || (n > 0 && !rows)) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	// the rows that exist (rb3_fmi_retrieve, fm-index.c:557: the others are answered -1 and nothing is walked for them): only they reach the device
+	std::vector<int64_t> vrow, vat; // vat[v]: which of the n rows asked for valid row v is
+	for (int64_t i = 0; i < n; ++i)
+		if (rows[i] >= 0 && rows[i] < h->n) vrow.push_back(rows[i]), vat.push_back(i);
+	const int64_t nv = (int64_t)vrow.size();
+	std::vector<int64_t> len((size_t)n, 0), end((size_t)n, -1), off;
+	const int64_t budget = h->tn.get_slice > 0 ? h->tn.get_slice : RB3_GET_SLICE;
+	WalkWs ws;
+	int64_t *d_rows = nullptr, *d_len = nullptr, *d_end = nullptr, *d_off = nullptr;
+	uint32_t *d_len32 = nullptr;
+	uint8_t *d_out = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	void *d_tmp = nullptr;
+	size_t tmp_bytes = 0;
+	double ms_count = 0, ms_emit = 0;
+	int64_t n_sym = 0, n_slices = 0, out_cap = 0;
+	const IdxView ix = view_of(h);
+	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+	if (nv > 0) { // count: the length of every walk and the row it ends at
+		HIPCHK(dalloc(&d_rows, (size_t)nv * 8));
+		HIPCHK(dalloc(&d_len, (size_t)nv * 8));
+		HIPCHK(dalloc(&d_end, (size_t)nv * 8));
+		HIPCHK(dalloc(&d_len32, (size_t)(nv + 1) * 4));
+		HIPCHK(dalloc(&d_off, (size_t)(nv + 1) * 8));
+		HIPCHK(dalloc(&d_ctr, 64));
+		HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 64, hipHostMallocDefault));
+		HIPCHK(hipEventCreate(&ws.e0));
+		HIPCHK(hipEventCreate(&ws.e1));
+		{
+			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, nv + 1, h->st);
+			if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+			HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
+		}
+		HIPCHK(hipMemcpyAsync(d_rows, vrow.data(), (size_t)nv * 8, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+		HIPCHK(hipMemsetAsync(d_len32, 0, (size_t)(nv + 1) * 4, h->st));
+		const int64_t nb = std::min<int64_t>((nv * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(ws.e0, h->st));
+		hipLaunchKernelGGL(k_get_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, (int64_t)0, nv, d_len, d_end, d_len32, (const int64_t*)nullptr, (uint8_t*)nullptr, (int64_t)0, d_ctr);
+		HIPCHK(hipEventRecord(ws.e1, h->st));
+		std::vector<int64_t> vlen((size_t)nv), vend((size_t)nv);
+		HIPCHK(hipMemcpyAsync(vlen.data(), d_len, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(vend.data(), d_end, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_count = ev_ms(ws.e0, ws.e1);
+		if (ws.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a walk that did not end: not an index
+		for (int64_t v = 0; v < nv; ++v) {
+			if (vlen[(size_t)v] < 0 || vlen[(size_t)v] >= h->n || vend[(size_t)v] < 0 || vend[(size_t)v] >= h->n) return RB3GPU_EINTERNAL;
+			if (vlen[(size_t)v] > 0xFFFFFFFFLL) return RB3GPU_EUNSUP; // (the scan of a slice adds 32-bit lengths)
+			len[(size_t)vat[(size_t)v]] = vlen[(size_t)v], end[(size_t)vat[(size_t)v]] = vend[(size_t)v];
+		}
+	}
+	// emit: slices of consecutive rows whose lengths sum to at most the budget, a longer row alone
+	int ret = 0;
+	for (int64_t i0 = 0, v0 = 0; i0 < n && ret == 0; ++n_slices) {
+		int64_t i1 = i0 + 1, tot = len[(size_t)i0];
+		while (i1 < n && tot + len[(size_t)i1] <= budget) tot += len[(size_t)i1++];
+		int64_t v1 = v0;
+		while (v1 < nv && vat[(size_t)v1] < i1) ++v1;
+		off.assign((size_t)(i1 - i0 + 1), 0);
+		for (int64_t i = i0; i < i1; ++i) off[(size_t)(i - i0 + 1)] = off[(size_t)(i - i0)] + len[(size_t)i];
+		if (tot > 0) {
+			if (tot > out_cap) { // (grows to the largest slice: the budget, or the one row that exceeds it)
+				if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
+				if (d_out) { for (void *&p : ws.dv) if (p == d_out) p = nullptr; HIPCHK(hipFree(d_out)); d_out = nullptr; }
+				out_cap = 0;
+				const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 20));
+				HIPCHK(dalloc(&d_out, (size_t)oc + 64));
+				HIPCHK(hipHostMalloc(&ws.h_out, (size_t)oc + 64, hipHostMallocDefault));
+				out_cap = oc;
+			}
+			size_t tb = tmp_bytes + 256;
+			const int r = rb3kount_scan(d_tmp, &tb, d_len32 + v0, d_off, v1 - v0 + 1, h->st); // (d_len32[nv] = 0: the entry behind the last row)
+			if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+			HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
+			HIPCHK(hipMemcpyAsync(ws.h_ctr + 4, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
+			const int64_t nb = std::min<int64_t>(((v1 - v0) * 8 + 255) / 256, 4096);
+			HIPCHK(hipEventRecord(ws.e0, h->st));
+			hipLaunchKernelGGL(k_get_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, v0, v1, d_len, d_end, d_len32, (const int64_t*)d_off, d_out, tot, d_ctr);
+			HIPCHK(hipEventRecord(ws.e1, h->st));
+			HIPCHK(hipMemcpyAsync(ws.h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_emit += ev_ms(ws.e0, ws.e1);
+			if ((int64_t)ws.h_ctr[4] != tot || ws.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // the scan on the device and the sum on the host are of the same lengths
+		}
+		n_sym += tot;
+		ret = cb(ud, i0, i1 - i0, end.data() + i0, off.data(), (const uint8_t*)ws.h_out);
+		i0 = i1, v0 = v1;
+	}
+	if (st) {
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = ms_count, st->ms_emit = ms_emit, st->n_rows = n, st->n_symbols = n_sym, st->n_slices = n_slices;
+		st->n_steps = ws.h_ctr ? (int64_t)ws.h_ctr[1] : 0;
+	}
 	return ret;
 }
 

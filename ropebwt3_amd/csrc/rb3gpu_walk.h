@@ -1,0 +1,118 @@
+/*
+ * rb3gpu_walk.h -- the two plain walks over the index: `suffix`, the longest suffix of a query that occurs in the index
+ * (main_suffix, main.c:167-217 of the reference, on the one-sided backward extension rb3_fmi_extend1, fm-index.h:140-147),
+ * and `get`, the i-th indexed string spelled out (rb3_fmi_retrieve, fm-index.c:552-567).
+ *
+ * Both are dependent chains of ranks: a step cannot start before the step in front of it has ended, so one chain runs at the
+ * latency of a rank and the throughput comes from the chains in flight.  An octet of lanes per chain, as everywhere in the
+ * engine; an octet that has finished its chain takes the next one from a counter, so the lanes of a wave stay busy whatever
+ * the chains' lengths (k_mem_walk, k_ssa_walk).
+ *
+ *   k_suffix_walk  a step is ONE pair of ranks of ONE symbol, at the two ends of the interval: two oct_rank_issue and two
+ *                  oct_rank_finish of the query's symbol -- a third of the decode of a step of k_mem_walk, which needs the
+ *                  six symbols of both ends for the other strand's interval.
+ *   k_get_walk     a step is oct_lf_self: the symbol at the row and its rank there.  Two modes of one template: COUNT
+ *                  notes the length of the walk and the row it met the sentinel at, EMIT walks again and stores symbol t of
+ *                  the walk at off + len - 1 - t, so the string lands in text order.  Between them lies an exclusive scan
+ *                  of the lengths of a slice of rows (the driver).
+ */
+#ifndef RB3GPU_WALK_H
+#define RB3GPU_WALK_H
+
+#include "rb3gpu_kernels.h"
+
+struct SuffixOut { int64_t start, size; };                            // rb3gpu_suffix_rec_t
+
+/* the next item of [0, n) from the counter, the same in the eight lanes of an octet */
+__device__ __forceinline__ int64_t walk_take(unsigned long long *ctr, int j)
+{
+	unsigned long long t = 0;
+	if (j == 0) t = atomicAdd(ctr, 1ull);
+	const uint32_t tl = oct_bcast0((uint32_t)t, j), th = oct_bcast0((uint32_t)(t >> 32), j);
+	return (int64_t)((unsigned long long)th << 32 | tl);
+}
+
+/* the queries [q0, q1): query q is sym[qoff[q], qoff[q + 1]) (fewer than 2^31 symbols: the driver refuses longer ones), its record out[q - q0].
+ * ctr[0]: the next query to hand out (0 at launch), ctr[1] += extension steps */
+__global__ void __launch_bounds__(256) k_suffix_walk(IdxView ix, Acc7 acc, const uint8_t *sym, const int64_t *qoff, int64_t q0, int64_t q1, SuffixOut *out, unsigned long long *ctr)
+{
+	const int j = threadIdx.x & 7;
+	bool act = false, done = false;
+	int64_t q = 0, qb = 0, k = 0, l = 0, last = 0;
+	int32_t i = -1;
+	unsigned long long steps = 0;
+	for (;;) {
+		while (!act && !done) { // (the same in the eight lanes of an octet)
+			q = q0 + walk_take(ctr, j);
+			if (q >= q1) { done = true; break; }
+			qb = qoff[q];
+			i = (int32_t)(qoff[q + 1] - qb) - 1;
+			k = 0, l = acc.a[6], last = 0;
+			if (i >= 0) act = true;
+			else if (j == 0) { SuffixOut r; r.start = 0, r.size = 0; out[q - q0] = r; } // a query of no symbols
+		}
+		if (__ballot(act) == 0ull) break;
+		// one extension by q[i]: the ranks of that symbol at both ends (main.c:199-206)
+		const int c = act ? min((int)sym[qb + i], 5) : 0;
+		RankLoad rl, ru;
+		oct_rank_issue(ix, act ? k : 0, j, rl); // (a finished octet: a valid address, the result unused)
+		oct_rank_issue(ix, act ? l : 0, j, ru);
+		const int64_t nk = oct_rank_finish(rl, c, j, ix.abs), nl = oct_rank_finish(ru, c, j, ix.abs);
+		if (act) {
+			++steps;
+			k = nk, l = nl;
+			const bool hit = l - k != 0;
+			if (hit) last = l - k, --i;
+			if (!hit || i < 0) { // the symbol at i does not extend the match, or the query ran out
+				if (j == 0) { SuffixOut r; r.start = (int64_t)i + 1, r.size = last; out[q - q0] = r; }
+				act = false;
+			}
+		}
+	}
+	if (j == 0 && steps) atomicAdd(ctr + 1, steps);
+}
+
+/* the rows rows[r0, r1) (each inside [0, ix.n): the driver keeps the others away; one that is not is answered like them, never walked).
+ * COUNT (EMIT = false): len[r] = the symbols in front of the sentinel, end[r] = the row whose symbol is the sentinel (what rb3_fmi_retrieve
+ * returns), len32[r] the length once more for the scan.  EMIT: symbol t of the walk of row r to out[off[r - r0] + len[r] - 1 - t], inside
+ * [0, cap).  ctr[0]: the next row to hand out (0 at launch), ctr[1] += LF steps, ctr[2] += walks that took more steps than the index has
+ * rows (no index does that: the driver answers RB3GPU_EINTERNAL) */
+template<bool EMIT> __global__ void __launch_bounds__(256) k_get_walk(IdxView ix, const int64_t *rows, int64_t r0, int64_t r1, int64_t *len, int64_t *end, uint32_t *len32,
+		const int64_t *off, uint8_t *out, int64_t cap, unsigned long long *ctr)
+{
+	const int j = threadIdx.x & 7;
+	bool act = false, done = false;
+	int64_t r = 0, k = 0, t = 0, base = 0;
+	unsigned long long steps = 0;
+	for (;;) {
+		while (!act && !done) {
+			r = r0 + walk_take(ctr, j);
+			if (r >= r1) { done = true; break; }
+			k = rows[r], t = 0;
+			if ((uint64_t)k < (uint64_t)ix.n) {
+				if (EMIT) base = off[r - r0] + len[r] - 1, act = len[r] > 0; // (a string of no symbols: nothing to write)
+				else act = true;
+			} else if (!EMIT && j == 0) len[r] = 0, end[r] = -1, len32[r] = 0u;
+		}
+		if (__ballot(act) == 0ull) break;
+		int c;
+		const int64_t k2 = oct_lf_self(ix, act ? k : 0, j, &c);
+		if (act) {
+			++steps;
+			if (c == 0 || t >= ix.n) { // the sentinel: the string starts here
+				if (!EMIT && j == 0) len[r] = t, end[r] = k, len32[r] = (uint32_t)t;
+				if (c != 0 && j == 0) atomicAdd(ctr + 2, 1ull);
+				act = false;
+			} else {
+				if (EMIT) {
+					const int64_t p = base - t;
+					if (j == 0 && p >= 0 && p < cap) out[p] = (uint8_t)c;
+				}
+				++t, k = k2;
+			}
+		}
+	}
+	if (j == 0 && steps) atomicAdd(ctr + 1, steps);
+}
+
+#endif

@@ -107,6 +107,26 @@ class LocateStats(ctypes.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+SUFFIX_REC = np.dtype([("start", "<i8"), ("size", "<i8")])  # rb3gpu_suffix_rec_t
+SUFFIX_OUT = np.dtype([("query", "<i8"), ("start", "<i8"), ("length", "<i8"), ("size", "<i8")])  # what Rb3Gpu.suffix returns
+RETRIEVE_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p)
+
+
+class SuffixStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_queries", ctypes.c_int64), ("n_symbols", ctypes.c_int64), ("n_steps", ctypes.c_int64),
+                ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RetrieveStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_count", ctypes.c_double), ("ms_emit", ctypes.c_double), ("n_rows", ctypes.c_int64), ("n_symbols", ctypes.c_int64),
+                ("n_steps", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
     "rb3gpu_opt_init": (None, [ctypes.POINTER(Opt)]),
@@ -224,6 +244,8 @@ SYMBOLS = {
     "rb3gpu_sw_e2e": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SwOpt), SW_F, ctypes.c_void_p, ctypes.POINTER(SwStats),
                                      ctypes.POINTER(LocateStats)]),
     "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
+    "rb3gpu_suffix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SuffixStats)]),
+    "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
 }
 
 # rb3gpu_comm_t (include/rb3gpu.h): the two collectives of the interval-sharded merge
@@ -824,6 +846,45 @@ class Rb3Gpu:
             stats.update(st.as_dict())
         return np.concatenate(got) if got else np.zeros(0, dtype=MEM_REC)
 
+    def suffix(self, queries, stats=None):
+        """rb3gpu_suffix: per query (forms as for mem) the longest suffix that occurs in the index, as the reference's `suffix` finds it: a structured
+        array (SUFFIX_OUT), one entry per query in input order -- query, start (where the suffix begins in the query), length (of the query), size
+        (the occurrences of the suffix; 0 where start == length).  stats: a dict that receives rb3gpu_suffix_stats_t"""
+        qs = [nt6_of(q) for q in queries]
+        off = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            off[1:] = np.cumsum([q.size for q in qs])
+        sym = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        rec = np.zeros(len(qs), dtype=SUFFIX_REC)
+        st = SuffixStats()
+        self._chk(self._lib.rb3gpu_suffix(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, rec.ctypes.data if rec.size else None, ctypes.byref(st)),
+                  "rb3gpu_suffix")
+        if stats is not None:
+            stats.update(st.as_dict())
+        out = np.zeros(len(qs), dtype=SUFFIX_OUT)
+        out["query"], out["start"], out["length"], out["size"] = np.arange(len(qs)), rec["start"], off[1:] - off[:-1], rec["size"]
+        return out
+
+    def retrieve(self, rows, stats=None):
+        """rb3gpu_retrieve: for every row asked for, in the order asked, the string in front of the suffix of that row (for a sentinel's row k < acc[1]
+        the whole of indexed string k) as the reference's `get` spells it: (end_rows, seqs) -- end_rows an int64 array, the row each walk met the
+        sentinel at (-1 for a row outside the index), seqs a list of uint8 arrays of nt6 codes in text order (empty for such a row).  stats: a dict
+        that receives rb3gpu_retrieve_stats_t"""
+        rows = np.ascontiguousarray(list(rows) if not isinstance(rows, np.ndarray) else rows, dtype=np.int64).reshape(-1)
+        ends, seqs = [], []
+
+        def cb(_ud, _i0, n, end_row, off, symbols):
+            o = np.ctypeslib.as_array(off, shape=(n + 1,)).copy()
+            ends.append(np.ctypeslib.as_array(end_row, shape=(n,)).copy())
+            buf = np.frombuffer(ctypes.string_at(symbols, int(o[n])), dtype=np.uint8) if o[n] > 0 else np.zeros(0, dtype=np.uint8)
+            seqs.extend(buf[int(o[i]):int(o[i + 1])].copy() for i in range(n))
+            return 0
+        st = RetrieveStats()
+        self._chk(self._lib.rb3gpu_retrieve(self._h, rows.size, rows.ctypes.data if rows.size else None, RETRIEVE_F(cb), None, ctypes.byref(st)), "rb3gpu_retrieve")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return (np.concatenate(ends) if ends else np.zeros(0, dtype=np.int64)), seqs
+
     def hapdiv(self, queries, k=101, w=50, n_best=25, min_sc=30, match=1, mis=3, gap_open=5, gap_ext=2, e2e_drop=-1, stats=None):
         """rb3gpu_hapdiv on the windows of the queries (k symbols every w, as the reference's `hapdiv` cuts them; queries as for mem): an (n, 9) int32
         array, a row of n_al, max_ed, n_hap[0..6] per window in query order, and -- second value -- the (query, offset) of every window as an (n, 2)
@@ -1191,6 +1252,30 @@ def mem_lines(recs, names=None, first_id=0, positions=None, seq_names=None, leng
         if isinstance(nm, str):
             nm = nm.encode()
         out.append(b"%s\t%d\t%d\t%d\n" % (nm, r["st"], r["en"], r["size"]))
+    return b"".join(out)
+
+
+def suffix_lines(recs, names=None, first_id=0):
+    """the reference's `suffix` output for the records of Rb3Gpu.suffix: name, start, length of the query, occurrences per query (bytes); names as
+    for mem_lines -- a query without a name is seq<first_id + q + 1>, the running number of the record"""
+    out = []
+    for r in recs:
+        q = int(r["query"])
+        nm = names[q] if names is not None and names[q] is not None else "seq%d" % (first_id + q + 1)
+        if isinstance(nm, str):
+            nm = nm.encode()
+        out.append(b"%s\t%d\t%d\t%d\n" % (nm, r["start"], r["length"], r["size"]))
+    return b"".join(out)
+
+
+def get_lines(rows, end_rows, seqs):
+    """the reference's `get` output for (end_rows, seqs) of Rb3Gpu.retrieve(rows): `>row end_row` and the string in $ACGTN letters, two lines per row;
+    nothing for a row outside the index (end row -1)"""
+    lut = np.frombuffer(b"$ACGTN", dtype=np.uint8)
+    out = []
+    for k, e, s in zip(rows, end_rows, seqs):
+        if int(e) >= 0:
+            out.append(b">%d %d\n" % (int(k), int(e)) + lut[np.minimum(np.asarray(s, dtype=np.uint8), 5)].tobytes() + b"\n")
     return b"".join(out)
 
 
