@@ -572,6 +572,24 @@ typedef struct { double ms_total, ms_dp, ms_backtrack; int64_t n_ext, n_hits, n_
 int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud,
 		rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst);
 
+/* local alignment of whole queries over their DAWG (`ropebwt3 sw` in its default mode: rb3_sw, bwa-sw.c:532-560, with rb3_dawg_gen): the rows of the dynamic
+ * program of rb3gpu_sw_e2e are the nodes of the query's directed acyclic word graph, which the caller builds (rb3h_dawg_batch of the host library; a graph is a
+ * function of the query alone).  Query q owns the nodes [node_off[q], node_off[q + 1]) (n_query + 1 offsets, node_off[0] = 0; at least the root, node 0 of the
+ * query); node g of the batch carries symbol node_sym[g] (1..4) and has the predecessors pre[pre_off[g], pre_off[g + 1]) (one offset more than there are nodes,
+ * pre_off[0] = 0), each a node number WITHIN the query and smaller than the node's own, in the order candidates arrive from them.  offsets are those of the
+ * queries' symbols as for rb3gpu_sw_e2e (symbols may be NULL: the nodes carry what is aligned).  A query has at most ONE hit: column 0 of the first node whose
+ * best score is above that of every earlier node, if that score reaches min_sc; its record, step bytes and positions are those of rb3gpu_sw_e2e (`=` is "the
+ * base is the node's symbol": the graph counts an N of the query as A), qlen the symbols of the query it spans, and hit_node[q] (n_query entries, written
+ * before the callback sees the slice of q) the node it ends at, -1 without a hit: the caller's qoff0 and n_qoff of that node say where on the query.
+ * e2e_drop plays no part.  Positions: one hit, so n_pos = min(max(max_pos, 1), hi - lo).  A slice is at most rb3gpu_tune "sw_slice" queries, fewer where the
+ * cells of all nodes (56 bytes per cell of n_node * n_best) and their backtrack words (12) would not fit in a quarter of the free memory; one query at least.
+ * A node's cells are extended once for every successor.  RB3GPU_EINVAL for a graph that is not one (offsets that decrease, a predecessor that is not an
+ * earlier node, more than 2 len + 2 nodes), n_node * n_best of 2^32 or more, and what rb3gpu_sw_e2e refuses; RB3GPU_ESTATE as there; RB3GPU_EINTERNAL if a
+ * query cannot be represented -- never a wrong record.  st (may be NULL): sw as rb3gpu_sw_e2e, n_nodes and n_edges of the batch */
+typedef struct { rb3gpu_sw_stats_t sw; int64_t n_nodes, n_edges; } rb3gpu_swl_stats_t;
+int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const int64_t *node_off, const uint8_t *node_sym, const int64_t *pre_off,
+		const int32_t *pre, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud, int32_t *hit_node, rb3gpu_swl_stats_t *st, rb3gpu_locate_stats_t *lst);
+
 /* the longest suffix of every query that occurs in the index, and how often (`ropebwt3 suffix`, main.c:167-217 of the reference: the one-sided backward
  * extension rb3_fmi_extend1, fm-index.h:140-147, from the last symbol of the query leftwards until the interval is empty): query q = symbols[offsets[q],
  * offsets[q + 1]) (nt6 codes 0..5 as for rb3gpu_mem; n_query + 1 offsets, offsets[0] = 0) gets out[q]: start, where that suffix begins in the query (0: the whole
@@ -616,7 +634,7 @@ int rb3gpu_stream_sync(void *stream);
  *   of fewer than N symbols carry the LF base in their slot headers; at most 2^32, only before an index exists: RB3GPU_ESTATE after);
  *   "mem_slice" N (query symbols per output slice of rb3gpu_mem; 0 = 8 M);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
- *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e; 0 = 16 K), "sw_table" N (as "hapdiv_table", for rb3gpu_sw_e2e);
+ *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e and rb3gpu_sw_local; 0 = 16 K), "sw_table" N (as "hapdiv_table", for both);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c

@@ -2041,7 +2041,9 @@ static int main_hapdiv(int argc, char *argv[])
 /* sw: the end-to-end alignments of every query (the reference's main_search for `sw` with -e, --all-e2e or -g, search.c:443-582) through rb3gpu_sw_e2e, batch by
  * batch; the PAF of write_paf or the blocks of write_all_hits (swfmt.c).  <index>.ssa and <index>.len.gz are loaded when they are there and belong to the index
  * (rb3_fmi_load_all, fm-index.c:606-640) unless --no-ssa, --all-e2e or -g says otherwise; with the first a hit gets positions, with the second they get names.
- * Differences, each a refusal with exit status 1 and nothing on stdout: the local mode (no -e), -j above the end length (the reference's MEM pre-filter),
+ * --local: the reference's default mode, the one best local hit of every query over the query's DAWG (host/dawg.c, rb3gpu_sw_local), written by the same write_paf
+ * with the hit's place on the query.  It is opt-in: without --local and without -e the command is refused as before.
+ * Differences, each a refusal with exit status 1 and nothing on stdout: no mode given (neither --local nor -e), --local with -e, --all-e2e or -g, -j above the end length (the reference's MEM pre-filter),
  * -N or -k below 1, and the options of `mem` and `hapdiv`. */
 typedef struct {
 	int32_t *n_hit; int64_t m_q;
@@ -2086,6 +2088,7 @@ static const struct option sw_long_opts[] = {
 	{ "no-ssa", no_argument, 0, 401 },
 	{ "seq", no_argument, 0, 402 },
 	{ "all-e2e", no_argument, 0, 406 },
+	{ "local", no_argument, 0, 407 },
 	{ "gpu", required_argument, 0, 301 },
 	{ "host-fmd", no_argument, 0, 308 },
 	{ 0, 0, 0, 0 }
@@ -2093,9 +2096,11 @@ static const struct option sw_long_opts[] = {
 
 static int main_sw(int argc, char *argv[])
 {
-	int c, is_line = 0, device = 0, ret = 0, j, e2e = 0, no_ssa = 0, write_all = 0, both = 0, unmapped = 0, with_rs = 0, max_pos = 0, min_mem_len = 0;
+	int c, is_line = 0, device = 0, ret = 0, j, e2e = 0, local = 0, no_ssa = 0, write_all = 0, both = 0, unmapped = 0, with_rs = 0, max_pos = 0, min_mem_len = 0;
 	int64_t batch_size = 100000000, id = 0, max_all_out = 0, n_ext = 0, n_hits = 0, n_tier2 = 0, n_slices = 0, n_batches = 0;
-	double ms_dp = 0, ms_bt = 0, ms_engine = 0, ms_locate = 0;
+	double ms_dp = 0, ms_bt = 0, ms_engine = 0, ms_locate = 0, ms_dawg = 0;
+	int64_t n_nodes = 0, n_edges = 0, *node_off = 0, m_node_off = 0;
+	int32_t *hit_node = 0;
 	rb3gpu_sw_opt_t so = { 25, 30, 1, 3, 5, 2, -1, 11, 0 };
 	rb3gpu_t *h;
 	rb3gpu_opt_t gopt;
@@ -2114,6 +2119,7 @@ static int main_sw(int argc, char *argv[])
 		if (c == 'L') is_line = 1;
 		else if (c == 'g') max_all_out = atol(optarg), write_all = 1, e2e = 1, so.end_len = 1, no_ssa = 1;
 		else if (c == 406) write_all = 1, e2e = 1, so.end_len = 1, no_ssa = 1;
+		else if (c == 407) local = 1;
 		else if (c == 'e') e2e = 1, so.end_len = 1;
 		else if (c == 'k') so.end_len = atoi(optarg);
 		else if (c == 'j') min_mem_len = atoi(optarg);
@@ -2139,7 +2145,8 @@ static int main_sw(int argc, char *argv[])
 	if (argc - optind < 2) {
 		fprintf(stdout, "Usage: ropebwt3-amd sw [options] <idx.fmr> <seq.fa> [...]\n");
 		fprintf(stderr, "Options:\n");
-		fprintf(stderr, "  -e          end-to-end mode (forcing -k to 1); required: the local mode is not implemented\n");
+		fprintf(stderr, "  --local     local mode: the best local hit of every query (BWA-SW over the query's DAWG)\n");
+		fprintf(stderr, "  -e          end-to-end mode (forcing -k to 1); one of --local and -e is required\n");
 		fprintf(stderr, "  -N INT      keep up to INT hits per row [%d]\n", so.n_best);
 		fprintf(stderr, "  -m INT      min alignment score [%d]\n", so.min_sc);
 		fprintf(stderr, "  -A INT      match score [%d]\n", so.match);
@@ -2159,7 +2166,8 @@ static int main_sw(int argc, char *argv[])
 		fprintf(stderr, "  -K NUM      query batch size [100m]\n");
 		return 0;
 	}
-	if (!e2e) { fprintf(stderr, "ERROR: local mode is not implemented: use -e\n"); return 1; }
+	if (local && e2e) { fprintf(stderr, "ERROR: --local does not go with -e, --all-e2e or -g\n"); return 1; }
+	if (!e2e && !local) { fprintf(stderr, "ERROR: local mode is not implemented: use -e\n"); return 1; }
 	if (so.n_best < 1) { fprintf(stderr, "ERROR: the number of hits kept per row (-N) must be at least 1\n"); return 1; }
 	if (so.end_len < 1) { fprintf(stderr, "ERROR: the end length (-k) must be at least 1\n"); return 1; }
 	if (so.n_best >= (1 << 24)) { fprintf(stderr, "ERROR: -N is too large\n"); return 1; }
@@ -2229,7 +2237,7 @@ static int main_sw(int argc, char *argv[])
 				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
 				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
 				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0 || o[0].n_hit == 0 || o[1].n_hit == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
-				if (l > 0x7ffffffeLL || (l + 1) * (int64_t)so.n_best >= 0xFFFFFFFFLL) { fprintf(stderr, "ERROR: a query times -N is too large\n"); ret = 1; break; }
+				if (l > 0x7ffffffeLL || (l + 1) * (int64_t)so.n_best * (local ? 2 : 1) >= 0xFFFFFFFFLL) { fprintf(stderr, "ERROR: a query times -N is too large\n"); ret = 1; break; }
 				if (n_q == 0) off[0] = 0;
 				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
 				rb3h_char2nt6(l, sym.s + sym.l); /* search.c:91 */
@@ -2241,6 +2249,45 @@ static int main_sw(int argc, char *argv[])
 			if (l < 0) eof = 1;
 			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
 			if (n_q == 0 || ret != 0) continue;
+			if (local) { /* the graphs of the batch on the host, the nodes as rows on the device, one hit per query at most with its place on the query */
+				rb3h_dawg_t dg;
+				rb3gpu_swl_stats_t st;
+				rb3gpu_locate_stats_t ls;
+				const double t_dg = rb3h_realtime();
+				int r;
+				if (n_q + 1 > m_node_off) {
+					m_node_off = n_q + 1;
+					node_off = (int64_t*)realloc(node_off, (size_t)m_node_off * 8), hit_node = (int32_t*)realloc(hit_node, (size_t)m_node_off * 4);
+				}
+				if (node_off == 0 || hit_node == 0 || (r = rb3h_dawg_batch(n_q, off, sym.s, &dg, node_off)) < 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; continue; }
+				ms_dawg += (rb3h_realtime() - t_dg) * 1e3;
+				o[0].m_q = n_q, o[0].n_hits = o[0].n_steps = o[0].n_pos = 0, o[0].err = 0;
+				r = rb3gpu_sw_local(h, n_q, off, sym.s, node_off, dg.sym, dg.pre_off, dg.pre, &so, sw_sink, &o[0], hit_node, &st, &ls);
+				if (r != 0 && o[0].err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+				else if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to align the queries: %s\n", rb3gpu_strerror(r)); ret = 1; }
+				n_ext += st.sw.n_ext, n_hits += st.sw.n_hits, n_tier2 += st.sw.n_tier2, n_slices += st.sw.n_slices, ms_dp += st.sw.ms_dp, ms_bt += st.sw.ms_backtrack, ms_engine += st.sw.ms_total;
+				ms_locate += ls.ms_locate, n_nodes += st.n_nodes, n_edges += st.n_edges;
+				for (q = 0; q < n_q && ret == 0; ++q) {
+					const char *nm = name_off[q] >= 0 ? (const char*)names.s + name_off[q] : 0;
+					const int64_t g = o[0].n_hit[q] > 0 ? node_off[q] + hit_node[q] : 0;
+					if (o[0].n_hit[q] > 1 || (o[0].n_hit[q] == 1 && (hit_node[q] < 0 || g >= node_off[q + 1]))) r = -3;
+					else r = rb3h_sw_format_paf_at(&out, nm, id + q, off[q + 1] - off[q], sym.s + off[q], o[0].n_hit[q], o[0].hits + at[0], o[0].steps, o[0].pos, sid, unmapped, with_rs,
+							dg.qoff0 + g, dg.n_qoff + g);
+					at[0] += o[0].n_hit[q];
+					if (r == -2) { fprintf(stderr, "ERROR: a position names a sequence that the name list does not have\n"); ret = 1; break; }
+					if (r == -3) { fprintf(stderr, "ERROR: the GPU engine returned a hit that is not on the query\n"); ret = 1; break; }
+					if (r < 0) ret = 1;
+					if (out.l > (1 << 20) || q == n_q - 1) {
+						if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) ret = 1;
+						out.l = 0;
+					}
+					if (ret) fprintf(stderr, "ERROR: failed to write the output\n");
+				}
+				rb3h_dawg_free(&dg);
+				id += n_q, ++n_batches;
+				if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] processed %lld sequences\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_q);
+				continue;
+			}
 			for (pass = 0; pass < (write_all && both ? 2 : 1) && ret == 0; ++pass) { /* the second pass: every query reverse-complemented in place (search.c:94-98) */
 				rb3gpu_sw_stats_t st;
 				rb3gpu_locate_stats_t ls;
@@ -2285,8 +2332,10 @@ static int main_sw(int argc, char *argv[])
 	if (rb3h_verbose >= 3 && ret == 0)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld hits in %lld slice(s), %lld extensions, %lld queries with a table in global memory; %.3f ms in the engine, the DP kernel %.3f ms, the backtrack %.3f ms, the locate kernels %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_hits, (long long)n_slices, (long long)n_ext, (long long)n_tier2, ms_engine, ms_dp, ms_bt, ms_locate);
+	if (rb3h_verbose >= 3 && ret == 0 && local)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] the graphs: %lld nodes, %lld edges, %.3f ms on the host\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_nodes, (long long)n_edges, ms_dawg);
 	for (j = 0; j < 2; ++j) { free(o[j].n_hit); free(o[j].hits); free(o[j].steps); free(o[j].pos); }
-	free(out.s); free(sym.s); free(rev.s); free(names.s); free(off); free(name_off);
+	free(out.s); free(sym.s); free(rev.s); free(names.s); free(off); free(name_off); free(node_off); free(hit_node);
 	rb3gpu_destroy(h);
 	rb3h_sid_destroy(sid);
 	return ret;

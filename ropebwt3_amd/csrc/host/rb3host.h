@@ -92,6 +92,21 @@ int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t le
 int rb3h_sw_format_all(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
 		char strand, int64_t max_out);
 
+/* the same with the hit's place on the query (`sw --local`): columns 3 and 4 are qoff0[i] and qoff0[i] + qlen of hit i, the cs string reads the query from
+ * qoff0[i] on, and qh:i: is n_qoff[i].  qoff0 / n_qoff NULL: 0 and 1, which is rb3h_sw_format_paf */
+int rb3h_sw_format_paf_at(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
+		const rb3h_pos_t *pos, const rb3h_sid_t *sid, int unmapped, int with_rs, const int32_t *qoff0, const int32_t *n_qoff);
+
+/* ---- the graph of a query that `sw --local` aligns over (dawg.c) ---- */
+/* n_node nodes in topological order, node 0 the root (the empty string); node i carries symbol sym[i] (1..4; 0 for the root), its predecessors are
+ * pre[pre_off[i], pre_off[i + 1]) in the order candidates arrive from them, its string starts at qoff0[i] of the query and occurs n_qoff[i] times in it */
+typedef struct { int64_t n_node, n_pre; uint8_t *sym; int64_t *pre_off; int32_t *pre, *qoff0, *n_qoff; } rb3h_dawg_t;
+int rb3h_dawg_build(int64_t len, const uint8_t *seq, rb3h_dawg_t *g);       /* seq: nt6 codes; 0, -1 (no memory) or -3 (too long) */
+/* the graphs of the queries symbols[offsets[q], offsets[q + 1]) one after another (OpenMP over the queries): query q owns the nodes [node_off[q], node_off[q + 1])
+ * of `out`, pre_off[] runs over all nodes and names places of pre[], whose entries are node numbers within the query; node_off holds n_query + 1 */
+int rb3h_dawg_batch(int64_t n_query, const int64_t *offsets, const uint8_t *symbols, rb3h_dawg_t *out, int64_t *node_off);
+void rb3h_dawg_free(rb3h_dawg_t *g);
+
 /* ---- the files beside an index that `mem -p` and `sw` read (sidefile.c) ---- */
 typedef struct { int32_t ss, ms; int64_t m, n_ssa; uint64_t *r2i, *ssa; } rb3h_ssa_t;
 rb3h_ssa_t *rb3h_ssa_read(const char *fn);                                 /* rb3_ssa_restore, ssa.c:215-241; NULL: no file, wrong magic, or it ends early */

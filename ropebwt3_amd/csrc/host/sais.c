@@ -56,6 +56,12 @@ int rb3h_build_bwt(int64_t n_seq, int64_t len, uint8_t *seq, int n_threads)
 	return sais_bwt_64(n_seq, len, seq, 0, 0);
 }
 
+/* the suffix array of one text over [0, K): T[n - 1] = 0 and nowhere else (dawg.c: a query and its sentinel, so SA[0] = n - 1) */
+int rb3h_sais_i32(const int32_t *T, int32_t *SA, int32_t n, int32_t K)
+{
+	return sais_main_32(T, SA, n, K);
+}
+
 #define RB3H_MIN_SEG 128
 #define RB3H_PROBE 64 /* a walker looks that many positions to the right of its start row for a record of its right neighbour.  (24 until the end
                        * of round 3: a walker that starts late runs its first iterations slower than the neighbour that follows it -- cold caches,

@@ -1,5 +1,5 @@
 /*
- * swfmt.c -- the text `sw` writes for one query in end-to-end mode, made from the step bytes of its hits (rb3gpu_sw_e2e: one byte per
+ * swfmt.c -- the text `sw` writes for one query (end to end, or its one local hit with its place on the query), made from the step bytes of its hits (rb3gpu_sw_e2e: one byte per
  * step from query position 0 on, op << 4 | base): the PAF of write_paf (search.c:175-216) with the cigar, the cs string (sw_cs_core,
  * bwa-sw.c:116-152), the rs tag and the further positions, the -u line of a query without a hit, and the QS / QH / // block of
  * write_all_hits (search.c:218-238).  Into a buffer that the caller writes out in large pieces, as memfmt.c does.
@@ -83,8 +83,8 @@ static void sw_stranded(const rb3h_sid_t *sid, const rb3h_pos_t *pos, int32_t rl
 	else *st = *clen - (pos->pos + rlen), *en = *clen - pos->pos;
 }
 
-int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
-		const rb3h_pos_t *pos, const rb3h_sid_t *sid, int unmapped, int with_rs)
+int rb3h_sw_format_paf_at(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
+		const rb3h_pos_t *pos, const rb3h_sid_t *sid, int unmapped, int with_rs, const int32_t *qoff0, const int32_t *n_qoff)
 {
 	const int64_t l_name = name ? (int64_t)strlen(name) : 24;
 	int64_t i, k;
@@ -102,8 +102,10 @@ int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t le
 		const rb3h_sw_hit_t *h = hits + i;
 		const uint8_t *st = steps + h->step_off;
 		const rb3h_pos_t *hp = h->n_pos > 0 ? pos + h->pos_off : 0;
+		const int64_t q0 = qoff0 ? qoff0[i] : 0; /* where the hit starts on the query: 0 end to end, the node's place in the local mode */
 		int64_t mlen, blen, l_sn = 0;
 		int32_t j;
+		if (q0 < 0 || q0 + h->qlen > len) return -3;
 		for (k = 0; k < h->n_pos; ++k) { /* (a string the name list does not know: the files do not belong together) */
 			if (sid && (hp[k].sid < 0 || (hp[k].sid >> 1) >= sid->n_seq)) return -2;
 			if (sid) l_sn += (int64_t)strlen(sid->name[hp[k].sid >> 1]);
@@ -111,8 +113,8 @@ int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t le
 		if (sw_reserve(out, l_name + 512 + (int64_t)h->n_steps * 20 + l_sn + h->n_pos * 48) < 0) return -1;
 		p = sw_name(out->s + out->l, name, id);
 		*p++ = '\t', p = sw_num(p, len);
-		*p++ = '\t', *p++ = '0';
-		*p++ = '\t', p = sw_num(p, h->qlen);
+		*p++ = '\t', p = sw_num(p, q0);
+		*p++ = '\t', p = sw_num(p, q0 + h->qlen);
 		if (hp) {
 			if (sid) {
 				int64_t clen, s0, e0;
@@ -132,7 +134,8 @@ int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t le
 		*p++ = '\t', p = sw_num(p, mlen);
 		*p++ = '\t', p = sw_num(p, blen);
 		p = sw_str(p, "\t0\tAS:i:"), p = sw_num(p, h->score);
-		p = sw_str(p, "\tqh:i:1\trh:i:"), p = sw_num(p, h->hi - h->lo);
+		p = sw_str(p, "\tqh:i:"), p = sw_num(p, n_qoff ? n_qoff[i] : 1);
+		p = sw_str(p, "\trh:i:"), p = sw_num(p, h->hi - h->lo);
 		p = sw_str(p, "\tcg:Z:");
 		for (j = 0; j < h->n_steps;) {
 			int32_t e = j + 1;
@@ -140,7 +143,7 @@ int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t le
 			p = sw_num(p, e - j), *p++ = (uint8_t)"=XID"[st[j] >> 4 & 3];
 			j = e;
 		}
-		p = sw_str(p, "\tcs:Z:"), p = sw_cs(p, seq, h->n_steps, st);
+		p = sw_str(p, "\tcs:Z:"), p = sw_cs(p, seq + q0, h->n_steps, st);
 		if (with_rs) {
 			p = sw_str(p, "\trs:Z:");
 			for (j = 0; j < h->n_steps; ++j)
@@ -162,6 +165,12 @@ int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t le
 		out->l = p - out->s;
 	}
 	return 0;
+}
+
+int rb3h_sw_format_paf(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,
+		const rb3h_pos_t *pos, const rb3h_sid_t *sid, int unmapped, int with_rs)
+{
+	return rb3h_sw_format_paf_at(out, name, id, len, seq, n, hits, steps, pos, sid, unmapped, with_rs, 0, 0);
 }
 
 int rb3h_sw_format_all(rb3h_buf_t *out, const char *name, int64_t id, int64_t len, const uint8_t *seq, int64_t n, const rb3h_sw_hit_t *hits, const uint8_t *steps,

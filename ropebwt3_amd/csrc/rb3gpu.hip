@@ -29,6 +29,7 @@
 #include "rb3gpu_walk.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
+#include "rb3gpu_swlocal.h"
 #include "rb3gpu_locate.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -5228,6 +5229,234 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	}
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->ms_backtrack = ms_bt, st->n_ext = (int64_t)hw.h_ctr[0], st->n_hits = n_hits, st->n_steps = n_steps,
 		st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
+	if (with_pos) loc_stats(lws, t0, lst);
+	return ret;
+}
+
+/* ---- sw --local: local alignment of whole queries over their DAWG (rb3gpu_swlocal.h) ------------- */
+
+int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const int64_t *node_off, const uint8_t *node_sym, const int64_t *pre_off,
+		const int32_t *pre, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud, int32_t *hit_node, rb3gpu_swl_stats_t *st, rb3gpu_locate_stats_t *lst)
+{
+	static_assert(sizeof(SwRaw) == 40, "the locate step reads (lo, hi) with a stride of five words");
+	static_assert(sizeof(HdCell) == 56 && sizeof(HdCell) % 4 == 0, "a cell is copied word by word");
+	if (st) memset(st, 0, sizeof(*st));
+	if (lst) memset(lst, 0, sizeof(*lst));
+	if (!h || !opt || !cb || opt->n_best < 1 || opt->end_len < 1 || n_query < 0 || n_query > 0x7fffffffLL) return RB3GPU_EINVAL;
+	if (n_query > 0 && (!offsets || !node_off || !node_sym || !pre_off || !hit_node)) return RB3GPU_EINVAL;
+	if (opt->n_best >= (1 << 24)) return RB3GPU_EINVAL; // (the F column of a cell has 24 bits)
+	if (n_query > 0 && (offsets[0] != 0 || node_off[0] != 0)) return RB3GPU_EINVAL;
+	const int64_t N = opt->n_best;
+	(void)symbols; // (the rows are the nodes: their symbols are what is aligned)
+	for (int64_t q = 0; q < n_query; ++q) { // a cell is named by node * n_best + column in 32 bits; a graph has at most two nodes per suffix
+		const int64_t l = offsets[q + 1] - offsets[q], nn = node_off[q + 1] - node_off[q];
+		if (l < 0 || l > 0x7ffffffeLL || nn < 1 || nn > 2 * l + 2 || nn * N >= 0xFFFFFFFFLL) return RB3GPU_EINVAL;
+	}
+	const int64_t n_nodes = n_query > 0 ? node_off[n_query] : 0;
+	const int64_t n_edges = n_nodes > 0 ? pre_off[n_nodes] : 0;
+	if (n_nodes > 0 && pre_off[0] != 0) return RB3GPU_EINVAL;
+	if (n_edges < 0 || (n_edges > 0 && !pre)) return RB3GPU_EINVAL;
+	for (int64_t q = 0; q < n_query; ++q) // every predecessor is an earlier node of the same query (the kernel checks again what it reads)
+		for (int64_t g = node_off[q]; g < node_off[q + 1]; ++g) {
+			if (pre_off[g + 1] < pre_off[g] || pre_off[g + 1] > n_edges) return RB3GPU_EINVAL;
+			for (int64_t j = pre_off[g]; j < pre_off[g + 1]; ++j)
+				if (pre[j] < 0 || pre[j] >= g - node_off[q]) return RB3GPU_EINVAL;
+		}
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE; // both strands, as rb3gpu_mem
+	const bool with_pos = opt->max_pos >= 0;
+	if (with_pos && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
+	const int64_t loc_cap = std::max<int64_t>(1, opt->max_pos); // one hit per query: rest > 0 ? rest : 1 at its first and only hit
+	HIPCHK(hipSetDevice(h->dev));
+	const double t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	if (n_query == 0) { if (st) st->sw.ms_total = (now_s() - t0) * 1e3; return 0; }
+	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
+	int64_t cap0 = 4;
+	while (cap0 < 4 * N) cap0 *= 2;
+	SlWs ws;
+	memset(&ws, 0, sizeof(ws));
+	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
+	ws.stack_cap = 16 * N + 64;
+	ws.fpar_cap = 32 * N + 64;
+	const size_t per_block = (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(SlZ) + (size_t)ws.fpar_cap * 16 + 256;
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
+	// the slices: at most sw_slice queries, and cells plus backtrack words (68 bytes a cell) in a quarter of the free memory, but one query at least
+	const int64_t cell_bytes = (int64_t)sizeof(HdCell) + 12;
+	const int64_t max_q = std::max<int64_t>(1, h->tn.sw_slice > 0 ? h->tn.sw_slice : RB3_SW_SLICE);
+	const int64_t budget = std::max<int64_t>((int64_t)1 << 20, (int64_t)(fr / 4)) / cell_bytes;
+	std::vector<int64_t> cell_off((size_t)n_query), cuts(1, 0);
+	int64_t max_cells = 0, max_nodes = 0;
+	{
+		int64_t cells = 0;
+		for (int64_t q = 0; q < n_query; ++q) {
+			const int64_t c = (node_off[q + 1] - node_off[q]) * N;
+			if (q > cuts.back() && (q - cuts.back() >= max_q || cells + c > budget)) cuts.push_back(q), cells = 0;
+			cell_off[q] = cells, cells += c;
+			max_cells = std::max(max_cells, cells);
+			max_nodes = std::max(max_nodes, node_off[q + 1] - node_off[cuts.back()]);
+		}
+		cuts.push_back(n_query);
+	}
+	int64_t slice = 0;
+	for (size_t i = 0; i + 1 < cuts.size(); ++i) slice = std::max(slice, cuts[i + 1] - cuts[i]);
+	const size_t fixed = (size_t)n_nodes * 9 + (size_t)n_edges * 4 + (size_t)n_query * 16 + (size_t)max_cells * cell_bytes + (size_t)max_nodes * 4 + (size_t)slice * 128 + ((size_t)64 << 20);
+	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
+	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
+	SwHostWs hw;
+	LocWs lws;
+	if (with_pos) {
+		const int r = loc_init(h, lws, std::min<int64_t>(slice, RB3_LOC_SLICE_IV), false);
+		if (r < 0) return r;
+	}
+	auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes + 64); if (e == hipSuccess) hw.dv.push_back(*p); return e; };
+	uint8_t *d_nsym = nullptr;
+	int64_t *d_noff = nullptr, *d_poff = nullptr, *d_coff = nullptr, *d_hoff = nullptr, *d_soff = nullptr;
+	int32_t *d_pre = nullptr, *d_node = nullptr, *h_node = nullptr;
+	uint32_t *d_flag = nullptr, *d_cnt = nullptr;
+	SwRaw *d_raw = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	void *d_tmp = nullptr;
+	size_t tmp_bytes = 0;
+	HIPCHK(dalloc((void**)&d_nsym, (size_t)n_nodes));
+	HIPCHK(dalloc((void**)&d_noff, (size_t)(n_query + 1) * 8));
+	HIPCHK(dalloc((void**)&d_poff, (size_t)(n_nodes + 1) * 8));
+	HIPCHK(dalloc((void**)&d_pre, (size_t)n_edges * 4));
+	HIPCHK(dalloc((void**)&d_coff, (size_t)n_query * 8));
+	HIPCHK(dalloc((void**)&d_flag, (size_t)(slice + 1) * 4));
+	HIPCHK(dalloc((void**)&d_cnt, (size_t)(slice + 1) * 4));
+	HIPCHK(dalloc((void**)&d_hoff, (size_t)(slice + 1) * 8));
+	HIPCHK(dalloc((void**)&d_soff, (size_t)(slice + 1) * 8));
+	HIPCHK(dalloc((void**)&d_raw, (size_t)slice * sizeof(SwRaw)));
+	HIPCHK(dalloc((void**)&d_node, (size_t)slice * 4));
+	HIPCHK(dalloc((void**)&d_ctr, 64));
+	HIPCHK(dalloc((void**)&ws.cells, (size_t)max_cells * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.bt, (size_t)max_cells * 12));
+	HIPCHK(dalloc((void**)&ws.ncnt, (size_t)max_nodes * 4));
+	HIPCHK(dalloc((void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
+	HIPCHK(dalloc((void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
+	HIPCHK(dalloc((void**)&ws.heap, (size_t)nb * N * 4));
+	HIPCHK(dalloc((void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(SlZ)));
+	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
+	{
+		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, slice + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
+	}
+	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 8, hipHostMallocDefault)); // (the flags of the slice, then the nodes of its hits)
+	h_node = hw.h_nhit + slice;
+	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
+	HIPCHK(hipHostMalloc((void**)&hw.h_tot, 64, hipHostMallocDefault));
+	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&hw.e[i]));
+	HIPCHK(hipMemcpyAsync(d_nsym, node_sym, (size_t)n_nodes, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_noff, node_off, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_poff, pre_off, (size_t)(n_nodes + 1) * 8, hipMemcpyHostToDevice, h->st));
+	if (n_edges > 0) HIPCHK(hipMemcpyAsync(d_pre, pre, (size_t)n_edges * 4, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_coff, cell_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+	const IdxView ix = view_of(h);
+	Acc7 acc;
+	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	HdOpt o;
+	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = -1, o.k = 0;
+	double ms_dp = 0, ms_bt = 0;
+	int64_t n_hits = 0, n_steps = 0, n_slices = 0;
+	std::vector<rb3gpu_sw_hit_t> hits;
+	std::vector<rb3gpu_pos_t> pairs;
+	int ret = 0;
+	for (size_t ci = 0; ci + 1 < cuts.size() && ret == 0; ++ci, ++n_slices) {
+		const int64_t q0 = cuts[ci], q1 = cuts[ci + 1], nq = q1 - q0;
+		HIPCHK(hipMemsetAsync(d_flag + nq, 0, 4, h->st)); // (the scans are exclusive: their last element is the total)
+		HIPCHK(hipMemsetAsync(d_cnt + nq, 0, 4, h->st));
+		HIPCHK(hipEventRecord(hw.e[0], h->st));
+		hipLaunchKernelGGL(k_swl_fill, dim3((unsigned)std::min(nb, nq)), dim3(64), 0, h->st, ix, acc, (const int64_t*)d_noff, (const uint8_t*)d_nsym, (const int64_t*)d_poff, (const int32_t*)d_pre,
+				n_edges, (const int64_t*)d_coff, q0, q1, o, (int)std::min<int64_t>(opt->end_len, 0x7fffffff), ws, lds_slots, d_flag, d_cnt, d_raw, d_node, d_ctr);
+		HIPCHK(hipEventRecord(hw.e[1], h->st));
+		size_t tb = tmp_bytes + 256;
+		int r = rb3kount_scan(d_tmp, &tb, d_flag, d_hoff, nq + 1, h->st);
+		if (r == 0) tb = tmp_bytes + 256, r = rb3kount_scan(d_tmp, &tb, d_cnt, d_soff, nq + 1, h->st);
+		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		HIPCHK(hipMemcpyAsync(hw.h_tot, d_hoff + nq, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, d_soff + nq, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_nhit, d_flag, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_node, d_node, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_dp += ev_ms(hw.e[0], hw.e[1]);
+		if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a query could not be represented: no record of this slice goes out
+		const int64_t nh = hw.h_tot[0], ns = hw.h_tot[1];
+		if (nh < 0 || nh > nq || ns < 0) return RB3GPU_EINTERNAL;
+		for (int64_t q = 0; q < nq; ++q) {
+			if ((hw.h_nhit[q] != 0) != (h_node[q] >= 0) || hw.h_nhit[q] < 0 || hw.h_nhit[q] > 1 || h_node[q] >= node_off[q0 + q + 1] - node_off[q0 + q]) return RB3GPU_EINTERNAL;
+			hit_node[q0 + q] = h_node[q];
+		}
+		hits.resize((size_t)nh);
+		pairs.clear();
+		if (nh > 0) {
+			if (nh > hw.hit_cap) {
+				const int64_t c = std::max(nh, std::min(slice, 2 * hw.hit_cap));
+				if (hw.d_hits) { HIPCHK(hipFree(hw.d_hits)); hw.d_hits = nullptr; }
+				if (hw.h_hits) { HIPCHK(hipHostFree(hw.h_hits)); hw.h_hits = nullptr; }
+				hw.hit_cap = 0;
+				HIPCHK(hipMalloc(&hw.d_hits, (size_t)c * sizeof(SwRaw)));
+				HIPCHK(hipHostMalloc((void**)&hw.h_hits, (size_t)c * sizeof(SwRaw), hipHostMallocDefault));
+				hw.hit_cap = c;
+			}
+			if (ns > hw.step_cap) {
+				const int64_t c = std::max(ns, 2 * hw.step_cap);
+				if (hw.d_steps) { HIPCHK(hipFree(hw.d_steps)); hw.d_steps = nullptr; }
+				if (hw.h_steps) { HIPCHK(hipHostFree(hw.h_steps)); hw.h_steps = nullptr; }
+				hw.step_cap = 0;
+				HIPCHK(hipMalloc(&hw.d_steps, (size_t)c + 64));
+				HIPCHK(hipHostMalloc((void**)&hw.h_steps, (size_t)c + 64, hipHostMallocDefault));
+				hw.step_cap = c;
+			}
+			HIPCHK(hipEventRecord(hw.e[2], h->st));
+			hipLaunchKernelGGL(k_swl_emit, dim3((unsigned)std::min<int64_t>((nq + 255) / 256, 16384)), dim3(256), 0, h->st, (const int64_t*)d_noff, (const uint8_t*)d_nsym, (const int64_t*)d_coff,
+					q0, (int)N, (const uint32_t*)ws.bt, nq, (const uint32_t*)d_flag, (const SwRaw*)d_raw, (const int32_t*)d_node, (const int64_t*)d_hoff, (const int64_t*)d_soff, hw.d_hits, hw.d_steps, d_ctr);
+			HIPCHK(hipEventRecord(hw.e[3], h->st));
+			HIPCHK(hipMemcpyAsync(hw.h_hits, hw.d_hits, (size_t)nh * sizeof(SwRaw), hipMemcpyDeviceToHost, h->st));
+			if (ns > 0) HIPCHK(hipMemcpyAsync(hw.h_steps, hw.d_steps, (size_t)ns, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_bt += ev_ms(hw.e[2], hw.e[3]);
+			if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL;
+			for (int64_t i = 0; i < nh; ++i) {
+				const SwRaw &x = hw.h_hits[i];
+				rb3gpu_sw_hit_t &y = hits[(size_t)i];
+				y.lo = x.lo, y.hi = x.hi, y.score = x.score, y.qlen = x.qlen, y.rlen = x.rlen, y.n_steps = x.n_steps, y.step_off = x.step_off, y.pos_off = 0, y.n_pos = 0;
+				if (x.n_steps < 0 || x.step_off < 0 || x.step_off + x.n_steps > ns) return RB3GPU_EINTERNAL;
+			}
+			if (with_pos) { // the intervals of the hits, read where k_swl_emit left them (bwa-sw.c:547-556 with one hit per query)
+				for (int64_t r0 = 0; r0 < nh;) {
+					const int64_t lim = std::min(nh - r0, lws.n_cap);
+					lws.h_size.resize((size_t)lim);
+					for (int64_t i = 0; i < lim; ++i) lws.h_size[i] = hits[(size_t)(r0 + i)].hi - hits[(size_t)(r0 + i)].lo;
+					const int64_t nn = loc_slice_end(lws, lws.h_size.data(), 0, lim, loc_cap);
+					lws.h_size.resize((size_t)nn);
+					const int lr = loc_slice(h, lws, nn, (const int64_t*)(hw.d_hits + r0), (int)(sizeof(SwRaw) / 8), 0, loc_cap);
+					if (lr < 0) return lr;
+					const int64_t base = (int64_t)pairs.size(), np = lws.h_off[(size_t)nn];
+					if (np > 0) pairs.insert(pairs.end(), (const rb3gpu_pos_t*)lws.h_pairs, (const rb3gpu_pos_t*)lws.h_pairs + np);
+					for (int64_t i = 0; i < nn; ++i) {
+						rb3gpu_sw_hit_t &y = hits[(size_t)(r0 + i)];
+						y.pos_off = base + lws.h_off[(size_t)i], y.n_pos = std::min<int64_t>(loc_cap, y.hi - y.lo);
+						if (lws.h_off[(size_t)i + 1] - lws.h_off[(size_t)i] < y.n_pos) return RB3GPU_EINTERNAL;
+					}
+					r0 += nn;
+				}
+			}
+		}
+		n_hits += nh, n_steps += ns;
+		ret = cb(ud, q0, nq, hw.h_nhit, hits.data(), hw.h_steps, pairs.data());
+	}
+	if (st) st->sw.ms_total = (now_s() - t0) * 1e3, st->sw.ms_dp = ms_dp, st->sw.ms_backtrack = ms_bt, st->sw.n_ext = (int64_t)hw.h_ctr[0], st->sw.n_hits = n_hits, st->sw.n_steps = n_steps,
+		st->sw.n_tier2 = (int64_t)hw.h_ctr[1], st->sw.n_slices = n_slices, st->n_nodes = n_nodes, st->n_edges = n_edges;
 	if (with_pos) loc_stats(lws, t0, lst);
 	return ret;
 }

@@ -118,6 +118,7 @@ __device__ static HdCell *hd_merge(HdTab &T, const HdCell &c, int &changed, HdCe
 		++T.count, changed = 7;
 		return q;
 	}
+	if (q->pad < c.pad) q->pad = c.pad; // (the symbols of the query consumed, where the caller counts them there: rb3gpu_swlocal.h; 0 otherwise)
 	if (q->E < c.E) q->E = c.E, q->E_pos = c.E_pos, q->fl = (q->fl & ~4u) | (c.fl & 4u), changed |= 2;
 	if (q->F < c.F) q->F = c.F, q->fl = (q->fl & ~8u) | (c.fl & 8u), changed |= 4;
 	if (q->H < c.H) {

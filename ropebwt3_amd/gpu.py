@@ -84,6 +84,15 @@ class SwStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SwlStats(ctypes.Structure):
+    _fields_ = [("sw", SwStats), ("n_nodes", ctypes.c_int64), ("n_edges", ctypes.c_int64)]
+
+    def as_dict(self):
+        d = self.sw.as_dict()
+        d.update(n_nodes=self.n_nodes, n_edges=self.n_edges)
+        return d
+
+
 class HapdivOpt(ctypes.Structure):
     _fields_ = [("n_best", ctypes.c_int32), ("min_sc", ctypes.c_int32), ("match", ctypes.c_int32), ("mis", ctypes.c_int32), ("gap_open", ctypes.c_int32),
                 ("gap_ext", ctypes.c_int32), ("e2e_drop", ctypes.c_int32)]
@@ -243,6 +252,8 @@ SYMBOLS = {
                                      ctypes.POINTER(HapdivStats)]),
     "rb3gpu_sw_e2e": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SwOpt), SW_F, ctypes.c_void_p, ctypes.POINTER(SwStats),
                                      ctypes.POINTER(LocateStats)]),
+    "rb3gpu_sw_local": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.POINTER(SwOpt), SW_F, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SwlStats), ctypes.POINTER(LocateStats)]),
     "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
     "rb3gpu_suffix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SuffixStats)]),
     "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
@@ -950,6 +961,61 @@ class Rb3Gpu:
             locate_stats.update(lst.as_dict())
         return out
 
+    def sw_local(self, queries, n_best=25, min_sc=30, match=1, mis=3, gap_open=5, gap_ext=2, end_len=11, max_pos=None, stats=None, locate_stats=None, dawg=None):
+        """rb3gpu_sw_local: the best local hit of every query (as for mem) as the reference's `sw` finds it in its default mode (end_len: its -k), aligned
+        over the query's DAWG, which the host library builds (host.dawg_batch; dawg: one built before, for the same queries).  Returns a list with one
+        entry per query: the list of its hits, none or one, each a dict as of sw_e2e plus qoff0 (where the hit starts on the query), n_qoff (in how
+        many places of the query the aligned part occurs: the qh tag) and node (the node of the graph it ends at).  qlen is the part of the query it
+        spans.  max_pos as for sw_e2e.  stats receives rb3gpu_swl_stats_t (flat) and dawg_ms, the host's time for the graphs"""
+        import time
+        from . import host
+        qs = [nt6_of(q) for q in queries]
+        off = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            off[1:] = np.cumsum([q.size for q in qs])
+        sym = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        t0 = time.time()
+        g = dawg if dawg is not None else host.dawg_batch(off, sym)
+        dawg_ms = (time.time() - t0) * 1e3
+        node_off = np.ascontiguousarray(g["node_off"], dtype=np.int64)
+        nsym = np.ascontiguousarray(g["sym"], dtype=np.uint8)
+        pre_off = np.ascontiguousarray(g["pre_off"], dtype=np.int64)
+        pre = np.ascontiguousarray(g["pre"], dtype=np.int32)
+        if node_off.size != len(qs) + 1 or (node_off.size and (pre_off.size != int(node_off[-1]) + 1 or nsym.size != int(node_off[-1]) or pre.size != int(pre_off[-1]))):
+            raise ValueError("the graphs do not belong to these queries")
+        hit_node = np.full(max(len(qs), 1), -1, dtype=np.int32)
+        out = [None] * len(qs)
+
+        def cb(_ud, q0, nq, n_hit, hits, steps, pos):
+            nh = np.frombuffer(ctypes.string_at(n_hit, nq * 4), dtype=np.int32)
+            tot = int(nh.sum())
+            hs = np.frombuffer(ctypes.string_at(hits, tot * SW_HIT.itemsize), dtype=SW_HIT) if tot else np.zeros(0, dtype=SW_HIT)
+            at = 0
+            for i in range(nq):
+                mine = []
+                for r in hs[at:at + int(nh[i])]:
+                    st_b = ctypes.string_at(steps + int(r["step_off"]), int(r["n_steps"])) if r["n_steps"] else b""
+                    n_pos = int(r["n_pos"])
+                    pp = np.frombuffer(ctypes.string_at(pos + int(r["pos_off"]) * POS.itemsize, n_pos * POS.itemsize), dtype=POS).copy() if n_pos else np.zeros(0, dtype=POS)
+                    node = int(hit_node[q0 + i])
+                    gi = int(node_off[q0 + i]) + node
+                    mine.append(dict(lo=int(r["lo"]), hi=int(r["hi"]), score=int(r["score"]), qlen=int(r["qlen"]), rlen=int(r["rlen"]), steps=st_b, pos=pp,
+                                     node=node, qoff0=int(g["qoff0"][gi]), n_qoff=int(g["n_qoff"][gi])))
+                out[q0 + i] = mine
+                at += int(nh[i])
+            return 0
+        st, lst = SwlStats(), LocateStats()
+        opt = SwOpt(int(n_best), int(min_sc), int(match), int(mis), int(gap_open), int(gap_ext), -1, int(end_len), -1 if max_pos is None else int(max_pos))
+        self._chk(self._lib.rb3gpu_sw_local(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, node_off.ctypes.data, nsym.ctypes.data if nsym.size else None,
+                                            pre_off.ctypes.data if pre_off.size else None, pre.ctypes.data if pre.size else None, ctypes.byref(opt), SW_F(cb), None,
+                                            hit_node.ctypes.data, ctypes.byref(st), ctypes.byref(lst)), "rb3gpu_sw_local")
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["dawg_ms"] = dawg_ms
+        if locate_stats is not None:
+            locate_stats.update(lst.as_dict())
+        return out
+
     def sync(self):
         self._chk(self._lib.rb3gpu_sync(self._h), "rb3gpu_sync")
 
@@ -1334,7 +1400,7 @@ def sw_rs(steps):
 
 
 def sw_lines(queries, hits, names=None, first_id=0, seq_names=None, lengths=None, unmapped=False, with_rs=False):
-    """the reference's PAF (`sw -e`) for the hits of Rb3Gpu.sw_e2e (bytes).  queries: what was aligned; names as for mem_lines; seq_names and lengths
+    """the reference's PAF (`sw -e`, `sw`) for the hits of Rb3Gpu.sw_e2e or Rb3Gpu.sw_local (bytes).  queries: what was aligned; names as for mem_lines; seq_names and lengths
     (what <index>.len.gz holds) name the positions -- without them a position is written as string number and offset, and a hit without a position
     has stars.  unmapped: the -u lines; with_rs: the rs tag of --seq"""
     out = []
@@ -1352,7 +1418,8 @@ def sw_lines(queries, hits, names=None, first_id=0, seq_names=None, lengths=None
             def stranded(p):
                 clen, x = int(lengths[int(p["sid"]) >> 1]), int(p["pos"])
                 return (clen, x, x + rlen) if int(p["sid"]) & 1 == 0 else (clen, clen - (x + rlen), clen - x)
-            f = [nm, str(query.size), "0", str(h["qlen"])]
+            q0 = h.get("qoff0", 0)         # (a local hit starts where its node does; an end-to-end one at 0)
+            f = [nm, str(query.size), str(q0), str(q0 + h["qlen"])]
             if len(pos) > 0:
                 sid = int(pos[0]["sid"])
                 if seq_names is not None:
@@ -1362,7 +1429,7 @@ def sw_lines(queries, hits, names=None, first_id=0, seq_names=None, lengths=None
                     f += ["+", str(sid), "*", str(int(pos[0]["pos"])), str(int(pos[0]["pos"]) + rlen)]
             else:
                 f += ["*", "*", str(rlen), "*", "*"]
-            f += [str(mlen), str(blen), "0", "AS:i:%d" % h["score"], "qh:i:1", "rh:i:%d" % (h["hi"] - h["lo"]), "cg:Z:" + cg, "cs:Z:" + sw_cs(h["steps"], query)]
+            f += [str(mlen), str(blen), "0", "AS:i:%d" % h["score"], "qh:i:%d" % h.get("n_qoff", 1), "rh:i:%d" % (h["hi"] - h["lo"]), "cg:Z:" + cg, "cs:Z:" + sw_cs(h["steps"], query[q0:])]
             if with_rs:
                 f.append("rs:Z:" + sw_rs(h["steps"]))
             if len(pos) > 1:

@@ -224,3 +224,43 @@ def fmd_bytes_from_words(words, acc):
         if r < 0:
             raise IOError("rb3h_fmdw_dump_file failed")
         return open(f.name, "rb").read()
+
+
+class _Dawg(ctypes.Structure):
+    _fields_ = [("n_node", ctypes.c_int64), ("n_pre", ctypes.c_int64), ("sym", ctypes.c_void_p), ("pre_off", ctypes.c_void_p), ("pre", ctypes.c_void_p),
+                ("qoff0", ctypes.c_void_p), ("n_qoff", ctypes.c_void_p)]
+
+
+def dawg_batch(offsets, symbols):
+    """the graphs `sw --local` aligns over (dawg.c), of the queries symbols[offsets[q], offsets[q + 1]) (nt6 codes), one after another:
+    dict(node_off, sym, pre_off, pre, qoff0, n_qoff) -- query q owns the nodes [node_off[q], node_off[q + 1]), node 0 of a query is its root,
+    the predecessors of node i (numbers within the query, in the order candidates arrive) are pre[pre_off[i], pre_off[i + 1]), its string
+    starts at qoff0[i] of the query and occurs n_qoff[i] times in it"""
+    L = load_library()
+    L.rb3h_dawg_batch.restype = ctypes.c_int
+    L.rb3h_dawg_batch.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.rb3h_dawg_free.restype = None
+    L.rb3h_dawg_free.argtypes = [ctypes.c_void_p]
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+    nq = off.size - 1
+    if nq < 0 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != sym.size:
+        raise ValueError("offsets must start at 0, not decrease, and end at the number of symbols")
+    g = _Dawg()
+    node_off = np.zeros(nq + 1, dtype=np.int64)
+    r = L.rb3h_dawg_batch(nq, off.ctypes.data, sym.ctypes.data if sym.size else None, ctypes.byref(g), node_off.ctypes.data)
+    if r < 0:
+        raise ValueError("rb3h_dawg_batch failed with code %d" % r)
+    try:
+        def arr(p, t, n):
+            return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(t)), shape=(n,)).copy() if n > 0 else np.zeros(0, dtype=t)
+        return dict(node_off=node_off, sym=arr(g.sym, ctypes.c_uint8, g.n_node), pre_off=arr(g.pre_off, ctypes.c_int64, g.n_node + 1),
+                    pre=arr(g.pre, ctypes.c_int32, g.n_pre), qoff0=arr(g.qoff0, ctypes.c_int32, g.n_node), n_qoff=arr(g.n_qoff, ctypes.c_int32, g.n_node))
+    finally:
+        L.rb3h_dawg_free(ctypes.byref(g))
+
+
+def dawg(symbols):
+    """the graph of one query (dawg_batch of it alone)"""
+    s = np.ascontiguousarray(symbols, dtype=np.uint8)
+    return dawg_batch([0, s.size], s)
