@@ -344,6 +344,57 @@ static int load_index(rb3gpu_t *h, const char *fn)
 	return index_upload(h, fn, &x);
 }
 
+/* ---- what the query commands share (their batches come from rb3h_qbatch_read) -------------- */
+
+/* a handle on --gpu `device` with the index `fn` in HBM; x != NULL: the index as index_host_read left it (`mem -p` has looked at it first).  NULL behind the command's one line */
+static rb3gpu_t *open_index(int device, const char *fn, index_host_t *x)
+{
+	rb3gpu_opt_t gopt;
+	rb3gpu_t *h;
+	rb3gpu_opt_init(&gopt);
+	gopt.device = device, gopt.verbose = rb3h_verbose;
+	h = rb3gpu_create(&gopt);
+	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 0; }
+	if ((x ? index_upload(h, fn, x) : load_index(h, fn)) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", fn);
+		rb3gpu_destroy(h);
+		return 0;
+	}
+	return h;
+}
+
+/* rb3_fmi_is_symmetric, fm-index.h:135, with the line of the commands that need both strands */
+static int both_strands(const int64_t acc[7])
+{
+	if ((acc[1] & 1) == 0 && acc[2] - acc[1] == acc[5] - acc[4] && acc[3] - acc[2] == acc[4] - acc[3]) return 1;
+	if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+	return 0;
+}
+
+/* `out` to stdout once it is past 1 MiB, or whatever it holds when forced; -1: the write failed */
+static int out_flush(rb3h_buf_t *out, int force)
+{
+	int r = 0;
+	if (out->l <= (1 << 20) && !force) return 0;
+	if (out->l > 0 && fwrite(out->s, 1, (size_t)out->l, stdout) != (size_t)out->l) r = -1;
+	out->l = 0;
+	return r;
+}
+
+/* the two files beside an index, <fn>.ssa and <fn>.len.gz (rb3_fmi_load_all, fm-index.c:606-640): each NULL if it is not there or is no such file.
+ * Whether they belong to the index, and whether they are needed, is the command's to say */
+static void side_read(const char *fn, rb3h_ssa_t **sa, rb3h_sid_t **sid)
+{
+	const size_t l = strlen(fn);
+	char *t = (char*)malloc(l + 8);
+	*sa = 0, *sid = 0;
+	if (t == 0) return;
+	memcpy(t, fn, l);
+	strcpy(t + l, ".ssa"), *sa = rb3h_ssa_read(t);
+	strcpy(t + l, ".len.gz"), *sid = rb3h_sid_read(t);
+	free(t);
+}
+
 /* ---- batches ----------------------------------------------------------------------------- */
 
 typedef struct {
@@ -1350,7 +1401,6 @@ static int main_kount(int argc, char *argv[])
 {
 	int c, k = 51, min_occ = 100, device = 0, n, i, ret;
 	rb3gpu_t **hs;
-	rb3gpu_opt_t gopt;
 	rb3gpu_kount_stats_t st;
 	kount_out_t o;
 	optind = 1;
@@ -1376,16 +1426,8 @@ static int main_kount(int argc, char *argv[])
 	n = argc - optind;
 	hs = (rb3gpu_t**)calloc((size_t)n, sizeof(*hs));
 	if (hs == 0) return 1;
-	rb3gpu_opt_init(&gopt);
-	gopt.device = device, gopt.verbose = rb3h_verbose;
-	for (i = 0, ret = 0; i < n && ret == 0; ++i) {
-		hs[i] = rb3gpu_create(&gopt);
-		if (hs[i] == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); ret = 1; }
-		else if (load_index(hs[i], argv[optind + i]) < 0) {
-			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind + i]);
-			ret = 1;
-		}
-	}
+	for (i = 0, ret = 0; i < n && ret == 0; ++i)
+		if ((hs[i] = open_index(device, argv[optind + i], 0)) == 0) ret = 1;
 	if (ret == 0) {
 		if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded %d index(es)\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), n);
 		o.fp = stdout, o.l = 0, o.err = 0, o.t_fmt = 0;
@@ -1417,7 +1459,6 @@ static int main_kount(int argc, char *argv[])
  * through <index>.ssa, named through <index>.len.gz (rb3gpu_mem_pos, rb3h_mem_format_pos).  Differences, each a refusal with exit status 1:
  * --old-mem, -l or -c below 1, the options of `sw` and `hapdiv`; and every refusal exits 1 (the reference exits 0 on some). */
 typedef struct {
-	FILE *fp;
 	rb3h_buf_t out;
 	int mode, err;
 	int64_t min_gap, id0, n_query, next_q, pend_q, n_pend, m_pend;
@@ -1430,12 +1471,6 @@ typedef struct {
 	rb3h_pos_t *pend_pos;
 } mem_out_t;
 
-static void mem_flush(mem_out_t *o)
-{
-	if (o->out.l > 0 && fwrite(o->out.s, 1, (size_t)o->out.l, o->fp) != (size_t)o->out.l) o->err = 1;
-	o->out.l = 0;
-}
-
 /* the lines of the queries [next_q, q) (the matches collected for pend_q among them) */
 static void mem_advance(mem_out_t *o, int64_t q)
 {
@@ -1446,7 +1481,7 @@ static void mem_advance(mem_out_t *o, int64_t q)
 			if (rb3h_mem_format_pos(&o->out, o->name_off[i] >= 0 ? o->names + o->name_off[i] : 0, o->id0 + i, n, o->pend, o->pend_off, o->pend_pos, o->sid) < 0) o->err = 1;
 		} else if (rb3h_mem_format(&o->out, o->mode, o->min_gap, o->name_off[i] >= 0 ? o->names + o->name_off[i] : 0, o->id0 + i, o->off[i + 1] - o->off[i], n, o->pend) < 0) o->err = 1;
 		if (n > 0) o->n_pend = 0;
-		if (o->out.l > (1 << 20)) mem_flush(o);
+		if (out_flush(&o->out, 0) < 0) o->err = 1;
 	}
 }
 
@@ -1518,11 +1553,9 @@ static int main_mem(int argc, char *argv[])
 	int64_t n_steps = 0, n_walkers = 0, n_records = 0, n_slices = 0, n_batches = 0;
 	double ms_walk = 0, ms_engine = 0;
 	rb3gpu_t *h;
-	rb3gpu_opt_t gopt;
 	int64_t acc[7];
 	mem_out_t o;
-	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0};
-	int64_t *off = 0, *name_off = 0, m_q = 0;
+	rb3h_qbatch_t b;
 	_Static_assert(sizeof(rb3h_mem_rec_t) == sizeof(rb3gpu_mem_rec_t), "one record layout on both sides");
 	_Static_assert(sizeof(rb3h_pos_t) == sizeof(rb3gpu_pos_t), "one position layout on both sides");
 	optind = 1;
@@ -1562,16 +1595,9 @@ static int main_mem(int argc, char *argv[])
 	memset(&ih, 0, sizeof(ih));
 	if (max_pos > 0) { /* the two files beside the index (rb3_fmi_load_all, fm-index.c:606-640), read and held against the index before anything is asked of a
 	                    * device: files of another index are no files (fm-index.c:615, 633), and the refusal is the only line (search.c:555-559: before the check for both strands) */
-		const size_t l = strlen(argv[optind]);
-		char *fn = (char*)malloc(l + 8);
 		int64_t m, n_sym;
 		int ms;
-		if (fn) {
-			memcpy(fn, argv[optind], l);
-			strcpy(fn + l, ".ssa"), sa = rb3h_ssa_read(fn);
-			strcpy(fn + l, ".len.gz"), sid = sa ? rb3h_sid_read(fn) : 0;
-			free(fn);
-		}
+		side_read(argv[optind], &sa, &sid);
 		if (sa == 0 || sid == 0) goto no_side;
 		if (index_host_read(argv[optind], &ih) < 0) {
 			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
@@ -1582,16 +1608,8 @@ static int main_mem(int argc, char *argv[])
 		for (ms = 1; (1LL << ms) < m; ++ms) {} /* ssa.c:63-64: what a sampled suffix array of THIS index looks like */
 		if (sa->m != m || sid->n_seq * 2 != m || sa->ms != ms || sa->ss > 40 || sa->n_ssa != (n_sym - m + (1LL << sa->ss) - 1) >> sa->ss) goto no_side;
 	}
-	rb3gpu_opt_init(&gopt);
-	gopt.device = device, gopt.verbose = rb3h_verbose;
-	h = rb3gpu_create(&gopt);
-	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid); index_host_free(&ih); return 1; }
-	if ((max_pos > 0 ? index_upload(h, argv[optind], &ih) : load_index(h, argv[optind])) < 0) {
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
-		rb3gpu_destroy(h);
-		rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid);
-		return 1;
-	}
+	h = open_index(device, argv[optind], max_pos > 0 ? &ih : 0);
+	if (h == 0) { rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid); index_host_free(&ih); return 1; }
 	rb3gpu_get_acc(h, acc);
 	if (max_pos > 0) { /* (the sample rate and the width of the string field must be those of this index as well) */
 		if (sa->m != acc[1] || sid->n_seq * 2 != acc[1] || rb3gpu_ssa_set(h, sa->ss, sa->ms, sa->m, sa->n_ssa, sa->r2i, sa->ssa) != 0) {
@@ -1600,61 +1618,40 @@ static int main_mem(int argc, char *argv[])
 		}
 		rb3h_ssa_destroy(sa), sa = 0; /* (it lives on the device from here on) */
 	}
-	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+	if (!both_strands(acc)) {
 		rb3gpu_destroy(h);
 		rb3h_sid_destroy(sid);
 		return 1;
 	}
 	if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded the index\n", __func__, rb3h_realtime(), rb3h_percent_cpu());
 	memset(&o, 0, sizeof(o));
-	o.fp = stdout, o.mode = mode, o.min_gap = min_gap;
+	memset(&b, 0, sizeof(b));
+	o.mode = mode, o.min_gap = min_gap;
 	if (max_pos > 0 && mode == RB3H_MEM_LINES) o.sid = sid; /* (--cov -p needs the files and prints no positions, search.c:279) */
 	for (j = optind + 1; j < argc && ret == 0; ++j) {
 		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
-		int eof = 0;
 		if (fp == 0) {
 			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
 			ret = 1;
 			break;
 		}
-		while (!eof && ret == 0) { /* a batch: records until their symbols reach -K (search.c:366-378) */
-			int64_t n_q = 0, l;
-			const uint8_t *s;
-			const char *name;
-			sym.l = names.l = 0;
-			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
-				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
-				if (n_q + 2 > m_q) {
-					m_q = m_q ? m_q * 2 : 1024;
-					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
-				}
-				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
-				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
-				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
-				if (l > 0x7fffffffLL) { fprintf(stderr, "ERROR: a query of more than 2^31 - 1 symbols\n"); ret = 1; break; }
-				if (n_q == 0) off[0] = 0;
-				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
-				rb3h_char2nt6(l, sym.s + sym.l); /* search.c:91 */
-				sym.l += l, off[++n_q] = sym.l;
-				name_off[n_q - 1] = name ? names.l : -1;
-				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
-				if (sym.l >= batch_size || n_q >= 0x7fffffffLL) break;
-			}
-			if (l < 0) eof = 1;
-			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
-			if (n_q > 0 && ret == 0) {
+		for (b.eof = 0; !b.eof && ret == 0;) { /* a batch: records until their symbols reach -K (search.c:366-378) */
+			const int64_t n_q = rb3h_qbatch_read(fp, &b, batch_size, 0x7fffffffLL, 0x7fffffffLL);
+			if (n_q == -1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+			if (n_q == -2) { fprintf(stderr, "ERROR: a query of more than 2^31 - 1 symbols\n"); ret = 1; }
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && b.eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q > 0) {
 				rb3gpu_mem_stats_t st;
 				int r;
-				o.off = off, o.name_off = name_off, o.names = (const char*)names.s, o.id0 = id, o.n_query = n_q, o.next_q = 0, o.n_pend = 0;
+				o.off = b.off, o.name_off = b.name_off, o.names = (const char*)b.names.s, o.id0 = id, o.n_query = n_q, o.next_q = 0, o.n_pend = 0;
 				if (o.sid) {
 					rb3gpu_locate_stats_t ls;
-					r = rb3gpu_mem_pos(h, n_q, off, sym.s, min_len, min_occ, chunk, max_pos, mem_sink_pos, &o, &st, &ls);
+					r = rb3gpu_mem_pos(h, n_q, b.off, b.sym.s, min_len, min_occ, chunk, max_pos, mem_sink_pos, &o, &st, &ls);
 					lsum.ms_locate += ls.ms_locate, lsum.n_pops += ls.n_pops, lsum.n_intervals += ls.n_intervals, lsum.n_tier2 += ls.n_tier2, lsum.n_pairs += ls.n_pairs;
 					lsum.max_heap = lsum.max_heap > ls.max_heap ? lsum.max_heap : ls.max_heap;
-				} else r = rb3gpu_mem(h, n_q, off, sym.s, min_len, min_occ, chunk, mem_sink, &o, &st);
+				} else r = rb3gpu_mem(h, n_q, b.off, b.sym.s, min_len, min_occ, chunk, mem_sink, &o, &st);
 				if (r == 0 && !o.err) mem_advance(&o, n_q);
-				mem_flush(&o);
+				if (out_flush(&o.out, 1) < 0) o.err = 1;
 				if (r != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to find the matches: %s\n", rb3gpu_strerror(r)); ret = 1; }
 				else if (o.err) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
 				id += n_q, ++n_batches;
@@ -1671,7 +1668,8 @@ static int main_mem(int argc, char *argv[])
 	if (rb3h_verbose >= 3 && ret == 0 && o.sid)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld positions of %lld matches: %lld heap pops, %lld matches with a heap in global memory, largest heap %lld; locate kernels %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)lsum.n_pairs, (long long)lsum.n_intervals, (long long)lsum.n_pops, (long long)lsum.n_tier2, (long long)lsum.max_heap, lsum.ms_locate);
-	free(o.out.s); free(o.pend); free(o.pend_off); free(o.pend_pos); free(sym.s); free(names.s); free(off); free(name_off);
+	free(o.out.s); free(o.pend); free(o.pend_off); free(o.pend_pos);
+	rb3h_qbatch_free(&b);
 	rb3gpu_destroy(h);
 	rb3h_sid_destroy(sid);
 	return ret;
@@ -1701,11 +1699,12 @@ static int main_suffix(int argc, char *argv[])
 	int64_t id = 0, n_steps = 0, n_slices = 0, n_batches = 0, n_sym = 0;
 	double ms_walk = 0, ms_engine = 0;
 	rb3gpu_t *h;
-	rb3gpu_opt_t gopt;
-	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0}, out = {0, 0, 0};
-	int64_t *off = 0, *name_off = 0, m_q = 0, m_rec = 0;
+	rb3h_buf_t out = {0, 0, 0};
+	rb3h_qbatch_t b;
+	int64_t m_rec = 0;
 	rb3gpu_suffix_rec_t *rec = 0;
 	optind = 1, opterr = 0;
+	memset(&b, 0, sizeof(b));
 	while ((c = getopt_long(argc, argv, "L", walk_long_opts, 0)) >= 0) {
 		if (c == 'L') is_line = 1;
 		else if (c == 301) device = atoi(optarg);
@@ -1717,50 +1716,22 @@ static int main_suffix(int argc, char *argv[])
 		fprintf(stderr, "  -L        one sequence per line in the input\n");
 		return 0;
 	}
-	rb3gpu_opt_init(&gopt);
-	gopt.device = device, gopt.verbose = rb3h_verbose;
-	h = rb3gpu_create(&gopt);
-	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
-	if (load_index(h, argv[optind]) < 0) {
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
-		rb3gpu_destroy(h);
-		return 1;
-	}
+	if ((h = open_index(device, argv[optind], 0)) == 0) return 1;
 	if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] loaded the index\n", __func__, rb3h_realtime(), rb3h_percent_cpu());
 	for (j = optind + 1; j < argc && ret == 0; ++j) {
 		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
-		int eof = 0;
 		if (fp == 0) {
 			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
 			ret = 1;
 			break;
 		}
-		while (!eof && ret == 0) { /* a batch: records until their symbols reach SUFFIX_BATCH */
-			int64_t n_q = 0, l, i;
-			const uint8_t *s;
-			const char *name;
-			sym.l = names.l = 0;
-			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
-				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
-				if (n_q + 2 > m_q) {
-					m_q = m_q ? m_q * 2 : 1024;
-					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
-				}
-				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
-				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
-				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
-				if (l > 0x7fffffffLL) { fprintf(stderr, "ERROR: a query of more than 2^31 - 1 symbols\n"); ret = 1; break; }
-				if (n_q == 0) off[0] = 0;
-				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
-				rb3h_char2nt6(l, sym.s + sym.l); /* main.c:200-202: the nt6 table, anything from 128 on is 5 */
-				sym.l += l, off[++n_q] = sym.l;
-				name_off[n_q - 1] = name ? names.l : -1;
-				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
-				if (sym.l >= SUFFIX_BATCH) break;
-			}
-			if (l < 0) eof = 1;
-			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
-			if (n_q > 0 && ret == 0) {
+		for (b.eof = 0; !b.eof && ret == 0;) { /* a batch: records until their symbols reach SUFFIX_BATCH, as nt6 codes (main.c:200-202: anything from 128 on is 5) */
+			const int64_t n_q = rb3h_qbatch_read(fp, &b, SUFFIX_BATCH, INT64_MAX, 0x7fffffffLL), *off = b.off, *name_off = b.name_off;
+			int64_t i;
+			if (n_q == -1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+			if (n_q == -2) { fprintf(stderr, "ERROR: a query of more than 2^31 - 1 symbols\n"); ret = 1; }
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && b.eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q > 0) {
 				rb3gpu_suffix_stats_t st;
 				int r, werr = 0;
 				if (n_q > m_rec) {
@@ -1768,19 +1739,16 @@ static int main_suffix(int argc, char *argv[])
 					rec = (rb3gpu_suffix_rec_t*)realloc(rec, (size_t)m_rec * sizeof(*rec));
 					if (rec == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
 				}
-				r = rb3gpu_suffix(h, n_q, off, sym.s, rec, &st);
+				r = rb3gpu_suffix(h, n_q, off, b.sym.s, rec, &st);
 				if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to find the suffixes: %s\n", rb3gpu_strerror(r)); ret = 1; break; }
 				for (i = 0; i < n_q && !werr; ++i) { /* name, start, length, occurrences: a line of `mem` (main.c:207-209; seq<N> counts every record) */
 					rb3h_mem_rec_t t;
 					t.query = i, t.x0 = 0, t.size = rec[i].size, t.st = (int32_t)rec[i].start, t.en = (int32_t)(off[i + 1] - off[i]);
-					if (rb3h_mem_format(&out, RB3H_MEM_LINES, 0, name_off[i] >= 0 ? (const char*)names.s + name_off[i] : 0, id + i, off[i + 1] - off[i], 1, &t) < 0) werr = 1;
-					if (out.l > (1 << 20) || i + 1 == n_q) {
-						if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) werr = 1;
-						out.l = 0;
-					}
+					if (rb3h_mem_format(&out, RB3H_MEM_LINES, 0, name_off[i] >= 0 ? (const char*)b.names.s + name_off[i] : 0, id + i, off[i + 1] - off[i], 1, &t) < 0) werr = 1;
+					if (out_flush(&out, i + 1 == n_q) < 0) werr = 1;
 				}
 				if (werr) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
-				id += n_q, ++n_batches, n_sym += sym.l;
+				id += n_q, ++n_batches, n_sym += b.sym.l;
 				n_steps += st.n_steps, n_slices += st.n_slices, ms_walk += st.ms_walk, ms_engine += st.ms_total;
 				if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] processed %lld sequences\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_q);
 			}
@@ -1791,7 +1759,8 @@ static int main_suffix(int argc, char *argv[])
 	if (rb3h_verbose >= 3 && ret == 0)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries of %lld symbols in %lld batch(es) and %lld slice(s): %lld extensions; %.3f ms in the engine, walk kernel %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_sym, (long long)n_batches, (long long)n_slices, (long long)n_steps, ms_engine, ms_walk);
-	free(out.s); free(sym.s); free(names.s); free(off); free(name_off); free(rec);
+	free(out.s); free(rec);
+	rb3h_qbatch_free(&b);
 	rb3gpu_destroy(h);
 	return ret;
 }
@@ -1820,10 +1789,7 @@ static int get_sink(void *ud, int64_t i0, int64_t n, const int64_t *end_row, con
 		for (k = 0; k < l; ++k) *p++ = (uint8_t)"$ACGTN"[symbols[off[i] + k] < 6 ? symbols[off[i] + k] : 5];
 		*p++ = '\n';
 		o->out.l = p - o->out.s;
-		if (o->out.l > (1 << 20)) {
-			if (fwrite(o->out.s, 1, (size_t)o->out.l, stdout) != (size_t)o->out.l) o->err = 1;
-			o->out.l = 0;
-		}
+		if (out_flush(&o->out, 0) < 0) o->err = 1;
 	}
 	return o->err ? -1 : 0;
 }
@@ -1833,7 +1799,6 @@ static int main_get(int argc, char *argv[])
 	int c, device = 0, ret = 0, i;
 	int64_t *rows, n = 0;
 	rb3gpu_t *h;
-	rb3gpu_opt_t gopt;
 	rb3gpu_retrieve_stats_t st;
 	get_out_t o;
 	optind = 1, opterr = 0;
@@ -1845,22 +1810,14 @@ static int main_get(int argc, char *argv[])
 		fprintf(stdout, "Usage: ropebwt3-amd get <idx.fmr> <int> [...]\n");
 		return 0;
 	}
-	rb3gpu_opt_init(&gopt);
-	gopt.device = device, gopt.verbose = rb3h_verbose;
-	h = rb3gpu_create(&gopt);
-	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
-	if (load_index(h, argv[optind]) < 0) {
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
-		rb3gpu_destroy(h);
-		return 1;
-	}
+	if ((h = open_index(device, argv[optind], 0)) == 0) return 1;
 	rows = (int64_t*)malloc((size_t)(argc - optind) * 8);
 	if (rows == 0) { fprintf(stderr, "ERROR: out of memory\n"); rb3gpu_destroy(h); return 1; }
 	for (i = optind + 1; i < argc; ++i) rows[n++] = atol(argv[i]); /* main.c:155: `abc` is row 0 */
 	memset(&o, 0, sizeof(o));
 	o.rows = rows;
 	c = rb3gpu_retrieve(h, n, rows, get_sink, &o, &st);
-	if (c == 0 && !o.err && o.out.l > 0 && fwrite(o.out.s, 1, (size_t)o.out.l, stdout) != (size_t)o.out.l) o.err = 1;
+	if (c == 0 && !o.err && out_flush(&o.out, 1) < 0) o.err = 1;
 	if (c != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to retrieve the sequences: %s\n", rb3gpu_strerror(c)); ret = 1; }
 	else if (o.err || fflush(stdout) != 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
 	if (rb3h_verbose >= 3 && ret == 0)
@@ -1901,13 +1858,14 @@ static int main_hapdiv(int argc, char *argv[])
 	double ms_dp = 0, ms_engine = 0;
 	rb3gpu_hapdiv_opt_t ho = { 25, 30, 1, 3, 5, 2, -1 };
 	rb3gpu_t *h;
-	rb3gpu_opt_t gopt;
 	int64_t acc[7];
-	rb3h_buf_t sym = {0, 0, 0}, names = {0, 0, 0}, out = {0, 0, 0};
-	int64_t *off = 0, *name_off = 0, m_q = 0, *win = 0, m_win = 0;
+	rb3h_buf_t out = {0, 0, 0};
+	rb3h_qbatch_t b;
+	int64_t *win = 0, m_win = 0;
 	hapdiv_out_t o = { 0, 0 };
 	_Static_assert(sizeof(rb3gpu_hapdiv_rec_t) == 36, "nine numbers per window");
 	optind = 1;
+	memset(&b, 0, sizeof(b));
 	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", hapdiv_long_opts, 0)) >= 0) {
 		if (c == 'L') is_line = 1;
 		else if (c == 'a') k = atoi(optarg);
@@ -1947,54 +1905,25 @@ static int main_hapdiv(int argc, char *argv[])
 	if (w < 1) { fprintf(stderr, "ERROR: the step size (-w) must be at least 1\n"); return 1; }
 	if (ho.n_best < 1) { fprintf(stderr, "ERROR: the number of hits kept per row (-N) must be at least 1\n"); return 1; }
 	if (k > 0x7ffffffeLL || (k + 1) * (int64_t)ho.n_best >= 0xFFFFFFFFLL || ho.n_best >= (1 << 24)) { fprintf(stderr, "ERROR: -a times -N is too large\n"); return 1; }
-	rb3gpu_opt_init(&gopt);
-	gopt.device = device, gopt.verbose = rb3h_verbose;
-	h = rb3gpu_create(&gopt);
-	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
-	if (load_index(h, argv[optind]) < 0) {
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
-		rb3gpu_destroy(h);
-		return 1;
-	}
+	if ((h = open_index(device, argv[optind], 0)) == 0) return 1;
 	rb3gpu_get_acc(h, acc);
-	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+	if (!both_strands(acc)) {
 		rb3gpu_destroy(h);
 		return 1;
 	}
 	for (j = optind + 1; j < argc && ret == 0; ++j) {
 		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
-		int eof = 0;
 		if (fp == 0) {
 			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
 			ret = 1;
 			break;
 		}
-		while (!eof && ret == 0) { /* a batch: whole records until their symbols reach -K (search.c:366-378) */
-			int64_t n_q = 0, l, n_win = 0, q, x;
-			const uint8_t *s;
-			const char *name;
-			sym.l = names.l = 0;
-			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
-				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
-				if (n_q + 2 > m_q) {
-					m_q = m_q ? m_q * 2 : 1024;
-					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
-				}
-				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
-				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
-				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
-				if (n_q == 0) off[0] = 0;
-				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
-				rb3h_char2nt6(l, sym.s + sym.l);
-				sym.l += l, off[++n_q] = sym.l;
-				name_off[n_q - 1] = name ? names.l : -1;
-				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
-				if (sym.l >= batch_size || n_q >= 0x7fffffffLL) break;
-			}
-			if (l < 0) eof = 1;
-			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
-			if (n_q == 0 || ret != 0) continue;
+		for (b.eof = 0; !b.eof && ret == 0;) { /* a batch: whole records until their symbols reach -K (search.c:366-378) */
+			const int64_t n_q = rb3h_qbatch_read(fp, &b, batch_size, 0x7fffffffLL, INT64_MAX), *off = b.off, *name_off = b.name_off;
+			int64_t n_win = 0, q, x;
+			if (n_q < 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && b.eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q <= 0) continue;
 			for (q = 0; q < n_q; ++q) {
 				const int64_t len = off[q + 1] - off[q];
 				n_win += len < k ? 0 : (len - k) / w + 1;
@@ -2010,16 +1939,13 @@ static int main_hapdiv(int argc, char *argv[])
 			if (n_win > 0) {
 				rb3gpu_hapdiv_stats_t st;
 				int64_t at = 0;
-				const int r = rb3gpu_hapdiv(h, n_win, win, sym.s, (int32_t)k, &ho, hapdiv_sink, &o, &st);
+				const int r = rb3gpu_hapdiv(h, n_win, win, b.sym.s, (int32_t)k, &ho, hapdiv_sink, &o, &st);
 				if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to align the windows: %s\n", rb3gpu_strerror(r)); ret = 1; break; }
 				for (q = 0; q < n_q && ret == 0; ++q) {
 					const int64_t len = off[q + 1] - off[q], nw = len < k ? 0 : (len - k) / w + 1;
-					if (nw > 0 && rb3h_hapdiv_format(&out, name_off[q] >= 0 ? (const char*)names.s + name_off[q] : 0, id + q, k, w, nw, o.r + 9 * at) < 0) ret = 1;
+					if (nw > 0 && rb3h_hapdiv_format(&out, name_off[q] >= 0 ? (const char*)b.names.s + name_off[q] : 0, id + q, k, w, nw, o.r + 9 * at) < 0) ret = 1;
 					at += nw;
-					if (out.l > (1 << 20) || q == n_q - 1) {
-						if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) ret = 1;
-						out.l = 0;
-					}
+					if (out_flush(&out, q == n_q - 1) < 0) ret = 1;
 				}
 				if (ret) { fprintf(stderr, "ERROR: failed to write the output\n"); break; }
 				n_win_all += n_win, n_ext += st.n_ext, n_tier2 += st.n_tier2, n_slices += st.n_slices, ms_dp += st.ms_dp, ms_engine += st.ms_total;
@@ -2033,7 +1959,8 @@ static int main_hapdiv(int argc, char *argv[])
 	if (rb3h_verbose >= 3 && ret == 0)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld windows in %lld slice(s), %lld extensions, %lld windows with a table in global memory; %.3f ms in the engine, the DP kernel %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_win_all, (long long)n_slices, (long long)n_ext, (long long)n_tier2, ms_engine, ms_dp);
-	free(out.s); free(o.r); free(win); free(sym.s); free(names.s); free(off); free(name_off);
+	free(out.s); free(o.r); free(win);
+	rb3h_qbatch_free(&b);
 	rb3gpu_destroy(h);
 	return ret;
 }
@@ -2099,21 +2026,21 @@ static int main_sw(int argc, char *argv[])
 	int c, is_line = 0, device = 0, ret = 0, j, e2e = 0, local = 0, no_ssa = 0, write_all = 0, both = 0, unmapped = 0, with_rs = 0, max_pos = 0, min_mem_len = 0;
 	int64_t batch_size = 100000000, id = 0, max_all_out = 0, n_ext = 0, n_hits = 0, n_tier2 = 0, n_slices = 0, n_batches = 0;
 	double ms_dp = 0, ms_bt = 0, ms_engine = 0, ms_locate = 0, ms_dawg = 0;
-	int64_t n_nodes = 0, n_edges = 0, *node_off = 0, m_node_off = 0;
+	int64_t n_nodes = 0, n_edges = 0, *node_off = 0, m_node_off = 0, m_hit = 0, max_len;
 	int32_t *hit_node = 0;
 	rb3gpu_sw_opt_t so = { 25, 30, 1, 3, 5, 2, -1, 11, 0 };
 	rb3gpu_t *h;
-	rb3gpu_opt_t gopt;
 	rb3h_ssa_t *sa = 0;
 	rb3h_sid_t *sid = 0;
 	int have_ssa = 0;
 	int64_t acc[7];
-	rb3h_buf_t sym = {0, 0, 0}, rev = {0, 0, 0}, names = {0, 0, 0}, out = {0, 0, 0};
-	int64_t *off = 0, *name_off = 0, m_q = 0;
+	rb3h_buf_t rev = {0, 0, 0}, out = {0, 0, 0};
+	rb3h_qbatch_t b;
 	sw_out_t o[2];
 	_Static_assert(sizeof(rb3h_sw_hit_t) == sizeof(rb3gpu_sw_hit_t), "one hit layout on both sides");
 	_Static_assert(sizeof(rb3h_pos_t) == sizeof(rb3gpu_pos_t), "one position layout on both sides");
 	memset(o, 0, sizeof(o));
+	memset(&b, 0, sizeof(b));
 	optind = 1;
 	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", sw_long_opts, 0)) >= 0) { /* the order of -e, -k, -g matters as in search.c:452-492 */
 		if (c == 'L') is_line = 1;
@@ -2172,25 +2099,10 @@ static int main_sw(int argc, char *argv[])
 	if (so.end_len < 1) { fprintf(stderr, "ERROR: the end length (-k) must be at least 1\n"); return 1; }
 	if (so.n_best >= (1 << 24)) { fprintf(stderr, "ERROR: -N is too large\n"); return 1; }
 	if (min_mem_len > 0 && min_mem_len > so.end_len) { fprintf(stderr, "ERROR: -j above the end length asks for the MEM pre-filter, which is not implemented\n"); return 1; }
-	rb3gpu_opt_init(&gopt);
-	gopt.device = device, gopt.verbose = rb3h_verbose;
-	h = rb3gpu_create(&gopt);
-	if (h == 0) { fprintf(stderr, "ERROR: no usable MI355X/HIP device; there is no CPU fallback\n"); return 1; }
-	if (load_index(h, argv[optind]) < 0) {
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
-		rb3gpu_destroy(h);
-		return 1;
-	}
+	if ((h = open_index(device, argv[optind], 0)) == 0) return 1;
 	rb3gpu_get_acc(h, acc);
 	if (!no_ssa) { /* the two files beside the index, each only if it is there and belongs to this index */
-		const size_t l = strlen(argv[optind]);
-		char *fn = (char*)malloc(l + 8);
-		if (fn) {
-			memcpy(fn, argv[optind], l);
-			strcpy(fn + l, ".ssa"), sa = rb3h_ssa_read(fn);
-			strcpy(fn + l, ".len.gz"), sid = rb3h_sid_read(fn);
-			free(fn);
-		}
+		side_read(argv[optind], &sa, &sid);
 		if (sa && (sa->m != acc[1] || rb3gpu_ssa_set(h, sa->ss, sa->ms, sa->m, sa->n_ssa, sa->r2i, sa->ssa) != 0)) {
 			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: number of sequences do not match between BWT and sampled suffix array\n");
 		} else if (sa) have_ssa = 1;
@@ -2206,49 +2118,37 @@ static int main_sw(int argc, char *argv[])
 		rb3h_sid_destroy(sid);
 		return 1;
 	}
-	if ((acc[1] & 1) != 0 || acc[2] - acc[1] != acc[5] - acc[4] || acc[3] - acc[2] != acc[4] - acc[3]) { /* rb3_fmi_is_symmetric, fm-index.h:135 */
-		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: BWT doesn't contain both strands\n");
+	if (!both_strands(acc)) {
 		rb3gpu_destroy(h);
 		rb3h_sid_destroy(sid);
 		return 1;
 	}
 	so.max_pos = have_ssa ? max_pos : -1;
+	/* the longest query: a cell of the backtrack matrix is named by row * n_best + column in 32 bits (two rows a symbol with --local), so with c = n_best * (local ? 2 : 1),
+	 * 1 <= c < 2^25, a query of l symbols is refused when l > 0x7ffffffe or (l + 1) * c >= 0xFFFFFFFF.  (l + 1) * c < 0xFFFFFFFF is (l + 1) * c <= 0xFFFFFFFE,
+	 * which for integers is l + 1 <= 0xFFFFFFFE / c rounded down: the largest l that passes is the smaller of 0x7ffffffe and 0xFFFFFFFE / c - 1 (127 at least) */
+	max_len = 0xFFFFFFFELL / (so.n_best * (local ? 2 : 1)) - 1;
+	if (max_len > 0x7ffffffeLL) max_len = 0x7ffffffeLL;
 	if (write_all) fputs("CC\tQS  queryName  queryLen  numHap\nCC\tQH  refCount   score     editDist   cs   strand   nOut   totAln\nCC\n", stdout);
 	for (j = optind + 1; j < argc && ret == 0; ++j) {
 		rb3h_seqio_t *fp = rb3h_seq_open(argv[j], is_line);
-		int eof = 0;
 		if (fp == 0) {
 			if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load the sequence file '%s'\n", argv[j]);
 			break; /* (the reference stops here and exits 0, search.c:570-576) */
 		}
-		while (!eof && ret == 0) { /* a batch: whole records until their symbols reach -K (search.c:366-378) */
-			int64_t n_q = 0, l, q, at[2] = { 0, 0 };
-			const uint8_t *s;
-			const char *name;
+		for (b.eof = 0; !b.eof && ret == 0;) { /* a batch: whole records until their symbols reach -K (search.c:366-378) */
+			const int64_t n_q = rb3h_qbatch_read(fp, &b, batch_size, 0x7fffffffLL, max_len), *off = b.off, *name_off = b.name_off;
+			const rb3h_buf_t sym = b.sym, names = b.names;
+			int64_t q, at[2] = { 0, 0 };
 			int pass;
-			sym.l = names.l = 0;
-			while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
-				const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
-				if (n_q + 2 > m_q) {
-					m_q = m_q ? m_q * 2 : 1024;
-					off = (int64_t*)realloc(off, (size_t)m_q * 8), name_off = (int64_t*)realloc(name_off, (size_t)m_q * 8);
-					o[0].n_hit = (int32_t*)realloc(o[0].n_hit, (size_t)m_q * 4), o[1].n_hit = (int32_t*)realloc(o[1].n_hit, (size_t)m_q * 4);
-				}
-				if (sym.l + l + 1 > sym.m) sym.m = (sym.l + l + 1) * 2, sym.s = (uint8_t*)realloc(sym.s, (size_t)sym.m);
-				if (names.l + l_name + 1 > names.m) names.m = (names.l + l_name + 1) * 2, names.s = (uint8_t*)realloc(names.s, (size_t)names.m);
-				if (off == 0 || name_off == 0 || sym.s == 0 || names.s == 0 || o[0].n_hit == 0 || o[1].n_hit == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
-				if (l > 0x7ffffffeLL || (l + 1) * (int64_t)so.n_best * (local ? 2 : 1) >= 0xFFFFFFFFLL) { fprintf(stderr, "ERROR: a query times -N is too large\n"); ret = 1; break; }
-				if (n_q == 0) off[0] = 0;
-				if (l > 0) memcpy(sym.s + sym.l, s, (size_t)l);
-				rb3h_char2nt6(l, sym.s + sym.l); /* search.c:91 */
-				sym.l += l, off[++n_q] = sym.l;
-				name_off[n_q - 1] = name ? names.l : -1;
-				if (name) memcpy(names.s + names.l, name, (size_t)l_name), names.l += l_name;
-				if (sym.l >= batch_size || n_q >= 0x7fffffffLL) break;
+			if (n_q > m_hit) {
+				m_hit = n_q + (n_q >> 1) + 1024;
+				o[0].n_hit = (int32_t*)realloc(o[0].n_hit, (size_t)m_hit * 4), o[1].n_hit = (int32_t*)realloc(o[1].n_hit, (size_t)m_hit * 4);
 			}
-			if (l < 0) eof = 1;
-			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
-			if (n_q == 0 || ret != 0) continue;
+			if (n_q == -1 || (n_q > 0 && (o[0].n_hit == 0 || o[1].n_hit == 0))) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+			if (n_q == -2) { fprintf(stderr, "ERROR: a query times -N is too large\n"); ret = 1; }
+			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && b.eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
+			if (n_q <= 0 || ret != 0) continue;
 			if (local) { /* the graphs of the batch on the host, the nodes as rows on the device, one hit per query at most with its place on the query */
 				rb3h_dawg_t dg;
 				rb3gpu_swl_stats_t st;
@@ -2277,10 +2177,7 @@ static int main_sw(int argc, char *argv[])
 					if (r == -2) { fprintf(stderr, "ERROR: a position names a sequence that the name list does not have\n"); ret = 1; break; }
 					if (r == -3) { fprintf(stderr, "ERROR: the GPU engine returned a hit that is not on the query\n"); ret = 1; break; }
 					if (r < 0) ret = 1;
-					if (out.l > (1 << 20) || q == n_q - 1) {
-						if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) ret = 1;
-						out.l = 0;
-					}
+					if (out_flush(&out, q == n_q - 1) < 0) ret = 1;
 					if (ret) fprintf(stderr, "ERROR: failed to write the output\n");
 				}
 				rb3h_dawg_free(&dg);
@@ -2317,10 +2214,7 @@ static int main_sw(int argc, char *argv[])
 				at[0] += o[0].n_hit[q];
 				if (r == -2) { fprintf(stderr, "ERROR: a position names a sequence that the name list does not have\n"); ret = 1; break; }
 				if (r < 0) ret = 1;
-				if (out.l > (1 << 20) || q == n_q - 1) {
-					if (out.l > 0 && fwrite(out.s, 1, (size_t)out.l, stdout) != (size_t)out.l) ret = 1;
-					out.l = 0;
-				}
+				if (out_flush(&out, q == n_q - 1) < 0) ret = 1;
 				if (ret) fprintf(stderr, "ERROR: failed to write the output\n");
 			}
 			id += n_q, ++n_batches;
@@ -2335,7 +2229,8 @@ static int main_sw(int argc, char *argv[])
 	if (rb3h_verbose >= 3 && ret == 0 && local)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] the graphs: %lld nodes, %lld edges, %.3f ms on the host\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_nodes, (long long)n_edges, ms_dawg);
 	for (j = 0; j < 2; ++j) { free(o[j].n_hit); free(o[j].hits); free(o[j].steps); free(o[j].pos); }
-	free(out.s); free(sym.s); free(rev.s); free(names.s); free(off); free(name_off); free(node_off); free(hit_node);
+	free(out.s); free(rev.s); free(node_off); free(hit_node);
+	rb3h_qbatch_free(&b);
 	rb3gpu_destroy(h);
 	rb3h_sid_destroy(sid);
 	return ret;

@@ -60,6 +60,12 @@ void rb3h_batch_free(void *p);
 int rb3h_seq_error(const rb3h_seqio_t *fp); /* != 0: a FASTX parsing error ended the file early (code as in kseq: -2 truncated quality, ...) */
 /* one record with its name (io.c:127-144): the query commands' reader; see seqio.c */
 int64_t rb3h_seq_read1(rb3h_seqio_t *fp, const uint8_t **seq, const char **name);
+/* a batch of whole records for a query command (the loop of search.c:366-378): records are added until sym.l >= max_sym or n >= max_rec.  Record q is the nt6
+ * codes sym.s[off[q], off[q + 1]) and its name names.s + name_off[q] (-1: none, a file of lines); eof: rb3h_seq_read1 said the file is over (see rb3h_seq_error).
+ * Returns n, -1 (no memory) or -2 (a record of more than max_len symbols); nothing of a failed batch is for use.  Prints nothing; the buffers serve the next call */
+typedef struct { rb3h_buf_t sym, names; int64_t *off, *name_off, n, m; int eof; } rb3h_qbatch_t;
+int64_t rb3h_qbatch_read(rb3h_seqio_t *fp, rb3h_qbatch_t *b, int64_t max_sym, int64_t max_rec, int64_t max_len);
+void rb3h_qbatch_free(rb3h_qbatch_t *b);
 int64_t rb3h_strand_pairs(int64_t len, const uint8_t *text, int64_t n_seq, int64_t max_pairs, int64_t *pair_start); /* record offsets of a both-strand batch */
 void rb3h_char2nt6(int64_t l, uint8_t *s);                                 /* io.c:23-28 */
 void rb3h_revcomp6(int64_t l, uint8_t *s);                                 /* io.c:30-40 */

@@ -506,6 +506,42 @@ int64_t rb3h_seq_read1(rb3h_seqio_t *fp, const uint8_t **seq, const char **name)
 	return ret;
 }
 
+/* the batch of a query command: whole records through rb3h_seq_read1 until their symbols reach max_sym or their number max_rec (rb3host.h) */
+int64_t rb3h_qbatch_read(rb3h_seqio_t *fp, rb3h_qbatch_t *b, int64_t max_sym, int64_t max_rec, int64_t max_len)
+{
+	int64_t l;
+	const uint8_t *s;
+	const char *name;
+	b->n = b->sym.l = b->names.l = 0, b->eof = 0;
+	while ((l = rb3h_seq_read1(fp, &s, &name)) >= 0) {
+		const int64_t l_name = name ? (int64_t)strlen(name) + 1 : 0;
+		if (b->n + 2 > b->m) {
+			const int64_t m = b->m ? b->m * 2 : 1024;
+			int64_t *t = (int64_t*)realloc(b->off, (size_t)m * 8), *u = t ? (int64_t*)realloc(b->name_off, (size_t)m * 8) : 0;
+			if (t) b->off = t;
+			if (u == 0) return -1;
+			b->name_off = u, b->m = m;
+		}
+		if (buf_grow(&b->sym, b->sym.l + l + 1) < 0 || buf_grow(&b->names, b->names.l + l_name + 1) < 0) return -1;
+		if (l > max_len) return -2;
+		if (l > 0) memcpy(b->sym.s + b->sym.l, s, (size_t)l);
+		rb3h_char2nt6(l, b->sym.s + b->sym.l); /* search.c:91 */
+		if (b->n == 0) b->off[0] = 0;
+		b->sym.l += l, b->off[++b->n] = b->sym.l;
+		b->name_off[b->n - 1] = name ? b->names.l : -1;
+		if (name) memcpy(b->names.s + b->names.l, name, (size_t)l_name), b->names.l += l_name;
+		if (b->sym.l >= max_sym || b->n >= max_rec) return b->n;
+	}
+	b->eof = 1;
+	return b->n;
+}
+
+void rb3h_qbatch_free(rb3h_qbatch_t *b)
+{
+	free(b->sym.s); free(b->names.s); free(b->off); free(b->name_off);
+	memset(b, 0, sizeof(*b));
+}
+
 /* the records of a batch that was read with BOTH strands (rb3h_seq_read with is_for and is_rev: per record l symbols, 0, the reverse
  * complement, 0): pair_start[i] = offset of record i, for rb3gpu_sorter_upload_fwd.  Returns the number of records, or 0 if the
  * batch has more than max_pairs records or not that layout (n_seq is the number of strings: two per record). */

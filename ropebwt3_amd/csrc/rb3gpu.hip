@@ -4296,6 +4296,37 @@ int rb3gpu_sync(rb3gpu_t *h)
 	return 0;
 }
 
+/* ---- what the query drivers below share: each keeps its own control flow and calls these in place ---- */
+
+// both strands (rb3_fmi_is_symmetric, fm-index.h:135): the forward extension is a backward extension of the reverse complement
+static bool both_strands(const rb3gpu_t *h) { return (h->acc[1] & 1) == 0 && h->acc[2] - h->acc[1] == h->acc[5] - h->acc[4] && h->acc[3] - h->acc[2] == h->acc[4] - h->acc[3]; }
+static Acc7 acc7_of(const rb3gpu_t *h) { Acc7 r; for (int a = 0; a < 7; ++a) r.a[a] = h->acc[a]; return r; } // C[] as the kernels take it
+static int scan_err(int r) { return r >= 0 ? 0 : r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV; } // what rb3kount_scan returns, as a code of the ABI
+
+// the entry of a driver, behind its refusals: its device, the start of its clock, and nothing of the handle's earlier work in flight
+static int drv_enter(rb3gpu_t *h, double *t0)
+{
+	HIPCHK(hipSetDevice(h->dev));
+	*t0 = now_s();
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipStreamSynchronize(h->st2));
+	return 0;
+}
+
+// the queries symbols[offsets[q], offsets[q + 1]): they start at 0, none is longer than max_len, and there are symbols if there is anything to read; *total: how many
+static bool queries_ok(int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t max_len, int64_t *total)
+{
+	*total = 0;
+	if (n_query <= 0) return true;
+	if (offsets[0] != 0) return false;
+	for (int64_t q = 0; q < n_query; ++q) {
+		const int64_t l = offsets[q + 1] - offsets[q];
+		if (l < 0 || l > max_len) return false;
+	}
+	*total = offsets[n_query];
+	return *total <= 0 || symbols != nullptr;
+}
+
 /* ---- kount: k-mer counting over one or more indexes (rb3gpu_kount.h) ------------------------- */
 
 int rb3kount_scan(void *tmp, size_t *tmp_bytes, const uint32_t *cnt, int64_t *off, int64_t n, hipStream_t st); // rb3gpu_kount.hip
@@ -4361,9 +4392,9 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 	for (int i = 0; i < n_idx; ++i)
 		if (hs[i]->n <= 0 || hs[i]->grp == nullptr) return RB3GPU_ESTATE;
 	rb3gpu_t *h = hs[0];
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	for (int i = 0; i < n_idx; ++i) {
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	for (int i = 1; i < n_idx; ++i) {
 		HIPCHK(hipStreamSynchronize(hs[i]->st));
 		HIPCHK(hipStreamSynchronize(hs[i]->st2));
 	}
@@ -4390,7 +4421,7 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 	HIPCHK(hipHostMalloc((void**)&ws.h_small, 64, hipHostMallocDefault));
 	{
 		int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, cap + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
 	}
 	double ms_expand = 0;
@@ -4419,7 +4450,7 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 		if (ni > 1) hipLaunchKernelGGL(k_kount_keep, dim3(grid(nub + 1)), dim3(256), 0, h->st, (const int64_t*)P.ci, ni, pn, nub, min_occ, P.cnt);
 		size_t b = ws.tmp_bytes + 256;
 		const int r = rb3kount_scan(ws.tmp, &b, P.cnt, P.off, nub + 1, h->st);
-		return r < 0 ? (r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV) : 0;
+		return scan_err(r);
 	};
 	struct Frame { const int64_t *pn; int64_t nub, n, total, i, base; int phase; }; // phase 0: to expand, 1: slices of its children, 2: done
 	std::vector<Frame> F((size_t)k);
@@ -4550,7 +4581,7 @@ static int loc_init(rb3gpu_t *h, LocWs &ws, int64_t n_cap, bool own_src)
 	HIPCHK(hipHostMalloc((void**)&ws.h_small, 128, hipHostMallocDefault));
 	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&ws.ev[i]));
 	const int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, n_cap + 1, h->st);
-	if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+	if (r < 0) return scan_err(r);
 	HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
 	return 0;
 }
@@ -4597,15 +4628,14 @@ static int loc_slice(rb3gpu_t *h, LocWs &ws, int64_t nn, const int64_t *d_src, i
 		ws.pair_cap = pc;
 	}
 	const IdxView ix = view_of(h);
-	Acc7 acc;
-	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const Acc7 acc = acc7_of(h);
 	const uint64_t *r2i = h->ssa_dev, *ssa = h->ssa_dev + h->ssa_m;
 	const int64_t cap = h->tn.locate_heap > 0 ? h->tn.locate_heap : RB3_LOC_HEAP;
 	auto grid = [](int64_t octets) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((octets * 8 + 255) / 256, 2048)); };
 	hipLaunchKernelGGL(k_locate_prep, dim3((unsigned)std::min<int64_t>((nn + 256) / 256, 4096)), dim3(256), 0, h->st, d_src, stride, is_size, nn, max_pos, ws.iv, ws.cnt);
 	size_t tb = ws.tmp_bytes + 256;
 	const int r = rb3kount_scan(ws.tmp, &tb, ws.cnt, ws.off, nn + 1, h->st);
-	if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+	if (r < 0) return scan_err(r);
 	HIPCHK(hipMemsetAsync(ws.flag, 0, (size_t)nn * 4, h->st));
 	HIPCHK(hipMemsetAsync(ws.ctr, 0, LOC_CTR_WORDS * 8, h->st));
 	HIPCHK(hipEventRecord(ws.ev[0], h->st));
@@ -4691,10 +4721,8 @@ int rb3gpu_locate(rb3gpu_t *h, int64_t n, const int64_t *lo, const int64_t *hi, 
 	if (max_pos > 0x7fffffffLL) max_pos = 0x7fffffffLL; // (an int in the reference)
 	for (int64_t i = 0; i < n; ++i)
 		if (lo[i] < hi[i] && (lo[i] < h->acc[1] || hi[i] > h->acc[6])) return RB3GPU_EINVAL; // (rows of sentinels: the reference reads in front of ssa[])
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	if (n == 0) return 0;
 	LocWs ws;
 	int r;
@@ -4751,26 +4779,17 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 	if (st) memset(st, 0, sizeof(*st));
 	if (lst) memset(lst, 0, sizeof(*lst));
 	if (!h || n_query < 0 || n_query > 0x7fffffffLL || (max_pos > 0 ? !cbp : !cb) || min_len < 1 || min_occ < 1 || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
-	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
-	int64_t max_len = 0;
-	for (int64_t q = 0; q < n_query; ++q) {
-		const int64_t l = offsets[q + 1] - offsets[q];
-		if (l < 0 || l > 0x7fffffffLL) return RB3GPU_EINVAL;
-		max_len = std::max(max_len, l);
-	}
-	const int64_t total = n_query > 0 ? offsets[n_query] : 0;
-	if (total > 0 && !symbols) return RB3GPU_EINVAL;
+	int64_t total, max_len = 0;
+	if (!queries_ok(n_query, offsets, symbols, 0x7fffffffLL, &total)) return RB3GPU_EINVAL;
+	for (int64_t q = 0; q < n_query; ++q) max_len = std::max(max_len, offsets[q + 1] - offsets[q]);
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	// both strands (rb3_fmi_is_symmetric, fm-index.h:135): the forward extension is a backward extension of the reverse complement
-	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE;
+	if (!both_strands(h)) return RB3GPU_ESTATE;
 	if (max_pos > 0 && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
 	if (max_pos > 0x7fffffffLL) max_pos = 0x7fffffffLL;
 	if (chunk <= 0) chunk = RB3_MEM_CHUNK;
 	if (chunk > 0x7fffffffLL) chunk = 0x7fffffffLL;
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	if (total == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
 	// the walkers: chunk after chunk of query after query, so that their chunks tile [0, total) in order
 	std::vector<int32_t> wq, wa;
@@ -4805,7 +4824,7 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 	HIPCHK(hipEventCreate(&ws.e1));
 	{
 		const int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, cap + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
 	}
 	HIPCHK(hipMemcpyAsync(ws.sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
@@ -4814,8 +4833,7 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 	HIPCHK(hipMemcpyAsync(ws.wa, wa.data(), (size_t)nw * 4, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(ws.ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
-	Acc7 acc;
-	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const Acc7 acc = acc7_of(h);
 	double ms_walk = 0;
 	int64_t n_rec = 0, n_slices = 0;
 	int ret = 0;
@@ -4834,7 +4852,7 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 		HIPCHK(hipEventRecord(ws.e1, h->st));
 		size_t tb = ws.tmp_bytes + 256;
 		const int r = rb3kount_scan(ws.tmp, &tb, ws.flag, ws.off, ns + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(hipMemcpyAsync(ws.h_small, ws.off + ns, 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
@@ -4925,11 +4943,9 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 		total = std::max(total, win_off[i] + k);
 	}
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE; // both strands, as rb3gpu_mem
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	if (!both_strands(h)) return RB3GPU_ESTATE;
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	if (n_win == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
 	const int64_t N = opt->n_best;
 	const int64_t slice = std::min(n_win, h->tn.hapdiv_slice > 0 ? h->tn.hapdiv_slice : RB3_HD_SLICE);
@@ -4974,8 +4990,7 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 	HIPCHK(hipMemcpyAsync(d_off, win_off, (size_t)n_win * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
-	Acc7 acc;
-	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const Acc7 acc = acc7_of(h);
 	HdOpt o;
 	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = opt->e2e_drop, o.k = k;
 	double ms_dp = 0;
@@ -5033,23 +5048,17 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	if (lst) memset(lst, 0, sizeof(*lst));
 	if (!h || !opt || !cb || opt->n_best < 1 || opt->end_len < 1 || n_query < 0 || n_query > 0x7fffffffLL || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
 	if (opt->n_best >= (1 << 24)) return RB3GPU_EINVAL; // (the F column of a cell has 24 bits)
-	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
 	const int64_t N = opt->n_best;
-	for (int64_t q = 0; q < n_query; ++q) {
-		const int64_t l = offsets[q + 1] - offsets[q];
-		if (l < 0 || l > 0x7ffffffeLL || (l + 1) * N >= 0xFFFFFFFFLL) return RB3GPU_EINVAL; // a cell of the backtrack matrix is named by row * n_best + column in 32 bits
-	}
-	const int64_t total = n_query > 0 ? offsets[n_query] : 0;
-	if (total > 0 && !symbols) return RB3GPU_EINVAL;
+	int64_t total;
+	// a cell of the backtrack matrix is named by row * n_best + column in 32 bits: (l + 1) * N < 0xFFFFFFFF, which is l <= 0xFFFFFFFE / N - 1
+	if (!queries_ok(n_query, offsets, symbols, std::min<int64_t>(0x7ffffffeLL, 0xFFFFFFFELL / N - 1), &total)) return RB3GPU_EINVAL;
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE; // both strands, as rb3gpu_mem
+	if (!both_strands(h)) return RB3GPU_ESTATE;
 	const bool with_pos = opt->max_pos >= 0;
 	if (with_pos && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
 	const int64_t loc_cap = std::max<int64_t>(1, opt->max_pos); // every hit is located at the largest cap one can have (rb3_sw: rest > 0 ? rest : 1) and cut to its own
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	if (n_query == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
 	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
 	int64_t cap0 = 4;
@@ -5117,7 +5126,7 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
 	{
 		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, n_slot_cap + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
 	}
 	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 4, hipHostMallocDefault));
@@ -5129,8 +5138,7 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	HIPCHK(hipMemcpyAsync(d_btoff, bt_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
-	Acc7 acc;
-	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const Acc7 acc = acc7_of(h);
 	HdOpt o;
 	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = opt->e2e_drop, o.k = 0;
 	double ms_dp = 0, ms_bt = 0;
@@ -5149,7 +5157,7 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 		size_t tb = tmp_bytes + 256;
 		int r = rb3kount_scan(d_tmp, &tb, d_flag, d_hoff, n_slot + 1, h->st);
 		if (r == 0) tb = tmp_bytes + 256, r = rb3kount_scan(d_tmp, &tb, d_cnt, d_soff, n_slot + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(hipMemcpyAsync(hw.h_tot, d_hoff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, d_soff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(hw.h_nhit, d_nhit, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
@@ -5263,14 +5271,12 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 				if (pre[j] < 0 || pre[j] >= g - node_off[q]) return RB3GPU_EINVAL;
 		}
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	if ((h->acc[1] & 1) != 0 || h->acc[2] - h->acc[1] != h->acc[5] - h->acc[4] || h->acc[3] - h->acc[2] != h->acc[4] - h->acc[3]) return RB3GPU_ESTATE; // both strands, as rb3gpu_mem
+	if (!both_strands(h)) return RB3GPU_ESTATE;
 	const bool with_pos = opt->max_pos >= 0;
 	if (with_pos && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
 	const int64_t loc_cap = std::max<int64_t>(1, opt->max_pos); // one hit per query: rest > 0 ? rest : 1 at its first and only hit
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	if (n_query == 0) { if (st) st->sw.ms_total = (now_s() - t0) * 1e3; return 0; }
 	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
 	int64_t cap0 = 4;
@@ -5343,7 +5349,7 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
 	{
 		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, slice + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
 	}
 	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 8, hipHostMallocDefault)); // (the flags of the slice, then the nodes of its hits)
@@ -5358,8 +5364,7 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 	HIPCHK(hipMemcpyAsync(d_coff, cell_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
-	Acc7 acc;
-	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const Acc7 acc = acc7_of(h);
 	HdOpt o;
 	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = -1, o.k = 0;
 	double ms_dp = 0, ms_bt = 0;
@@ -5378,7 +5383,7 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 		size_t tb = tmp_bytes + 256;
 		int r = rb3kount_scan(d_tmp, &tb, d_flag, d_hoff, nq + 1, h->st);
 		if (r == 0) tb = tmp_bytes + 256, r = rb3kount_scan(d_tmp, &tb, d_cnt, d_soff, nq + 1, h->st);
-		if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+		if (r < 0) return scan_err(r);
 		HIPCHK(hipMemcpyAsync(hw.h_tot, d_hoff + nq, 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, d_soff + nq, 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(hw.h_nhit, d_flag, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
@@ -5486,18 +5491,11 @@ int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	static_assert(sizeof(SuffixOut) == sizeof(rb3gpu_suffix_rec_t), "one record layout on both sides");
 	if (st) memset(st, 0, sizeof(*st));
 	if (!h || n_query < 0 || (n_query > 0 && (!offsets || !out))) return RB3GPU_EINVAL;
-	if (n_query > 0 && offsets[0] != 0) return RB3GPU_EINVAL;
-	for (int64_t q = 0; q < n_query; ++q) { // the kernel keeps a position in 32 bits
-		const int64_t l = offsets[q + 1] - offsets[q];
-		if (l < 0 || l > 0x7fffffffLL) return RB3GPU_EINVAL;
-	}
-	const int64_t total = n_query > 0 ? offsets[n_query] : 0;
-	if (total > 0 && !symbols) return RB3GPU_EINVAL;
+	int64_t total;
+	if (!queries_ok(n_query, offsets, symbols, 0x7fffffffLL, &total)) return RB3GPU_EINVAL; // (the kernel keeps a position in 32 bits)
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	if (st) st->n_queries = n_query, st->n_symbols = total;
 	if (total == 0) { // nothing but queries of no symbols
 		if (n_query > 0) memset(out, 0, (size_t)n_query * sizeof(*out));
@@ -5522,8 +5520,7 @@ int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	HIPCHK(hipMemcpyAsync(d_qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
-	Acc7 acc;
-	for (int a = 0; a < 7; ++a) acc.a[a] = h->acc[a];
+	const Acc7 acc = acc7_of(h);
 	double ms_walk = 0;
 	int64_t n_slices = 0;
 	for (int64_t q0 = 0; q0 < n_query; ++n_slices) {
@@ -5550,10 +5547,8 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 	if (st) memset(st, 0, sizeof(*st));
 	if (!h || n < 0 || !cb || (n > 0 && !rows)) return RB3GPU_EINVAL;
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	HIPCHK(hipSetDevice(h->dev));
-	const double t0 = now_s();
-	HIPCHK(hipStreamSynchronize(h->st));
-	HIPCHK(hipStreamSynchronize(h->st2));
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
 	// the rows that exist (rb3_fmi_retrieve, fm-index.c:557: the others are answered -1 and nothing is walked for them): only they reach the device
 	std::vector<int64_t> vrow, vat; // vat[v]: which of the n rows asked for valid row v is
 	for (int64_t i = 0; i < n; ++i)
@@ -5584,7 +5579,7 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 		HIPCHK(hipEventCreate(&ws.e1));
 		{
 			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, nv + 1, h->st);
-			if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+			if (r < 0) return scan_err(r);
 			HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
 		}
 		HIPCHK(hipMemcpyAsync(d_rows, vrow.data(), (size_t)nv * 8, hipMemcpyHostToDevice, h->st));
@@ -5629,7 +5624,7 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 			}
 			size_t tb = tmp_bytes + 256;
 			const int r = rb3kount_scan(d_tmp, &tb, d_len32 + v0, d_off, v1 - v0 + 1, h->st); // (d_len32[nv] = 0: the entry behind the last row)
-			if (r < 0) return r == -2 ? RB3GPU_ENOMEM : RB3GPU_ENODEV;
+			if (r < 0) return scan_err(r);
 			HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
 			HIPCHK(hipMemcpyAsync(ws.h_ctr + 4, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
 			const int64_t nb = std::min<int64_t>(((v1 - v0) * 8 + 255) / 256, 4096);
