@@ -4915,6 +4915,38 @@ int rb3gpu_mem_pos(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 #define RB3_HD_SLICE ((int64_t)1 << 16)       // windows per launch
 #define RB3_HD_BLOCKS 2048                    // windows in flight at most: 8 single-wave blocks on each of 256 CUs (20 KB of LDS a block)
 
+// a device buffer that lives as long as dv's owner does (64 bytes to spare behind it)
+static hipError_t dv_alloc(std::vector<void*> &dv, void **p, size_t bytes)
+{
+	const hipError_t e = hipMalloc(p, bytes + 64);
+	if (e == hipSuccess) dv.push_back(*p);
+	return e;
+}
+
+/* the per-block workspace of the dynamic program (HdWs of rb3gpu_hapdiv.h) for hapdiv, sw -e and sw --local: hd_ws_size sets the capacities for n_best N
+ * (everything else 0) and returns the bytes a block takes, without a backtrack matrix; hd_ws_alloc gives nb blocks their six arrays */
+static size_t hd_ws_size(HdWs &ws, int64_t N)
+{
+	int64_t cap0 = 4;
+	while (cap0 < 4 * N) cap0 *= 2;
+	memset(&ws, 0, sizeof(ws));
+	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
+	ws.stack_cap = 16 * N + 64;
+	ws.fpar_cap = 32 * N + 64;
+	return (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(HdZ) + (size_t)ws.fpar_cap * 16 + 256;
+}
+
+static int hd_ws_alloc(rb3gpu_t *h, std::vector<void*> &dv, HdWs &ws, int64_t nb, int64_t N)
+{
+	HIPCHK(dv_alloc(dv, (void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
+	HIPCHK(dv_alloc(dv, (void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
+	HIPCHK(dv_alloc(dv, (void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
+	HIPCHK(dv_alloc(dv, (void**)&ws.heap, (size_t)nb * N * 4));
+	HIPCHK(dv_alloc(dv, (void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ)));
+	HIPCHK(dv_alloc(dv, (void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
+	return 0;
+}
+
 struct HdHostWs {
 	std::vector<void*> dv;
 	int32_t *h_out = nullptr;
@@ -4950,23 +4982,17 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 	const int64_t N = opt->n_best;
 	const int64_t slice = std::min(n_win, h->tn.hapdiv_slice > 0 ? h->tn.hapdiv_slice : RB3_HD_SLICE);
 	const int lds_slots = h->tn.hapdiv_table > 0 ? (int)h->tn.hapdiv_table : HD_LDS_SLOTS;
-	int64_t cap0 = 4;
-	while (cap0 < 4 * N) cap0 *= 2;
 	HdWs ws;
-	memset(&ws, 0, sizeof(ws));
+	const size_t ws_block = hd_ws_size(ws, N);
 	ws.bt_stride = ((int64_t)k + 1) * N * 3;
-	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
-	ws.stack_cap = 16 * N + 64;
-	ws.fpar_cap = 32 * N + 64;
-	const size_t per_block = (size_t)ws.bt_stride * 4 + (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(HdZ)
-		+ (size_t)ws.fpar_cap * 16 + 256;
+	const size_t per_block = (size_t)ws.bt_stride * 4 + ws_block;
 	size_t fr = 0, tot = 0;
 	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
 	const size_t fixed = (size_t)total + (size_t)n_win * 8 + (size_t)slice * 36 + ((size_t)64 << 20);
 	if (fr / 2 < fixed + per_block) return RB3GPU_ENOMEM;
 	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr / 2 - fixed) / per_block)); // the windows in flight: by the free memory
 	HdHostWs hw;
-	auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes + 64); if (e == hipSuccess) hw.dv.push_back(*p); return e; };
+	auto dalloc = [&](void **p, size_t bytes) { return dv_alloc(hw.dv, p, bytes); };
 	uint8_t *d_sym = nullptr;
 	int64_t *d_off = nullptr;
 	int32_t *d_out = nullptr;
@@ -4976,12 +5002,7 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 	HIPCHK(dalloc((void**)&d_out, (size_t)slice * 36));
 	HIPCHK(dalloc((void**)&d_ctr, 64));
 	HIPCHK(dalloc((void**)&ws.bt, (size_t)nb * ws.bt_stride * 4));
-	HIPCHK(dalloc((void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
-	HIPCHK(dalloc((void**)&ws.heap, (size_t)nb * N * 4));
-	HIPCHK(dalloc((void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ)));
-	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
+	if (const int e = hd_ws_alloc(h, hw.dv, ws, nb, N)) return e;
 	HIPCHK(hipHostMalloc((void**)&hw.h_out, (size_t)slice * 36, hipHostMallocDefault));
 	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
 	HIPCHK(hipEventCreate(&hw.e0));
@@ -5022,6 +5043,15 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 
 struct SwHostWs {
 	std::vector<void*> dv;
+	// per slot of a slice (sw_slices): hit or not, its steps, both scanned, and the hit as the fill kernel found it
+	uint32_t *d_flag = nullptr, *d_cnt = nullptr;
+	int64_t *d_hoff = nullptr, *d_soff = nullptr;
+	SwRaw *d_raw = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	void *d_tmp = nullptr;
+	size_t tmp_bytes = 0;
+	int64_t n_slot_cap = 0;
+	// the hits and the step bytes of a slice, grown as slices need them
 	SwRaw *d_hits = nullptr, *h_hits = nullptr;
 	uint8_t *d_steps = nullptr, *h_steps = nullptr;
 	int64_t hit_cap = 0, step_cap = 0;
@@ -5040,162 +5070,106 @@ struct SwHostWs {
 	}
 };
 
-int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud,
-		rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst)
+// a device buffer and its page-locked copy on the host, both of `bytes` bytes, in place of the ones there are
+static int sw_regrow(rb3gpu_t *h, void **d, void **hp, size_t bytes)
+{
+	if (*d) { HIPCHK(hipFree(*d)); *d = nullptr; }
+	if (*hp) { HIPCHK(hipHostFree(*hp)); *hp = nullptr; }
+	HIPCHK(hipMalloc(d, bytes));
+	HIPCHK(hipHostMalloc(hp, bytes, hipHostMallocDefault));
+	return 0;
+}
+
+// what sw_slices works with, for slices of up to n_slot_cap slots: the caller's kernels are given these
+static int sw_slice_bufs(rb3gpu_t *h, SwHostWs &hw, int64_t n_slot_cap)
+{
+	hw.n_slot_cap = n_slot_cap;
+	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_flag, (size_t)(n_slot_cap + 1) * 4));
+	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_cnt, (size_t)(n_slot_cap + 1) * 4));
+	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_hoff, (size_t)(n_slot_cap + 1) * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_soff, (size_t)(n_slot_cap + 1) * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_raw, (size_t)n_slot_cap * sizeof(SwRaw)));
+	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_ctr, 64));
+	const int r = rb3kount_scan(nullptr, &hw.tmp_bytes, nullptr, nullptr, n_slot_cap + 1, h->st);
+	if (r < 0) return scan_err(r);
+	HIPCHK(dv_alloc(hw.dv, &hw.d_tmp, hw.tmp_bytes + 256));
+	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
+	HIPCHK(hipHostMalloc((void**)&hw.h_tot, 64, hipHostMallocDefault));
+	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&hw.e[i]));
+	HIPCHK(hipMemsetAsync(hw.d_ctr, 0, 64, h->st));
+	return 0;
+}
+
+struct SwFetch { const void *d; void *h; }; // an int per query of the slice that the fill kernel leaves on the device and the host wants
+
+/* The slices of `sw -e` and `sw --local` behind sw_slice_bufs: slice i is the queries [cuts[i], cuts[i + 1]) with per_q slots each (N columns; the one best
+ * hit).  Per slice: fill(q0, q1) launches the kernel that leaves flag, cnt and raw of every slot in hw; the two scans; their totals, the counters and
+ * the arrays of `fetch` -- the first is the hits per query, to hw.h_nhit -- come to the host; after(q0, nq) sees them (not 0: the call fails with it);
+ * emit(q0, nq) launches the kernel that puts hits and steps in their places (hw.d_hits, hw.d_steps by hw.d_hoff, hw.d_soff); the hits are located
+ * (max_pos >= 0: every one at the largest cap a hit can have, rb3_sw's rest > 0 ? rest : 1, and cut to its own) and the slice goes to cb.
+ * Returns what failed, or 0 and in *cb_ret what cb returned last; the statistics are written then */
+extern "C++" {
+template<class Fill, class After, class Emit>
+static int sw_slices(rb3gpu_t *h, SwHostWs &hw, const std::vector<int64_t> &cuts, int64_t per_q, const std::vector<SwFetch> &fetch, int64_t max_pos, double t0, Fill fill, After after,
+		Emit emit, rb3gpu_sw_cb cb, void *ud, int *cb_ret, rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst)
 {
 	static_assert(sizeof(SwRaw) == 40, "the locate step reads (lo, hi) with a stride of five words");
-	if (st) memset(st, 0, sizeof(*st));
-	if (lst) memset(lst, 0, sizeof(*lst));
-	if (!h || !opt || !cb || opt->n_best < 1 || opt->end_len < 1 || n_query < 0 || n_query > 0x7fffffffLL || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
-	if (opt->n_best >= (1 << 24)) return RB3GPU_EINVAL; // (the F column of a cell has 24 bits)
-	const int64_t N = opt->n_best;
-	int64_t total;
-	// a cell of the backtrack matrix is named by row * n_best + column in 32 bits: (l + 1) * N < 0xFFFFFFFF, which is l <= 0xFFFFFFFE / N - 1
-	if (!queries_ok(n_query, offsets, symbols, std::min<int64_t>(0x7ffffffeLL, 0xFFFFFFFELL / N - 1), &total)) return RB3GPU_EINVAL;
-	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	if (!both_strands(h)) return RB3GPU_ESTATE;
-	const bool with_pos = opt->max_pos >= 0;
-	if (with_pos && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
-	const int64_t loc_cap = std::max<int64_t>(1, opt->max_pos); // every hit is located at the largest cap one can have (rb3_sw: rest > 0 ? rest : 1) and cut to its own
-	double t0;
-	if (const int e = drv_enter(h, &t0)) return e;
-	if (n_query == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
-	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
-	int64_t cap0 = 4;
-	while (cap0 < 4 * N) cap0 *= 2;
-	HdWs ws;
-	memset(&ws, 0, sizeof(ws));
-	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
-	ws.stack_cap = 16 * N + 64;
-	ws.fpar_cap = 32 * N + 64;
-	const size_t per_block = (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(HdZ) + (size_t)ws.fpar_cap * 16 + 256;
-	size_t fr = 0, tot = 0;
-	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
-	// the slices: at most sw_slice queries, RB3_SW_SLOTS columns and bt_budget bytes of matrices, but one query at least; bt_off[q]: the first cell of query q in its slice
-	const int64_t max_q = std::max<int64_t>(1, std::min(h->tn.sw_slice > 0 ? h->tn.sw_slice : RB3_SW_SLICE, RB3_SW_SLOTS / N));
-	const int64_t bt_budget = std::max<int64_t>((int64_t)1 << 20, std::min<int64_t>(RB3_SW_BT_BYTES, (int64_t)(fr / 4))) / 12;
-	std::vector<int64_t> bt_off((size_t)n_query), cuts(1, 0);
-	int64_t max_cells = 0;
-	{
-		int64_t cells = 0;
-		for (int64_t q = 0; q < n_query; ++q) {
-			const int64_t c = (offsets[q + 1] - offsets[q] + 1) * N;
-			if (q > cuts.back() && (q - cuts.back() >= max_q || cells + c > bt_budget)) cuts.push_back(q), cells = 0;
-			bt_off[q] = cells, cells += c;
-			max_cells = std::max(max_cells, cells);
-		}
-		cuts.push_back(n_query);
-	}
-	int64_t slice = 0;
-	for (size_t i = 0; i + 1 < cuts.size(); ++i) slice = std::max(slice, cuts[i + 1] - cuts[i]);
-	const int64_t n_slot_cap = slice * N;
-	const size_t fixed = (size_t)total + (size_t)n_query * 16 + (size_t)max_cells * 12 + (size_t)n_slot_cap * 64 + ((size_t)64 << 20);
-	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
-	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
-	SwHostWs hw;
+	const int64_t n_slot_cap = hw.n_slot_cap;
+	const bool with_pos = max_pos >= 0;
+	const int64_t loc_cap = std::max<int64_t>(1, max_pos);
 	LocWs lws;
 	if (with_pos) {
 		const int r = loc_init(h, lws, std::min<int64_t>(n_slot_cap, RB3_LOC_SLICE_IV), false);
 		if (r < 0) return r;
 	}
-	auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes + 64); if (e == hipSuccess) hw.dv.push_back(*p); return e; };
-	uint8_t *d_sym = nullptr;
-	int64_t *d_off = nullptr, *d_btoff = nullptr, *d_hoff = nullptr, *d_soff = nullptr;
-	uint32_t *d_flag = nullptr, *d_cnt = nullptr;
-	SwRaw *d_raw = nullptr;
-	int32_t *d_nhit = nullptr;
-	unsigned long long *d_ctr = nullptr;
-	void *d_tmp = nullptr;
-	size_t tmp_bytes = 0;
-	HIPCHK(dalloc((void**)&d_sym, (size_t)total));
-	HIPCHK(dalloc((void**)&d_off, (size_t)(n_query + 1) * 8));
-	HIPCHK(dalloc((void**)&d_btoff, (size_t)n_query * 8));
-	HIPCHK(dalloc((void**)&d_flag, (size_t)(n_slot_cap + 1) * 4));
-	HIPCHK(dalloc((void**)&d_cnt, (size_t)(n_slot_cap + 1) * 4));
-	HIPCHK(dalloc((void**)&d_hoff, (size_t)(n_slot_cap + 1) * 8));
-	HIPCHK(dalloc((void**)&d_soff, (size_t)(n_slot_cap + 1) * 8));
-	HIPCHK(dalloc((void**)&d_raw, (size_t)n_slot_cap * sizeof(SwRaw)));
-	HIPCHK(dalloc((void**)&d_nhit, (size_t)slice * 4));
-	HIPCHK(dalloc((void**)&d_ctr, 64));
-	HIPCHK(dalloc((void**)&ws.bt, (size_t)max_cells * 12));
-	HIPCHK(dalloc((void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
-	HIPCHK(dalloc((void**)&ws.heap, (size_t)nb * N * 4));
-	HIPCHK(dalloc((void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ)));
-	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
-	{
-		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, n_slot_cap + 1, h->st);
-		if (r < 0) return scan_err(r);
-		HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
-	}
-	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 4, hipHostMallocDefault));
-	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
-	HIPCHK(hipHostMalloc((void**)&hw.h_tot, 64, hipHostMallocDefault));
-	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&hw.e[i]));
-	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
-	HIPCHK(hipMemcpyAsync(d_off, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
-	HIPCHK(hipMemcpyAsync(d_btoff, bt_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
-	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
-	const IdxView ix = view_of(h);
-	const Acc7 acc = acc7_of(h);
-	HdOpt o;
-	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = opt->e2e_drop, o.k = 0;
 	double ms_dp = 0, ms_bt = 0;
 	int64_t n_hits = 0, n_steps = 0, n_slices = 0;
 	std::vector<rb3gpu_sw_hit_t> hits;
 	std::vector<rb3gpu_pos_t> pairs;
 	int ret = 0;
 	for (size_t ci = 0; ci + 1 < cuts.size() && ret == 0; ++ci, ++n_slices) {
-		const int64_t q0 = cuts[ci], q1 = cuts[ci + 1], nq = q1 - q0, n_slot = nq * N;
-		HIPCHK(hipMemsetAsync(d_flag + n_slot, 0, 4, h->st)); // (the scans are exclusive: their last element is the total)
-		HIPCHK(hipMemsetAsync(d_cnt + n_slot, 0, 4, h->st));
+		const int64_t q0 = cuts[ci], q1 = cuts[ci + 1], nq = q1 - q0, n_slot = nq * per_q;
+		HIPCHK(hipMemsetAsync(hw.d_flag + n_slot, 0, 4, h->st)); // (the scans are exclusive: their last element is the total)
+		HIPCHK(hipMemsetAsync(hw.d_cnt + n_slot, 0, 4, h->st));
 		HIPCHK(hipEventRecord(hw.e[0], h->st));
-		hipLaunchKernelGGL(k_sw_fill, dim3((unsigned)std::min(nb, nq)), dim3(64), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_off, (const int64_t*)d_btoff, q0, q1, o,
-				(int)std::min<int64_t>(opt->end_len, 0x7fffffff), ws, lds_slots, d_flag, d_cnt, d_raw, d_nhit, d_ctr);
+		fill(q0, q1);
 		HIPCHK(hipEventRecord(hw.e[1], h->st));
-		size_t tb = tmp_bytes + 256;
-		int r = rb3kount_scan(d_tmp, &tb, d_flag, d_hoff, n_slot + 1, h->st);
-		if (r == 0) tb = tmp_bytes + 256, r = rb3kount_scan(d_tmp, &tb, d_cnt, d_soff, n_slot + 1, h->st);
+		size_t tb = hw.tmp_bytes + 256;
+		int r = rb3kount_scan(hw.d_tmp, &tb, hw.d_flag, hw.d_hoff, n_slot + 1, h->st);
+		if (r == 0) tb = hw.tmp_bytes + 256, r = rb3kount_scan(hw.d_tmp, &tb, hw.d_cnt, hw.d_soff, n_slot + 1, h->st);
 		if (r < 0) return scan_err(r);
-		HIPCHK(hipMemcpyAsync(hw.h_tot, d_hoff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, d_soff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_nhit, d_nhit, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_tot, hw.d_hoff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, hw.d_soff + n_slot, 8, hipMemcpyDeviceToHost, h->st));
+		for (const SwFetch &f : fetch) HIPCHK(hipMemcpyAsync(f.h, f.d, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(hw.h_ctr, hw.d_ctr, 24, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
 		ms_dp += ev_ms(hw.e[0], hw.e[1]);
 		if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a query could not be represented: no record of this slice goes out
 		const int64_t nh = hw.h_tot[0], ns = hw.h_tot[1];
 		if (nh < 0 || nh > n_slot || ns < 0) return RB3GPU_EINTERNAL;
+		if (const int e = after(q0, nq)) return e;
 		hits.resize((size_t)nh);
 		pairs.clear();
 		if (nh > 0) {
 			if (nh > hw.hit_cap) {
 				const int64_t c = std::max(nh, std::min(n_slot_cap, 2 * hw.hit_cap));
-				if (hw.d_hits) { HIPCHK(hipFree(hw.d_hits)); hw.d_hits = nullptr; }
-				if (hw.h_hits) { HIPCHK(hipHostFree(hw.h_hits)); hw.h_hits = nullptr; }
 				hw.hit_cap = 0;
-				HIPCHK(hipMalloc(&hw.d_hits, (size_t)c * sizeof(SwRaw)));
-				HIPCHK(hipHostMalloc((void**)&hw.h_hits, (size_t)c * sizeof(SwRaw), hipHostMallocDefault));
+				if (const int e = sw_regrow(h, (void**)&hw.d_hits, (void**)&hw.h_hits, (size_t)c * sizeof(SwRaw))) return e;
 				hw.hit_cap = c;
 			}
 			if (ns > hw.step_cap) {
 				const int64_t c = std::max(ns, 2 * hw.step_cap);
-				if (hw.d_steps) { HIPCHK(hipFree(hw.d_steps)); hw.d_steps = nullptr; }
-				if (hw.h_steps) { HIPCHK(hipHostFree(hw.h_steps)); hw.h_steps = nullptr; }
 				hw.step_cap = 0;
-				HIPCHK(hipMalloc(&hw.d_steps, (size_t)c + 64));
-				HIPCHK(hipHostMalloc((void**)&hw.h_steps, (size_t)c + 64, hipHostMallocDefault));
+				if (const int e = sw_regrow(h, (void**)&hw.d_steps, (void**)&hw.h_steps, (size_t)c + 64)) return e;
 				hw.step_cap = c;
 			}
 			HIPCHK(hipEventRecord(hw.e[2], h->st));
-			hipLaunchKernelGGL(k_sw_emit, dim3((unsigned)std::min<int64_t>((n_slot + 255) / 256, 16384)), dim3(256), 0, h->st, (const uint8_t*)d_sym, (const int64_t*)d_off, (const int64_t*)d_btoff,
-					q0, (int)N, (const uint32_t*)ws.bt, n_slot, (const uint32_t*)d_flag, (const SwRaw*)d_raw, (const int64_t*)d_hoff, (const int64_t*)d_soff, hw.d_hits, hw.d_steps, d_ctr);
+			emit(q0, nq);
 			HIPCHK(hipEventRecord(hw.e[3], h->st));
 			HIPCHK(hipMemcpyAsync(hw.h_hits, hw.d_hits, (size_t)nh * sizeof(SwRaw), hipMemcpyDeviceToHost, h->st));
 			if (ns > 0) HIPCHK(hipMemcpyAsync(hw.h_steps, hw.d_steps, (size_t)ns, hipMemcpyDeviceToHost, h->st));
-			HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(hw.h_ctr, hw.d_ctr, 24, hipMemcpyDeviceToHost, h->st));
 			HIPCHK(hipStreamSynchronize(h->st));
 			HIPCHK(hipGetLastError());
 			ms_bt += ev_ms(hw.e[2], hw.e[3]);
@@ -5204,8 +5178,9 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 				const SwRaw &x = hw.h_hits[i];
 				rb3gpu_sw_hit_t &y = hits[(size_t)i];
 				y.lo = x.lo, y.hi = x.hi, y.score = x.score, y.qlen = x.qlen, y.rlen = x.rlen, y.n_steps = x.n_steps, y.step_off = x.step_off, y.pos_off = 0, y.n_pos = 0;
+				if (x.n_steps < 0 || x.step_off < 0 || x.step_off + x.n_steps > ns) return RB3GPU_EINTERNAL;
 			}
-			if (with_pos) { // the intervals of the hits, read where k_sw_emit left them; every hit at loc_cap, then cut to what rb3_sw gives it
+			if (with_pos) { // the intervals of the hits, read where the emit kernel left them; every hit at loc_cap (n_pos: what came), then cut to what rb3_sw gives it
 				for (int64_t r0 = 0; r0 < nh;) {
 					const int64_t lim = std::min(nh - r0, lws.n_cap);
 					lws.h_size.resize((size_t)lim);
@@ -5216,17 +5191,21 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 					if (lr < 0) return lr;
 					const int64_t base = (int64_t)pairs.size(), np = lws.h_off[(size_t)nn];
 					if (np > 0) pairs.insert(pairs.end(), (const rb3gpu_pos_t*)lws.h_pairs, (const rb3gpu_pos_t*)lws.h_pairs + np);
-					for (int64_t i = 0; i < nn; ++i) hits[(size_t)(r0 + i)].pos_off = base + lws.h_off[(size_t)i];
+					for (int64_t i = 0; i < nn; ++i) {
+						rb3gpu_sw_hit_t &y = hits[(size_t)(r0 + i)];
+						y.pos_off = base + lws.h_off[(size_t)i], y.n_pos = lws.h_off[(size_t)i + 1] - lws.h_off[(size_t)i];
+					}
 					r0 += nn;
 				}
 				int64_t at = 0;
-				for (int64_t q = 0; q < nq; ++q) { // bwa-sw.c:547-556
-					int64_t rest = opt->max_pos;
+				for (int64_t q = 0; q < nq; ++q) { // bwa-sw.c:547-556; a query's only hit gets min(max(1, max_pos), hi - lo)
+					int64_t rest = max_pos;
 					for (int32_t k = 0; k < hw.h_nhit[q]; ++k, ++at) {
 						if (at >= nh) return RB3GPU_EINTERNAL;
 						rb3gpu_sw_hit_t &y = hits[(size_t)at];
-						y.n_pos = std::min<int64_t>(rest > 0 ? rest : 1, y.hi - y.lo);
-						rest -= y.n_pos;
+						const int64_t n_pos = std::min<int64_t>(rest > 0 ? rest : 1, y.hi - y.lo);
+						if (y.n_pos < n_pos) return RB3GPU_EINTERNAL;
+						y.n_pos = n_pos, rest -= n_pos;
 					}
 				}
 				if (at != nh) return RB3GPU_EINTERNAL;
@@ -5238,6 +5217,83 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->ms_backtrack = ms_bt, st->n_ext = (int64_t)hw.h_ctr[0], st->n_hits = n_hits, st->n_steps = n_steps,
 		st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
 	if (with_pos) loc_stats(lws, t0, lst);
+	*cb_ret = ret;
+	return 0;
+}
+} // extern "C++"
+
+int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud,
+		rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (lst) memset(lst, 0, sizeof(*lst));
+	if (!h || !opt || !cb || opt->n_best < 1 || opt->end_len < 1 || n_query < 0 || n_query > 0x7fffffffLL || (n_query > 0 && !offsets)) return RB3GPU_EINVAL;
+	if (opt->n_best >= (1 << 24)) return RB3GPU_EINVAL; // (the F column of a cell has 24 bits)
+	const int64_t N = opt->n_best;
+	int64_t total;
+	// a cell of the backtrack matrix is named by row * n_best + column in 32 bits: (l + 1) * N < 0xFFFFFFFF, which is l <= 0xFFFFFFFE / N - 1
+	if (!queries_ok(n_query, offsets, symbols, std::min<int64_t>(0x7ffffffeLL, 0xFFFFFFFELL / N - 1), &total)) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	if (!both_strands(h)) return RB3GPU_ESTATE;
+	if (opt->max_pos >= 0 && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	if (n_query == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
+	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
+	HdWs ws;
+	const size_t per_block = hd_ws_size(ws, N);
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
+	// the slices: at most sw_slice queries, RB3_SW_SLOTS columns and bt_budget bytes of matrices, but one query at least; bt_off[q]: the first cell of query q in its slice
+	const int64_t max_q = std::max<int64_t>(1, std::min(h->tn.sw_slice > 0 ? h->tn.sw_slice : RB3_SW_SLICE, RB3_SW_SLOTS / N));
+	const int64_t bt_budget = std::max<int64_t>((int64_t)1 << 20, std::min<int64_t>(RB3_SW_BT_BYTES, (int64_t)(fr / 4))) / 12;
+	std::vector<int64_t> bt_off((size_t)n_query), cuts(1, 0);
+	int64_t max_cells = 0, slice = 0;
+	{
+		int64_t cells = 0;
+		for (int64_t q = 0; q < n_query; ++q) {
+			const int64_t c = (offsets[q + 1] - offsets[q] + 1) * N;
+			if (q > cuts.back() && (q - cuts.back() >= max_q || cells + c > bt_budget)) cuts.push_back(q), cells = 0;
+			bt_off[q] = cells, cells += c;
+			max_cells = std::max(max_cells, cells);
+			slice = std::max(slice, q + 1 - cuts.back());
+		}
+		cuts.push_back(n_query);
+	}
+	const size_t fixed = (size_t)total + (size_t)n_query * 16 + (size_t)max_cells * 12 + (size_t)slice * N * 64 + ((size_t)64 << 20);
+	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
+	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
+	SwHostWs hw;
+	uint8_t *d_sym = nullptr;
+	int64_t *d_off = nullptr, *d_btoff = nullptr;
+	int32_t *d_nhit = nullptr;
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_sym, (size_t)total));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_off, (size_t)(n_query + 1) * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_btoff, (size_t)n_query * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_nhit, (size_t)slice * 4));
+	HIPCHK(dv_alloc(hw.dv, (void**)&ws.bt, (size_t)max_cells * 12));
+	if (const int e = hd_ws_alloc(h, hw.dv, ws, nb, N)) return e;
+	if (const int e = sw_slice_bufs(h, hw, slice * N)) return e;
+	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 4, hipHostMallocDefault));
+	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_off, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_btoff, bt_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
+	const IdxView ix = view_of(h);
+	const Acc7 acc = acc7_of(h);
+	HdOpt o;
+	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = opt->e2e_drop, o.k = 0;
+	const int end_len = (int)std::min<int64_t>(opt->end_len, 0x7fffffff);
+	auto fill = [&](int64_t q0, int64_t q1) {
+		hipLaunchKernelGGL(k_sw_fill, dim3((unsigned)std::min(nb, q1 - q0)), dim3(64), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_off, (const int64_t*)d_btoff, q0, q1, o,
+				end_len, ws, lds_slots, hw.d_flag, hw.d_cnt, hw.d_raw, d_nhit, hw.d_ctr);
+	};
+	auto emit = [&](int64_t q0, int64_t nq) {
+		const int64_t n_slot = nq * N;
+		hipLaunchKernelGGL(k_sw_emit, dim3((unsigned)std::min<int64_t>((n_slot + 255) / 256, 16384)), dim3(256), 0, h->st, (const uint8_t*)d_sym, (const int64_t*)d_off, (const int64_t*)d_btoff,
+				q0, (int)N, (const uint32_t*)ws.bt, n_slot, (const uint32_t*)hw.d_flag, (const SwRaw*)hw.d_raw, (const int64_t*)hw.d_hoff, (const int64_t*)hw.d_soff, hw.d_hits, hw.d_steps, hw.d_ctr);
+	};
+	int ret = 0;
+	if (const int e = sw_slices(h, hw, cuts, N, {{d_nhit, hw.h_nhit}}, opt->max_pos, t0, fill, [](int64_t, int64_t) { return 0; }, emit, cb, ud, &ret, st, lst)) return e;
 	return ret;
 }
 
@@ -5246,7 +5302,6 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, const int64_t *node_off, const uint8_t *node_sym, const int64_t *pre_off,
 		const int32_t *pre, const rb3gpu_sw_opt_t *opt, rb3gpu_sw_cb cb, void *ud, int32_t *hit_node, rb3gpu_swl_stats_t *st, rb3gpu_locate_stats_t *lst)
 {
-	static_assert(sizeof(SwRaw) == 40, "the locate step reads (lo, hi) with a stride of five words");
 	static_assert(sizeof(HdCell) == 56 && sizeof(HdCell) % 4 == 0, "a cell is copied word by word");
 	if (st) memset(st, 0, sizeof(*st));
 	if (lst) memset(lst, 0, sizeof(*lst));
@@ -5272,21 +5327,13 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 		}
 	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
 	if (!both_strands(h)) return RB3GPU_ESTATE;
-	const bool with_pos = opt->max_pos >= 0;
-	if (with_pos && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
-	const int64_t loc_cap = std::max<int64_t>(1, opt->max_pos); // one hit per query: rest > 0 ? rest : 1 at its first and only hit
+	if (opt->max_pos >= 0 && h->ssa_dev == nullptr) return RB3GPU_ESTATE;
 	double t0;
 	if (const int e = drv_enter(h, &t0)) return e;
 	if (n_query == 0) { if (st) st->sw.ms_total = (now_s() - t0) * 1e3; return 0; }
 	const int lds_slots = h->tn.sw_table > 0 ? (int)h->tn.sw_table : HD_LDS_SLOTS;
-	int64_t cap0 = 4;
-	while (cap0 < 4 * N) cap0 *= 2;
 	SlWs ws;
-	memset(&ws, 0, sizeof(ws));
-	ws.tab_cap = std::max<int64_t>(cap0 * 8, 2048);
-	ws.stack_cap = 16 * N + 64;
-	ws.fpar_cap = 32 * N + 64;
-	const size_t per_block = (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(SlZ) + (size_t)ws.fpar_cap * 16 + 256;
+	const size_t per_block = hd_ws_size(ws.w, N);
 	size_t fr = 0, tot = 0;
 	if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = (size_t)1 << 32; }
 	// the slices: at most sw_slice queries, and cells plus backtrack words (68 bytes a cell) in a quarter of the free memory, but one query at least
@@ -5294,7 +5341,7 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 	const int64_t max_q = std::max<int64_t>(1, h->tn.sw_slice > 0 ? h->tn.sw_slice : RB3_SW_SLICE);
 	const int64_t budget = std::max<int64_t>((int64_t)1 << 20, (int64_t)(fr / 4)) / cell_bytes;
 	std::vector<int64_t> cell_off((size_t)n_query), cuts(1, 0);
-	int64_t max_cells = 0, max_nodes = 0;
+	int64_t max_cells = 0, max_nodes = 0, slice = 0;
 	{
 		int64_t cells = 0;
 		for (int64_t q = 0; q < n_query; ++q) {
@@ -5303,166 +5350,59 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 			cell_off[q] = cells, cells += c;
 			max_cells = std::max(max_cells, cells);
 			max_nodes = std::max(max_nodes, node_off[q + 1] - node_off[cuts.back()]);
+			slice = std::max(slice, q + 1 - cuts.back());
 		}
 		cuts.push_back(n_query);
 	}
-	int64_t slice = 0;
-	for (size_t i = 0; i + 1 < cuts.size(); ++i) slice = std::max(slice, cuts[i + 1] - cuts[i]);
 	const size_t fixed = (size_t)n_nodes * 9 + (size_t)n_edges * 4 + (size_t)n_query * 16 + (size_t)max_cells * cell_bytes + (size_t)max_nodes * 4 + (size_t)slice * 128 + ((size_t)64 << 20);
 	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
 	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
 	SwHostWs hw;
-	LocWs lws;
-	if (with_pos) {
-		const int r = loc_init(h, lws, std::min<int64_t>(slice, RB3_LOC_SLICE_IV), false);
-		if (r < 0) return r;
-	}
-	auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes + 64); if (e == hipSuccess) hw.dv.push_back(*p); return e; };
 	uint8_t *d_nsym = nullptr;
-	int64_t *d_noff = nullptr, *d_poff = nullptr, *d_coff = nullptr, *d_hoff = nullptr, *d_soff = nullptr;
+	int64_t *d_noff = nullptr, *d_poff = nullptr, *d_coff = nullptr;
 	int32_t *d_pre = nullptr, *d_node = nullptr, *h_node = nullptr;
-	uint32_t *d_flag = nullptr, *d_cnt = nullptr;
-	SwRaw *d_raw = nullptr;
-	unsigned long long *d_ctr = nullptr;
-	void *d_tmp = nullptr;
-	size_t tmp_bytes = 0;
-	HIPCHK(dalloc((void**)&d_nsym, (size_t)n_nodes));
-	HIPCHK(dalloc((void**)&d_noff, (size_t)(n_query + 1) * 8));
-	HIPCHK(dalloc((void**)&d_poff, (size_t)(n_nodes + 1) * 8));
-	HIPCHK(dalloc((void**)&d_pre, (size_t)n_edges * 4));
-	HIPCHK(dalloc((void**)&d_coff, (size_t)n_query * 8));
-	HIPCHK(dalloc((void**)&d_flag, (size_t)(slice + 1) * 4));
-	HIPCHK(dalloc((void**)&d_cnt, (size_t)(slice + 1) * 4));
-	HIPCHK(dalloc((void**)&d_hoff, (size_t)(slice + 1) * 8));
-	HIPCHK(dalloc((void**)&d_soff, (size_t)(slice + 1) * 8));
-	HIPCHK(dalloc((void**)&d_raw, (size_t)slice * sizeof(SwRaw)));
-	HIPCHK(dalloc((void**)&d_node, (size_t)slice * 4));
-	HIPCHK(dalloc((void**)&d_ctr, 64));
-	HIPCHK(dalloc((void**)&ws.cells, (size_t)max_cells * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.bt, (size_t)max_cells * 12));
-	HIPCHK(dalloc((void**)&ws.ncnt, (size_t)max_nodes * 4));
-	HIPCHK(dalloc((void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
-	HIPCHK(dalloc((void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
-	HIPCHK(dalloc((void**)&ws.heap, (size_t)nb * N * 4));
-	HIPCHK(dalloc((void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(SlZ)));
-	HIPCHK(dalloc((void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
-	{
-		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, slice + 1, h->st);
-		if (r < 0) return scan_err(r);
-		HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
-	}
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_nsym, (size_t)n_nodes));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_noff, (size_t)(n_query + 1) * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_poff, (size_t)(n_nodes + 1) * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_pre, (size_t)n_edges * 4));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_coff, (size_t)n_query * 8));
+	HIPCHK(dv_alloc(hw.dv, (void**)&d_node, (size_t)slice * 4));
+	HIPCHK(dv_alloc(hw.dv, (void**)&ws.cells, (size_t)max_cells * sizeof(HdCell)));
+	HIPCHK(dv_alloc(hw.dv, (void**)&ws.w.bt, (size_t)max_cells * 12));
+	HIPCHK(dv_alloc(hw.dv, (void**)&ws.ncnt, (size_t)max_nodes * 4));
+	if (const int e = hd_ws_alloc(h, hw.dv, ws.w, nb, N)) return e;
+	if (const int e = sw_slice_bufs(h, hw, slice)) return e;
 	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 8, hipHostMallocDefault)); // (the flags of the slice, then the nodes of its hits)
 	h_node = hw.h_nhit + slice;
-	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
-	HIPCHK(hipHostMalloc((void**)&hw.h_tot, 64, hipHostMallocDefault));
-	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&hw.e[i]));
 	HIPCHK(hipMemcpyAsync(d_nsym, node_sym, (size_t)n_nodes, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_noff, node_off, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_poff, pre_off, (size_t)(n_nodes + 1) * 8, hipMemcpyHostToDevice, h->st));
 	if (n_edges > 0) HIPCHK(hipMemcpyAsync(d_pre, pre, (size_t)n_edges * 4, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_coff, cell_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
-	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
 	const Acc7 acc = acc7_of(h);
 	HdOpt o;
 	o.N = (int32_t)N, o.min_sc = opt->min_sc, o.ma = opt->match, o.mi = opt->mis, o.go = opt->gap_open, o.ge = opt->gap_ext, o.drop = -1, o.k = 0;
-	double ms_dp = 0, ms_bt = 0;
-	int64_t n_hits = 0, n_steps = 0, n_slices = 0;
-	std::vector<rb3gpu_sw_hit_t> hits;
-	std::vector<rb3gpu_pos_t> pairs;
-	int ret = 0;
-	for (size_t ci = 0; ci + 1 < cuts.size() && ret == 0; ++ci, ++n_slices) {
-		const int64_t q0 = cuts[ci], q1 = cuts[ci + 1], nq = q1 - q0;
-		HIPCHK(hipMemsetAsync(d_flag + nq, 0, 4, h->st)); // (the scans are exclusive: their last element is the total)
-		HIPCHK(hipMemsetAsync(d_cnt + nq, 0, 4, h->st));
-		HIPCHK(hipEventRecord(hw.e[0], h->st));
-		hipLaunchKernelGGL(k_swl_fill, dim3((unsigned)std::min(nb, nq)), dim3(64), 0, h->st, ix, acc, (const int64_t*)d_noff, (const uint8_t*)d_nsym, (const int64_t*)d_poff, (const int32_t*)d_pre,
-				n_edges, (const int64_t*)d_coff, q0, q1, o, (int)std::min<int64_t>(opt->end_len, 0x7fffffff), ws, lds_slots, d_flag, d_cnt, d_raw, d_node, d_ctr);
-		HIPCHK(hipEventRecord(hw.e[1], h->st));
-		size_t tb = tmp_bytes + 256;
-		int r = rb3kount_scan(d_tmp, &tb, d_flag, d_hoff, nq + 1, h->st);
-		if (r == 0) tb = tmp_bytes + 256, r = rb3kount_scan(d_tmp, &tb, d_cnt, d_soff, nq + 1, h->st);
-		if (r < 0) return scan_err(r);
-		HIPCHK(hipMemcpyAsync(hw.h_tot, d_hoff + nq, 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_tot + 1, d_soff + nq, 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_nhit, d_flag, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(h_node, d_node, (size_t)nq * 4, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		HIPCHK(hipGetLastError());
-		ms_dp += ev_ms(hw.e[0], hw.e[1]);
-		if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a query could not be represented: no record of this slice goes out
-		const int64_t nh = hw.h_tot[0], ns = hw.h_tot[1];
-		if (nh < 0 || nh > nq || ns < 0) return RB3GPU_EINTERNAL;
+	const int end_len = (int)std::min<int64_t>(opt->end_len, 0x7fffffff);
+	auto fill = [&](int64_t q0, int64_t q1) {
+		hipLaunchKernelGGL(k_swl_fill, dim3((unsigned)std::min(nb, q1 - q0)), dim3(64), 0, h->st, ix, acc, (const int64_t*)d_noff, (const uint8_t*)d_nsym, (const int64_t*)d_poff, (const int32_t*)d_pre,
+				n_edges, (const int64_t*)d_coff, q0, q1, o, end_len, ws, lds_slots, hw.d_flag, hw.d_cnt, hw.d_raw, d_node, hw.d_ctr);
+	};
+	auto after = [&](int64_t q0, int64_t nq) { // a query has a hit iff it has a node for it: that node to the caller
 		for (int64_t q = 0; q < nq; ++q) {
-			if ((hw.h_nhit[q] != 0) != (h_node[q] >= 0) || hw.h_nhit[q] < 0 || hw.h_nhit[q] > 1 || h_node[q] >= node_off[q0 + q + 1] - node_off[q0 + q]) return RB3GPU_EINTERNAL;
+			if ((hw.h_nhit[q] != 0) != (h_node[q] >= 0) || hw.h_nhit[q] < 0 || hw.h_nhit[q] > 1 || h_node[q] >= node_off[q0 + q + 1] - node_off[q0 + q]) return (int)RB3GPU_EINTERNAL;
 			hit_node[q0 + q] = h_node[q];
 		}
-		hits.resize((size_t)nh);
-		pairs.clear();
-		if (nh > 0) {
-			if (nh > hw.hit_cap) {
-				const int64_t c = std::max(nh, std::min(slice, 2 * hw.hit_cap));
-				if (hw.d_hits) { HIPCHK(hipFree(hw.d_hits)); hw.d_hits = nullptr; }
-				if (hw.h_hits) { HIPCHK(hipHostFree(hw.h_hits)); hw.h_hits = nullptr; }
-				hw.hit_cap = 0;
-				HIPCHK(hipMalloc(&hw.d_hits, (size_t)c * sizeof(SwRaw)));
-				HIPCHK(hipHostMalloc((void**)&hw.h_hits, (size_t)c * sizeof(SwRaw), hipHostMallocDefault));
-				hw.hit_cap = c;
-			}
-			if (ns > hw.step_cap) {
-				const int64_t c = std::max(ns, 2 * hw.step_cap);
-				if (hw.d_steps) { HIPCHK(hipFree(hw.d_steps)); hw.d_steps = nullptr; }
-				if (hw.h_steps) { HIPCHK(hipHostFree(hw.h_steps)); hw.h_steps = nullptr; }
-				hw.step_cap = 0;
-				HIPCHK(hipMalloc(&hw.d_steps, (size_t)c + 64));
-				HIPCHK(hipHostMalloc((void**)&hw.h_steps, (size_t)c + 64, hipHostMallocDefault));
-				hw.step_cap = c;
-			}
-			HIPCHK(hipEventRecord(hw.e[2], h->st));
-			hipLaunchKernelGGL(k_swl_emit, dim3((unsigned)std::min<int64_t>((nq + 255) / 256, 16384)), dim3(256), 0, h->st, (const int64_t*)d_noff, (const uint8_t*)d_nsym, (const int64_t*)d_coff,
-					q0, (int)N, (const uint32_t*)ws.bt, nq, (const uint32_t*)d_flag, (const SwRaw*)d_raw, (const int32_t*)d_node, (const int64_t*)d_hoff, (const int64_t*)d_soff, hw.d_hits, hw.d_steps, d_ctr);
-			HIPCHK(hipEventRecord(hw.e[3], h->st));
-			HIPCHK(hipMemcpyAsync(hw.h_hits, hw.d_hits, (size_t)nh * sizeof(SwRaw), hipMemcpyDeviceToHost, h->st));
-			if (ns > 0) HIPCHK(hipMemcpyAsync(hw.h_steps, hw.d_steps, (size_t)ns, hipMemcpyDeviceToHost, h->st));
-			HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
-			HIPCHK(hipStreamSynchronize(h->st));
-			HIPCHK(hipGetLastError());
-			ms_bt += ev_ms(hw.e[2], hw.e[3]);
-			if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL;
-			for (int64_t i = 0; i < nh; ++i) {
-				const SwRaw &x = hw.h_hits[i];
-				rb3gpu_sw_hit_t &y = hits[(size_t)i];
-				y.lo = x.lo, y.hi = x.hi, y.score = x.score, y.qlen = x.qlen, y.rlen = x.rlen, y.n_steps = x.n_steps, y.step_off = x.step_off, y.pos_off = 0, y.n_pos = 0;
-				if (x.n_steps < 0 || x.step_off < 0 || x.step_off + x.n_steps > ns) return RB3GPU_EINTERNAL;
-			}
-			if (with_pos) { // the intervals of the hits, read where k_swl_emit left them (bwa-sw.c:547-556 with one hit per query)
-				for (int64_t r0 = 0; r0 < nh;) {
-					const int64_t lim = std::min(nh - r0, lws.n_cap);
-					lws.h_size.resize((size_t)lim);
-					for (int64_t i = 0; i < lim; ++i) lws.h_size[i] = hits[(size_t)(r0 + i)].hi - hits[(size_t)(r0 + i)].lo;
-					const int64_t nn = loc_slice_end(lws, lws.h_size.data(), 0, lim, loc_cap);
-					lws.h_size.resize((size_t)nn);
-					const int lr = loc_slice(h, lws, nn, (const int64_t*)(hw.d_hits + r0), (int)(sizeof(SwRaw) / 8), 0, loc_cap);
-					if (lr < 0) return lr;
-					const int64_t base = (int64_t)pairs.size(), np = lws.h_off[(size_t)nn];
-					if (np > 0) pairs.insert(pairs.end(), (const rb3gpu_pos_t*)lws.h_pairs, (const rb3gpu_pos_t*)lws.h_pairs + np);
-					for (int64_t i = 0; i < nn; ++i) {
-						rb3gpu_sw_hit_t &y = hits[(size_t)(r0 + i)];
-						y.pos_off = base + lws.h_off[(size_t)i], y.n_pos = std::min<int64_t>(loc_cap, y.hi - y.lo);
-						if (lws.h_off[(size_t)i + 1] - lws.h_off[(size_t)i] < y.n_pos) return RB3GPU_EINTERNAL;
-					}
-					r0 += nn;
-				}
-			}
-		}
-		n_hits += nh, n_steps += ns;
-		ret = cb(ud, q0, nq, hw.h_nhit, hits.data(), hw.h_steps, pairs.data());
-	}
-	if (st) st->sw.ms_total = (now_s() - t0) * 1e3, st->sw.ms_dp = ms_dp, st->sw.ms_backtrack = ms_bt, st->sw.n_ext = (int64_t)hw.h_ctr[0], st->sw.n_hits = n_hits, st->sw.n_steps = n_steps,
-		st->sw.n_tier2 = (int64_t)hw.h_ctr[1], st->sw.n_slices = n_slices, st->n_nodes = n_nodes, st->n_edges = n_edges;
-	if (with_pos) loc_stats(lws, t0, lst);
+		return 0;
+	};
+	auto emit = [&](int64_t q0, int64_t nq) {
+		hipLaunchKernelGGL(k_swl_emit, dim3((unsigned)std::min<int64_t>((nq + 255) / 256, 16384)), dim3(256), 0, h->st, (const int64_t*)d_noff, (const uint8_t*)d_nsym, (const int64_t*)d_coff,
+				q0, (int)N, (const uint32_t*)ws.w.bt, nq, (const uint32_t*)hw.d_flag, (const SwRaw*)hw.d_raw, (const int32_t*)d_node, (const int64_t*)hw.d_hoff, (const int64_t*)hw.d_soff, hw.d_hits, hw.d_steps, hw.d_ctr);
+	};
+	int ret = 0;
+	if (const int e = sw_slices(h, hw, cuts, 1, {{hw.d_flag, hw.h_nhit}, {d_node, h_node}}, opt->max_pos, // (one slot per query: its flag is its number of hits)
+			 t0, fill, after, emit, cb, ud, &ret, st ? &st->sw : nullptr, lst)) return e;
+	if (st) st->n_nodes = n_nodes, st->n_edges = n_edges;
 	return ret;
 }
 

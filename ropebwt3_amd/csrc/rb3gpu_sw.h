@@ -2,8 +2,8 @@
  * rb3gpu_sw.h -- end-to-end alignments of whole queries against the index with the alignment written out (`sw -e`, `--all-e2e`, `-g`: the
  * reference's sw_core on a linear query, bwa-sw.c:329-526, and its sw_backtrack / sw_backtrack1_core, bwa-sw.c:76-114, 218-253).
  *
- * The dynamic program is that of `hapdiv` (hd_rows of rb3gpu_hapdiv.h: one row loop for both), with three differences: a query has its own
- * length, mismatches and gaps start after end_len symbols, and a cell of the backtrack matrix keeps its base (bits 5-7 of its third word; the
+ * The dynamic program is that of `hapdiv` (hd_rows of rb3gpu_hapdiv.h: one row loop for both, over the row step that `sw --local` uses
+ * too), with three differences: a query has its own length, mismatches and gaps start after end_len symbols, and a cell of the backtrack matrix keeps its base (bits 5-7 of its third word; the
  * matrix stays at 12 bytes a cell and the F column keeps its 24 bits).  The matrices of ALL queries of a slice stay in global memory, query q
  * at cell bt_off[q] (a prefix sum of (len + 1) * N over the slice), because the alignments are written in a second pass:
  *
@@ -15,8 +15,9 @@
  *               0 `=`, 1 `X`, 2 `I`, 3 `D`, in the order sw_backtrack1_core pushes them: the first byte is query position 0.  `=` is
  *               "base equals the query's symbol", so N against N is `=`.
  *
- * A walk that leaves the matrix, runs too long or needs an F column that was not kept raises ctr[2] like everything hd_rows cannot
- * represent, and the call fails.
+ * sw_walk is the one backtrack of this file and of rb3gpu_swlocal.h: it is told the rows of the matrix, the cell to start from and how to read the
+ * query's symbol of a row.  A walk that leaves the matrix, runs longer than rows * (N + 1) steps or needs an F column that was not kept raises ctr[2]
+ * like everything hd_rows cannot represent, and the call fails.
  */
 #ifndef RB3GPU_SW_H
 #define RB3GPU_SW_H
@@ -25,18 +26,25 @@
 
 struct SwRaw { int64_t lo, hi; int32_t score, qlen, rlen, n_steps; int64_t step_off; };   // 40 bytes; the host reads (lo, hi) of the dense array with stride 5
 
-/* the walk from column c of the last row of a query of k symbols q[] to the root.  EMIT: one byte per step to out.  Returns the steps, -1 if
- * the walk cannot be represented (or, EMIT, needs more than `room` bytes); qlen / rlen: symbols of the query / of the index it consumed */
-template<bool EMIT>
-__device__ static int sw_walk(const uint32_t *bt, int N, int k, const uint8_t *q, int c, uint8_t *out, uint32_t room, int &qlen, int &rlen)
+/* how the walk reads the symbol of row r of the query q[0, k): its last r symbols are aligned there */
+struct SwQrySym {
+	const uint8_t *q; int k;
+	__device__ __forceinline__ int operator()(uint32_t r) const { return min((int)q[k - (int)r], 5); }
+};
+
+/* the walk from cell `pos` (row * N + column) of a matrix of `rows` rows to the root; sym(r): the query's symbol of row r (SwQrySym here, the node's symbol
+ * in rb3gpu_swlocal.h).  EMIT: one byte per step to out.  Returns the steps, -1 if the walk cannot be represented -- it leaves the matrix, takes more
+ * than the rows * (N + 1) steps of the longest walk there is (every row once, and its N columns through gaps of the index side) or, EMIT, more than
+ * `room` bytes; qlen / rlen: symbols of the query / of the index it consumed */
+template<bool EMIT, class Sym>
+__device__ static int sw_walk(const uint32_t *bt, int N, int64_t rows, uint32_t pos, const Sym sym, uint8_t *out, uint32_t room, int &qlen, int &rlen)
 {
-	const uint32_t total = (uint32_t)(k + 1) * (uint32_t)N;
-	const uint32_t limit = (uint32_t)(k + 1) * ((uint32_t)min(N, 1 << 20) + 1u);
-	uint32_t pos = (uint32_t)k * (uint32_t)N + (uint32_t)c, steps = 0;
+	const uint64_t total = (uint64_t)rows * (uint32_t)N, limit = (uint64_t)rows * ((uint64_t)N + 1);
+	uint64_t steps = 0;
 	int last = 0;
 	qlen = rlen = 0;
 	while (pos > 0) {
-		if (pos >= total || steps >= limit) return -1;
+		if (pos >= total || steps >= limit || steps >= 0x7fffffffu) return -1;
 		const uint32_t r = pos / (uint32_t)N, m = bt[(size_t)pos * 3 + 2];
 		const int state = last == 0 ? (int)(m & 3u) : last;
 		const int gext = state == 1 ? (int)(m >> 2 & 1u) : state == 2 ? (int)(m >> 3 & 1u) : 0;
@@ -46,7 +54,7 @@ __device__ static int sw_walk(const uint32_t *bt, int N, int k, const uint8_t *q
 		if (state == 0) {
 			np = bt[(size_t)pos * 3];
 			if (np >= r * (uint32_t)N) return -1;
-			op = base == min((int)q[k - (int)r], 5) ? 0 : 1, ++qlen, ++rlen;
+			op = base == sym(r) ? 0 : 1, ++qlen, ++rlen;
 		} else if (state == 1) {
 			np = bt[(size_t)pos * 3 + 1];
 			if (np >= r * (uint32_t)N) return -1;
@@ -80,17 +88,9 @@ __global__ void __launch_bounds__(64) k_sw_fill(IdxView ix, Acc7 acc, const uint
 	const int lane = threadIdx.x;
 	const int N = o.N;
 	const int64_t b = blockIdx.x;
-	HdCell *gtab = ws.tab + b * ws.tab_cap;
-	const bool small = N <= HD_LDS_N;
-	HdCell *row = small ? s_row : ws.row + b * N;
-	HdExt *ext = small ? s_ext : ws.ext + b * 5 * N;
-	int32_t *heap = small ? s_heap : ws.heap + b * N;
-	HdZ *stack = ws.stack + b * ws.stack_cap;
-	int64_t *fpar = ws.fpar + b * 2 * ws.fpar_cap;
-	int bits0 = 2;
-	while ((1 << bits0) < 4 * N) ++bits0;
+	const HdBlk B = hd_blk(ws, b, N, lds_slots, s_tab, s_row, s_ext, s_heap, &s_T, &s_err);
+	const HdCell *row = B.row;
 	unsigned long long n_ext = 0, n_t2 = 0;
-	const HdLds L = { s_tab, &s_T, &s_err };
 
 	for (int64_t w = q0 + b; w < q1; w += gridDim.x) {
 		const uint8_t *q = sym + qoff[w];
@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(64) k_sw_fill(IdxView ix, Acc7 acc, const uint
 		const int64_t slot0 = (w - q0) * N;
 		int best_sc = 0, n = 0, hits = 0;
 		bool done = true;
-		if (k > 0) n = hd_rows<true>(ix, acc, q, k, end_len, o, ws, gtab, row, ext, heap, stack, fpar, bt, L, lds_slots, bits0, n_ext, best_sc, done);
+		if (k > 0) n = hd_rows<true>(ix, acc, q, k, end_len, o, B, bt, n_ext, best_sc, done);
 		else { // (no rows: no hits)
 			__syncthreads();
 			if (lane == 0) s_err = 0;
@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(64) k_sw_fill(IdxView ix, Acc7 acc, const uint
 				hit = !(x.fl & HD_FLT) && (x.fl & 3u) == 0 && x.H >= o.min_sc && (o.drop < 0 || h0 - x.H <= o.drop);
 				if (hit) {
 					int ql, rl;
-					const int steps = sw_walk<false>(bt, N, k, q, c, nullptr, 0u, ql, rl);
+					const int steps = sw_walk<false>(bt, N, (int64_t)k + 1, (uint32_t)k * (uint32_t)N + (uint32_t)c, SwQrySym{q, k}, nullptr, 0u, ql, rl);
 					if (steps < 0) atomicOr(&s_err, 1), hit = false;
 					else r.lo = x.lo, r.hi = x.hi, r.score = x.H, r.qlen = ql, r.rlen = rl, r.n_steps = steps;
 				}
@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(256) k_sw_emit(const uint8_t *sym, const int64
 		SwRaw r = raw[s];
 		int ql, rl;
 		r.step_off = soff[s];
-		const int n = sw_walk<true>(bt + bt_off[w] * 3, N, k, sym + qoff[w], c, steps + soff[s], (uint32_t)r.n_steps, ql, rl);
+		const int n = sw_walk<true>(bt + bt_off[w] * 3, N, (int64_t)k + 1, (uint32_t)k * (uint32_t)N + (uint32_t)c, SwQrySym{sym + qoff[w], k}, steps + soff[s], (uint32_t)r.n_steps, ql, rl);
 		if (n != r.n_steps || ql != r.qlen || rl != r.rlen) atomicAdd(ctr + 2, 1ull); // (the same walk twice: cannot happen)
 		out[hoff[s]] = r;
 	}

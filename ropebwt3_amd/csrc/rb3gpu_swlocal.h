@@ -3,8 +3,9 @@
  * general form, bwa-sw.c:329-526, and the backtrack of its one best hit, bwa-sw.c:76-114, 154-195, 254-258).
  *
  * The rows of the dynamic program are the NODES of the query's directed acyclic word graph (host/dawg.c), in topological order; a node has a
- * symbol and a list of predecessors, any earlier nodes.  So, against the linear program of rb3gpu_hapdiv.h (hd_rows), whose table, growth,
- * selection, extension and heap are used as they are:
+ * symbol and a list of predecessors, any earlier nodes.  The table, growth, selection, extension, heap and the whole row step of rb3gpu_hapdiv.h
+ * (hd_tab_clear, hd_stage_ext, hd_cands, hd_fphase, hd_store_bt) are used as they are, and the backtrack is sw_walk of rb3gpu_sw.h; this file keeps
+ * what the graph adds to the linear program (hd_rows):
  *   - the kept cells of EVERY node of a query stay in global memory (n_node * N cells of 56 bytes from cell_off[q] on, their count per node
  *     beside them), because any later node may read them; the 12-byte backtrack words lie beside them as in `sw -e`, word node * N + column;
  *   - a node with several predecessors whose cells number more than N drops what cannot reach its best N: max_min_sc is the (N + 1)-th largest
@@ -12,9 +13,9 @@
  *   - candidates arrive predecessor by predecessor in list order, cell by cell in column order; a predecessor's cells are staged in the row
  *     buffer, extended an octet per cell, and merged by lane 0.  (A node's cells are extended once per successor here; the reference keeps
  *     the extensions in a cache: DESIGN.md 7h);
- *   - a cell carries the symbols of the query it has consumed (HdCell.pad; the larger stays when two candidates meet), and a mismatch, a gap
- *     of the index side and the F phase are allowed by that number, not by the row: the F phase of a node runs iff the LAST predecessor cell
- *     the loops visited has consumed end_len symbols, cut or not.
+ *   - the symbols of the query a cell has consumed (HdCell.pad; the larger stays when two candidates meet) differ within a row, so the rule that
+ *     hd_rows states by row is stated by cell: the F phase of a node runs iff the LAST predecessor cell the loops visited (what hd_cands
+ *     returns) has consumed end_len symbols, cut or not.
  * The hit of a query is column 0 of the first node whose best H is above that of every node before it, if that H reaches min_sc.
  *
  *   k_swl_fill   a wave per query, queries by grid stride: the nodes, then lane 0 walks from the best cell back to the root and COUNTS the steps:
@@ -32,54 +33,16 @@
 
 #include "rb3gpu_sw.h"
 
-struct SlZ { int64_t lo, hi, lo_rc; int32_t H, F, qlen, pad; };
 struct SlWs {
-	HdCell *cells; uint32_t *bt; int32_t *ncnt;   // of the slice: cells and 3 words per cell from cell_off[q] on, counts per node of the slice
-	HdCell *tab; int64_t tab_cap;                 // per block, as HdWs
-	HdCell *row;                                  // N
-	HdExt *ext;                                   // 5 N
-	int32_t *heap;                                // N
-	SlZ *stack; int64_t stack_cap;
-	int64_t *fpar; int64_t fpar_cap;              // pairs
+	HdWs w;                          // the per-block arrays as everywhere; w.bt: 3 words per cell of the slice, query q from cell_off[q] on (w.bt_stride is not used)
+	HdCell *cells; int32_t *ncnt;    // of the slice: the cells from cell_off[q] on, their counts per node of the slice
 };
 
-/* the walk from cell `pos` (node * N + column) of a query of n_node nodes with symbols nsym[] to the root; as sw_walk of rb3gpu_sw.h */
-template<bool EMIT>
-__device__ static int sl_walk(const uint32_t *bt, int N, int64_t n_node, const uint8_t *nsym, uint32_t pos, uint8_t *out, uint32_t room, int &qlen, int &rlen)
-{
-	const uint64_t total = (uint64_t)n_node * (uint32_t)N, limit = (uint64_t)n_node * ((uint64_t)N + 1);
-	uint64_t steps = 0;
-	int last = 0;
-	qlen = rlen = 0;
-	while (pos > 0) {
-		if (pos >= total || steps >= limit || steps >= 0x7fffffffu) return -1;
-		const uint32_t r = pos / (uint32_t)N, m = bt[(size_t)pos * 3 + 2];
-		const int state = last == 0 ? (int)(m & 3u) : last;
-		const int gext = state == 1 ? (int)(m >> 2 & 1u) : state == 2 ? (int)(m >> 3 & 1u) : 0;
-		const int base = (int)(m >> 5 & 7u);
-		uint32_t np = 0;
-		int op;
-		if (state == 0) {
-			np = bt[(size_t)pos * 3];
-			if (np >= r * (uint32_t)N) return -1;
-			op = base == (int)nsym[r] ? 0 : 1, ++qlen, ++rlen;
-		} else if (state == 1) {
-			np = bt[(size_t)pos * 3 + 1];
-			if (np >= r * (uint32_t)N) return -1;
-			op = 2, ++qlen;
-		} else if (state == 2 && (m & 16u) && (m >> 8) < (uint32_t)N) {
-			np = r * (uint32_t)N + (m >> 8);
-			op = 3, ++rlen;
-		} else return -1;
-		if (EMIT) {
-			if (steps >= room) return -1;
-			out[steps] = (uint8_t)(op << 4 | base);
-		}
-		++steps;
-		pos = np, last = gext ? state : 0;
-	}
-	return (int)steps;
-}
+/* how sw_walk reads the symbol of row r: that of node r */
+struct SlNodeSym {
+	const uint8_t *nsym;
+	__device__ __forceinline__ int operator()(uint32_t r) const { return (int)nsym[r]; }
+};
 
 /* cells of the predecessors [p0, p1) of pre[] whose H is at least v (all lanes; the same number in every lane) */
 __device__ static int sl_count_ge(const HdCell *cells, const int32_t *ncnt, const int32_t *pre, int64_t p0, int64_t p1, int N, int32_t v, int lane)
@@ -95,7 +58,7 @@ __device__ static int sl_count_ge(const HdCell *cells, const int32_t *ncnt, cons
 }
 
 /* queries [q0, q1): query q owns the nodes [node_off[q], node_off[q + 1]) of nsym[] and pre_off[] (pre_off has one more entry than there are nodes and
- * names places of pre[0, n_pre_all), whose entries are node numbers within the query); its cells start at cell_off[q] of ws.cells / ws.bt, its counts at
+ * names places of pre[0, n_pre_all), whose entries are node numbers within the query); its cells start at cell_off[q] of ws.cells / ws.w.bt, its counts at
  * node_off[q] - node_off[q0] of ws.ncnt.  Per query of the slice flag, cnt, raw, node (every one is written).  ctr as k_sw_fill */
 __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int64_t *node_off, const uint8_t *nsym, const int64_t *pre_off, const int32_t *pre, int64_t n_pre_all,
 		const int64_t *cell_off, int64_t q0, int64_t q1, HdOpt o, int end_len, SlWs ws, int lds_slots, uint32_t *flag, uint32_t *cnt, SwRaw *raw, int32_t *node,
@@ -107,18 +70,11 @@ __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int
 	__shared__ int32_t s_heap[HD_LDS_N];
 	__shared__ HdTab s_T;
 	__shared__ int32_t s_err, s_lastq;
-	const int lane = threadIdx.x, j8 = lane & 7, oct = lane >> 3;
+	const int lane = threadIdx.x;
 	const int N = o.N;
 	const int64_t b = blockIdx.x;
-	HdCell *gtab = ws.tab + b * ws.tab_cap;
-	const bool small = N <= HD_LDS_N;
-	HdCell *row = small ? s_row : ws.row + b * N;
-	HdExt *ext = small ? s_ext : ws.ext + b * 5 * N;
-	int32_t *heap = small ? s_heap : ws.heap + b * N;
-	SlZ *stack = ws.stack + b * ws.stack_cap;
-	int64_t *fpar = ws.fpar + b * 2 * ws.fpar_cap;
-	int bits0 = 2;
-	while ((1 << bits0) < 4 * N) ++bits0;
+	const HdBlk B = hd_blk(ws.w, b, N, lds_slots, s_tab, s_row, s_ext, s_heap, &s_T, &s_err);
+	HdCell *const row = B.row;
 	unsigned long long n_ext = 0, n_t2 = 0;
 	const int64_t node0 = node_off[q0];
 
@@ -127,23 +83,15 @@ __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int
 		const uint8_t *sym = nsym + g0;
 		const int64_t *poff = pre_off + g0;
 		HdCell *cells = ws.cells + cell_off[w];
-		uint32_t *bt = ws.bt + cell_off[w] * 3;
+		uint32_t *bt = ws.w.bt + cell_off[w] * 3;
 		int32_t *ncnt = ws.ncnt + (g0 - node0);
 		int32_t best = 0;
 		uint32_t best_pos = 0;
 		bool done = n_node >= 1 && (uint64_t)n_node * (uint32_t)N < 0xFFFFFFFFull;
 		__syncthreads();
 		if (lane == 0) {
-			HdTab T;
-			T.bits = bits0, T.count = 0, T.ub = HD_USED_A;
-			T.tier = (1 << bits0) > lds_slots ? 1 : 0;
-			T.t = T.tier ? gtab : s_tab;
-			s_T = T, s_err = 0, s_lastq = 0;
-			if (done) {
-				HdCell r;
-				r.lo = 0, r.hi = acc.a[6], r.lo_rc = 0, r.H = r.E = r.F = 0, r.H_pos = r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 0, r.pad = 0;
-				cells[0] = r, ncnt[0] = 1;
-			}
+			hd_tab_init(B), s_lastq = 0;
+			if (done) cells[0] = hd_root(acc), ncnt[0] = 1;
 		}
 		if (done && lane < 3) bt[lane] = lane < 2 ? HD_NONE : 0u;
 		__syncthreads();
@@ -181,12 +129,7 @@ __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int
 				mm -= max(o.go + o.ge, o.mi);
 				mm = max(mm, 0);
 			}
-			{ // an empty table of the capacity it has grown to
-				HdCell *t = s_T.t;
-				const uint32_t cap = 1u << s_T.bits;
-				for (uint32_t s = lane; s < cap; s += 64) t[s].fl = 0;
-				if (lane == 0) s_T.count = 0;
-			}
+			hd_tab_clear(B, lane);
 			__syncthreads();
 			for (int64_t j = p0; j < p1; ++j) { // the candidates, predecessor by predecessor
 				const int32_t pid = pre[j], n = ncnt[pid];
@@ -197,53 +140,9 @@ __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int
 					for (int x = lane; x < n * (int)(sizeof(HdCell) / 4); x += 64) dst[x] = src[x];
 				}
 				__syncthreads();
-				for (int c0 = 0; c0 < n; c0 += 8) {
-					const int col = c0 + oct;
-					const bool act = col < n;
-					const int64_t lo = act ? row[col].lo : 0, hi = act ? row[col].hi : 0, rc = act ? row[col].lo_rc : 0;
-					HdExt e[5];
-					hd_extend(ix, lo, hi, rc, j8, e);
-					if (act && j8 < 5) {
-						HdExt v = e[0];
-#pragma unroll
-						for (int c = 1; c < 5; ++c) v = j8 == c ? e[c] : v;
-						ext[col * 5 + j8] = v;
-					}
-				}
+				hd_stage_ext(ix, B, n, lane);
 				__syncthreads();
-				if (lane == 0) {
-					HdTab T = s_T;
-					bool ok = true;
-					int ch;
-					for (int col = 0; col < n && ok; ++col) {
-						const HdCell p = row[col];
-						s_lastq = (int32_t)p.pad;
-						if (p.H + o.ma < mm) continue;
-						const uint32_t pos = (uint32_t)pid * (uint32_t)N + (uint32_t)col;
-						const bool inner = (int32_t)p.pad >= end_len;
-						int64_t last_rc = 0;
-						HdCell r;
-						r.E = r.F = 0, r.H_pos = pos, r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 0, r.pad = p.pad + 1;
-						for (int c = 1; c < 6 && ok; ++c) {
-							const HdExt e = ext[col * 5 + c - 1];
-							const int sc = c == cq && c != 5 ? o.ma : -o.mi;
-							if (e.hi == e.lo || p.H + sc <= 0 || p.H + sc < mm || (c != cq && !inner)) continue;
-							last_rc = e.rc;
-							r.lo = e.lo, r.hi = e.hi, r.lo_rc = e.rc, r.H = p.H + sc;
-							ok = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots) != nullptr;
-						}
-						int32_t ev = p.H - o.go > p.E ? p.H - o.go : p.E;
-						const uint32_t ef = p.H - o.go > p.E ? 0u : 4u;
-						ev -= o.ge;
-						if (ev > 0 && ev >= mm && inner && ok) {
-							r.lo = p.lo, r.hi = p.hi, r.lo_rc = last_rc, r.H = r.E = ev, r.F = 0, r.H_pos = HD_NONE, r.E_pos = pos, r.fl = 1u | ef;
-							ok = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots) != nullptr;
-						}
-					}
-					n_ext += n;
-					if (!ok) s_err = 1;
-					s_T = T;
-				}
+				if (lane == 0) s_lastq = hd_cands<true>(B, o, n, (uint32_t)pid * (uint32_t)N, cq, end_len, 0, mm, n_ext);
 				__syncthreads();
 				if (s_err) break;
 			}
@@ -255,93 +154,10 @@ __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int
 			}
 			int n = hd_top(s_T.t, 1u << s_T.bits, s_T.ub, N, row, lane);
 			__syncthreads();
-			int n_fpar = 0;
-			if (s_lastq >= end_len) { // the F phase of hd_rows; a candidate inherits the consumed symbols of the cell it leaves
-				HdTab T = s_T; // (used by lane 0)
-				int hsz = 0, next = 0, sp = 0;
-				bool ok = true;
-				if (lane == 0) for (int t = n - 1; t >= 0; --t) hd_heap_put(heap, hsz, N, row[t].H);
-				for (;;) {
-					SlZ z = {0, 0, 0, 0, 0, 0, 0};
-					int32_t f = 0, low = 0;
-					uint32_t ff = 0;
-					int go_on = 0;
-					if (lane == 0) {
-						while (ok) {
-							if (sp > 0) z = stack[--sp];
-							else if (next < n) {
-								const HdCell c = row[next++];
-								if (c.H <= o.go + o.ge) continue;
-								z.lo = c.lo, z.hi = c.hi, z.lo_rc = c.lo_rc, z.H = c.H, z.F = c.F, z.qlen = (int32_t)c.pad;
-							} else break;
-							low = hsz < N ? 0 : heap[0];
-							f = z.H - o.go > z.F ? z.H - o.go : z.F;
-							ff = z.H - o.go > z.F ? 0u : 8u;
-							f -= o.ge;
-							if (f > low) { go_on = 1; break; }
-						}
-					}
-					go_on = __shfl(go_on, 0);
-					if (!go_on) break;
-					const int64_t zlo = hd_shfl64(z.lo, 0), zhi = hd_shfl64(z.hi, 0), zrc = hd_shfl64(z.lo_rc, 0);
-					HdExt e[5];
-					hd_extend(ix, zlo, zhi, zrc, j8, e);
-					if (lane == 0) {
-						++n_ext;
-						for (int c = 0; c < 5 && ok; ++c) {
-							if (e[c].hi == e[c].lo) continue;
-							HdCell r;
-							r.lo = e[c].lo, r.hi = e[c].hi, r.lo_rc = e[c].rc, r.H = r.F = f, r.E = 0, r.H_pos = r.E_pos = HD_NONE, r.fpar = HD_UNSET, r.fl = 2u | ff, r.pad = (uint32_t)z.qlen;
-							int ch;
-							HdCell *qc = hd_merge(T, r, ch, gtab, ws.tab_cap, lds_slots);
-							if (qc == nullptr) { ok = false; break; }
-							if (!(ch & 4)) continue;
-							hd_heap_put(heap, hsz, N, f);
-							if (n_fpar >= ws.fpar_cap || n_fpar >= (int)HD_UNSET) { ok = false; break; }
-							fpar[2 * n_fpar] = z.lo, fpar[2 * n_fpar + 1] = z.hi;
-							qc->fl = (qc->fl & ~8u) | ff, qc->fpar = (uint32_t)n_fpar++;
-							if (f - o.ge > low) {
-								if (sp >= ws.stack_cap) { ok = false; break; }
-								SlZ y;
-								y.lo = qc->lo, y.hi = qc->hi, y.lo_rc = qc->lo_rc, y.H = qc->H, y.F = qc->F, y.qlen = (int32_t)qc->pad, y.pad = 0;
-								stack[sp++] = y;
-							}
-						}
-					}
-				}
-				if (lane == 0) {
-					s_T = T;
-					if (!ok) s_err = 1;
-				}
-				n_fpar = __shfl(n_fpar, 0);
-				__syncthreads();
-				if (s_err) { done = false; break; }
-				if (n_fpar > 0) {
-					n = hd_top(s_T.t, 1u << s_T.bits, s_T.ub, N, row, lane);
-					__syncthreads();
-					for (int c = lane; c < n; c += 64) {
-						if (row[c].F == 0 || row[c].fpar == HD_UNSET) continue;
-						const int64_t plo = fpar[2 * row[c].fpar], phi = fpar[2 * row[c].fpar + 1];
-						int at = -1;
-						for (int d = 0; d < n && at < 0; ++d)
-							if (row[d].lo == plo && row[d].hi == phi) at = d;
-						if (at >= 0) row[c].fpar = (uint32_t)at, row[c].fl |= HD_FSET;
-						else row[c].fpar = HD_UNSET;
-					}
-					__syncthreads();
-				}
-			}
+			if (s_lastq >= end_len && !hd_fphase<true>(ix, B, o, n, n_ext, lane)) { done = false; break; } // (by the LAST predecessor cell visited, cut or not)
 			if (row[0].H > best) best = row[0].H, best_pos = (uint32_t)i * (uint32_t)N;
-			for (int c = lane; c < n; c += 64) { // the cells for the nodes to come, and what the backtrack needs
-				const HdCell x = row[c];
-				int base = 0;
-#pragma unroll
-				for (int a = 1; a < 6; ++a) base = acc.a[a] <= x.lo ? a : base;
-				const uint32_t m = (x.fl & 15u) | (x.F != 0 && (x.fl & HD_FSET) ? 16u : 0u) | (uint32_t)base << 5 | (x.fpar & 0xFFFFFFu) << 8;
-				uint32_t *d = bt + ((size_t)i * N + c) * 3;
-				d[0] = x.H_pos, d[1] = x.E_pos, d[2] = m;
-				cells[(size_t)i * N + c] = x;
-			}
+			hd_store_bt<true>(acc, row, n, cq, bt + (size_t)i * N * 3, lane); // what the backtrack needs, and the cells for the nodes to come
+			for (int c = lane; c < n; c += 64) cells[(size_t)i * N + c] = row[c];
 			if (lane == 0) ncnt[i] = n;
 			__syncthreads();
 		}
@@ -352,7 +168,7 @@ __global__ void __launch_bounds__(64) k_swl_fill(IdxView ix, Acc7 acc, const int
 			bool hit = false;
 			if (done && !s_err && best >= o.min_sc) {
 				int ql, rl;
-				const int steps = sl_walk<false>(bt, N, n_node, sym, best_pos, nullptr, 0u, ql, rl);
+				const int steps = sw_walk<false>(bt, N, n_node, best_pos, SlNodeSym{sym}, nullptr, 0u, ql, rl);
 				if (steps < 0) s_err = 1;
 				else {
 					const HdCell x = cells[best_pos];
@@ -381,7 +197,7 @@ __global__ void __launch_bounds__(256) k_swl_emit(const int64_t *node_off, const
 		int ql = 0, rl = 0, n = -1;
 		r.step_off = soff[s];
 		if (node[s] >= 0 && node[s] < n_node)
-			n = sl_walk<true>(bt + cell_off[w] * 3, N, n_node, nsym + node_off[w], (uint32_t)node[s] * (uint32_t)N, steps + soff[s], (uint32_t)r.n_steps, ql, rl);
+			n = sw_walk<true>(bt + cell_off[w] * 3, N, n_node, (uint32_t)node[s] * (uint32_t)N, SlNodeSym{nsym + node_off[w]}, steps + soff[s], (uint32_t)r.n_steps, ql, rl);
 		if (n != r.n_steps || ql != r.qlen || rl != r.rlen) atomicAdd(ctr + 2, 1ull); // (the same walk twice: cannot happen)
 		out[hoff[s]] = r;
 	}
