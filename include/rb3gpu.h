@@ -602,6 +602,19 @@ typedef struct { int64_t start, size; } rb3gpu_suffix_rec_t;
 typedef struct { double ms_total, ms_walk; int64_t n_queries, n_symbols, n_steps, n_slices; } rb3gpu_suffix_stats_t;
 int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, rb3gpu_suffix_rec_t *out, rb3gpu_suffix_stats_t *st);
 
+/* does a query hold a seed: a stretch of at least min_len symbols that occurs in the index (rb3_fmd_smem_present, fm-index.c:483-498 and 530-538 of the reference,
+ * the test behind `sw -j`, bwa-sw.c:536-539)?  Query q as for rb3gpu_suffix gets present[q] = 1 if it does and 0 if not; a query of fewer than min_len symbols, an
+ * empty one among them, gets 0.  All six symbol codes are extended as they come: an N of the query matches an indexed N.  Any index serves, one strand or both.
+ * A window of min_len symbols is walked from its last symbol to its first with the step of rb3gpu_suffix; where the interval empties at symbol i the next window
+ * starts at i + 1, as in the reference.  A query is cut into walkers of `chunk` window starts each (0: rb3gpu_tune "seed_chunk", default 2048), an octet of
+ * lanes per walker; the answer is the OR of the walkers' and does not depend on chunk.  rb3gpu_tune "seed_slice": walkers per launch
+ * (default 1 M).  The call holds the symbols, 9 bytes per query and 16 per walker of a slice on the device.  RB3GPU_EINVAL for min_len < 2 (at 1 the reference's
+ * loop answers 1 for any query that is not empty, whatever the index holds) and for a query of 2^31 symbols or more; RB3GPU_ESTATE for a handle without an index.
+ * st (may be NULL): ms_total wall time of the call, ms_walk the kernel alone (HIP events), n_steps extensions (a rank pair each; with more than one walker
+ * per query it depends on which walker finds a seed first), n_queries, n_present, n_walkers, n_slices */
+typedef struct { double ms_total, ms_walk; int64_t n_queries, n_present, n_walkers, n_steps, n_slices; } rb3gpu_seed_stats_t;
+int rb3gpu_seed_present(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t chunk, uint8_t *present, rb3gpu_seed_stats_t *st);
+
 /* the indexed strings spelled out (`ropebwt3 get`, rb3_fmi_retrieve, fm-index.c:552-567 of the reference): from row rows[i] the LF walk until the row whose
  * symbol is the sentinel; the symbols met, reversed, are the string in front of the suffix of that row -- for a sentinel's row k < acc[1] the whole of
  * string k -- and the row the walk ends at is what rb3_fmi_retrieve returns.  A row outside [0, acc[6]) has no string and end row -1; such rows never
@@ -636,6 +649,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
  *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e and rb3gpu_sw_local; 0 = 16 K), "sw_table" N (as "hapdiv_table", for both);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
+ *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c
  * Test hooks "force_fallback", "tent_limit", "text_mode" exist only in the test build of the library (compiled with

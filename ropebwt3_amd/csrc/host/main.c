@@ -1970,8 +1970,57 @@ static int main_hapdiv(int argc, char *argv[])
  * (rb3_fmi_load_all, fm-index.c:606-640) unless --no-ssa, --all-e2e or -g says otherwise; with the first a hit gets positions, with the second they get names.
  * --local: the reference's default mode, the one best local hit of every query over the query's DAWG (host/dawg.c, rb3gpu_sw_local), written by the same write_paf
  * with the hit's place on the query.  It is opt-in: without --local and without -e the command is refused as before.
- * Differences, each a refusal with exit status 1 and nothing on stdout: no mode given (neither --local nor -e), --local with -e, --all-e2e or -g, -j above the end length (the reference's MEM pre-filter),
+ * --prefilter: with -j above the end length, the reference's MEM pre-filter (rb3_sw, bwa-sw.c:536-539): rb3gpu_seed_present runs first on every batch, only the
+ * queries with a seed of -j symbols go to the alignment, as a compacted batch, and the others are written as queries without a hit.  Opt-in as well.
+ * Differences, each a refusal with exit status 1 and nothing on stdout: no mode given (neither --local nor -e), --local with -e, --all-e2e or -g, -j above the end length without --prefilter,
  * -N or -k below 1, and the options of `mem` and `hapdiv`. */
+typedef struct {
+	int64_t n, *off, *map, m_q; /* the compacted batch: n queries, query i is the batch's query map[i] */
+	rb3h_buf_t sym;
+	uint8_t *present;
+} sw_seed_t;
+
+/* the queries of the batch that hold a seed of min_len symbols, as a batch of their own; 1: out of memory, < 0: the engine's error */
+static int sw_seed_filter(rb3gpu_t *h, int64_t n_q, const int64_t *off, const uint8_t *sym, int min_len, sw_seed_t *f, rb3gpu_seed_stats_t *st)
+{
+	int64_t q, total = 0;
+	int r;
+	if (n_q + 1 > f->m_q) {
+		f->m_q = n_q + (n_q >> 1) + 1024;
+		f->off = (int64_t*)realloc(f->off, (size_t)f->m_q * 8), f->map = (int64_t*)realloc(f->map, (size_t)f->m_q * 8), f->present = (uint8_t*)realloc(f->present, (size_t)f->m_q);
+		if (f->off == 0 || f->map == 0 || f->present == 0) return 1;
+	}
+	if ((r = rb3gpu_seed_present(h, n_q, off, sym, min_len, 0, f->present, st)) != 0) return r;
+	for (q = 0; q < n_q; ++q) if (f->present[q]) total += off[q + 1] - off[q];
+	if (f->sym.m < total + 1) {
+		f->sym.m = total + 1, f->sym.s = (uint8_t*)realloc(f->sym.s, (size_t)f->sym.m);
+		if (f->sym.s == 0) return 1;
+	}
+	for (q = 0, f->n = 0, f->off[0] = 0; q < n_q; ++q)
+		if (f->present[q]) {
+			memcpy(f->sym.s + f->off[f->n], sym + off[q], (size_t)(off[q + 1] - off[q]));
+			f->map[f->n] = q, f->off[f->n + 1] = f->off[f->n] + (off[q + 1] - off[q]), ++f->n;
+		}
+	f->sym.l = total;
+	return 0;
+}
+
+/* the hits of a compacted batch, as counted per query by sw_sink, spread back over the n_q queries of the whole batch (the hits themselves stay in order) */
+static void sw_seed_spread(const sw_seed_t *f, int64_t n_q, int32_t *n_hit, int32_t *hit_node)
+{
+	int64_t i, q;
+	for (i = f->n - 1, q = n_q - 1; q >= 0; --q) { /* map[i] >= i: from the back, nothing is overwritten before it is read */
+		if (i >= 0 && f->map[i] == q) {
+			n_hit[q] = n_hit[i];
+			if (hit_node) hit_node[q] = hit_node[i];
+			--i;
+		} else {
+			n_hit[q] = 0;
+			if (hit_node) hit_node[q] = 0;
+		}
+	}
+}
+
 typedef struct {
 	int32_t *n_hit; int64_t m_q;
 	rb3h_sw_hit_t *hits; int64_t n_hits, m_hits;
@@ -2016,6 +2065,7 @@ static const struct option sw_long_opts[] = {
 	{ "seq", no_argument, 0, 402 },
 	{ "all-e2e", no_argument, 0, 406 },
 	{ "local", no_argument, 0, 407 },
+	{ "prefilter", no_argument, 0, 408 },
 	{ "gpu", required_argument, 0, 301 },
 	{ "host-fmd", no_argument, 0, 308 },
 	{ 0, 0, 0, 0 }
@@ -2023,9 +2073,9 @@ static const struct option sw_long_opts[] = {
 
 static int main_sw(int argc, char *argv[])
 {
-	int c, is_line = 0, device = 0, ret = 0, j, e2e = 0, local = 0, no_ssa = 0, write_all = 0, both = 0, unmapped = 0, with_rs = 0, max_pos = 0, min_mem_len = 0;
-	int64_t batch_size = 100000000, id = 0, max_all_out = 0, n_ext = 0, n_hits = 0, n_tier2 = 0, n_slices = 0, n_batches = 0;
-	double ms_dp = 0, ms_bt = 0, ms_engine = 0, ms_locate = 0, ms_dawg = 0;
+	int c, is_line = 0, device = 0, ret = 0, j, e2e = 0, local = 0, no_ssa = 0, write_all = 0, both = 0, unmapped = 0, with_rs = 0, max_pos = 0, min_mem_len = 0, prefilter = 0, seeded;
+	int64_t batch_size = 100000000, id = 0, max_all_out = 0, n_ext = 0, n_hits = 0, n_tier2 = 0, n_slices = 0, n_batches = 0, n_filtered = 0, n_seed_walkers = 0, n_seed_steps = 0;
+	double ms_dp = 0, ms_bt = 0, ms_engine = 0, ms_locate = 0, ms_dawg = 0, ms_seed = 0;
 	int64_t n_nodes = 0, n_edges = 0, *node_off = 0, m_node_off = 0, m_hit = 0, max_len;
 	int32_t *hit_node = 0;
 	rb3gpu_sw_opt_t so = { 25, 30, 1, 3, 5, 2, -1, 11, 0 };
@@ -2037,16 +2087,19 @@ static int main_sw(int argc, char *argv[])
 	rb3h_buf_t rev = {0, 0, 0}, out = {0, 0, 0};
 	rb3h_qbatch_t b;
 	sw_out_t o[2];
+	sw_seed_t sf[2];
 	_Static_assert(sizeof(rb3h_sw_hit_t) == sizeof(rb3gpu_sw_hit_t), "one hit layout on both sides");
 	_Static_assert(sizeof(rb3h_pos_t) == sizeof(rb3gpu_pos_t), "one position layout on both sides");
 	memset(o, 0, sizeof(o));
 	memset(&b, 0, sizeof(b));
+	memset(sf, 0, sizeof(sf));
 	optind = 1;
 	while ((c = getopt_long(argc, argv, "Ll:c:t:K:MdN:A:B:O:E:C:m:k:uj:ey:a:w:p:bg:", sw_long_opts, 0)) >= 0) { /* the order of -e, -k, -g matters as in search.c:452-492 */
 		if (c == 'L') is_line = 1;
 		else if (c == 'g') max_all_out = atol(optarg), write_all = 1, e2e = 1, so.end_len = 1, no_ssa = 1;
 		else if (c == 406) write_all = 1, e2e = 1, so.end_len = 1, no_ssa = 1;
 		else if (c == 407) local = 1;
+		else if (c == 408) prefilter = 1;
 		else if (c == 'e') e2e = 1, so.end_len = 1;
 		else if (c == 'k') so.end_len = atoi(optarg);
 		else if (c == 'j') min_mem_len = atoi(optarg);
@@ -2082,6 +2135,8 @@ static int main_sw(int argc, char *argv[])
 		fprintf(stderr, "  -E INT      gap extension penalty; a k-long gap costs O+k*E [%d]\n", so.gap_ext);
 		fprintf(stderr, "  -y INT      ignore secondary hits scored INT lower than the best [%d]\n", so.e2e_drop);
 		fprintf(stderr, "  -k INT      require INT-mer match at the end of alignment [%d]\n", so.end_len);
+		fprintf(stderr, "  -j INT      min MEM length to initiate alignment (with --prefilter) [%d]\n", min_mem_len);
+		fprintf(stderr, "  --prefilter with -j above the end length: align only the queries that hold an exact match of -j symbols\n");
 		fprintf(stderr, "  -b          align both strands (effective with --all-e2e)\n");
 		fprintf(stderr, "  -u          write unmapped queries to PAF\n");
 		fprintf(stderr, "  --seq       write reference sequence to the rs tag\n");
@@ -2098,7 +2153,8 @@ static int main_sw(int argc, char *argv[])
 	if (so.n_best < 1) { fprintf(stderr, "ERROR: the number of hits kept per row (-N) must be at least 1\n"); return 1; }
 	if (so.end_len < 1) { fprintf(stderr, "ERROR: the end length (-k) must be at least 1\n"); return 1; }
 	if (so.n_best >= (1 << 24)) { fprintf(stderr, "ERROR: -N is too large\n"); return 1; }
-	if (min_mem_len > 0 && min_mem_len > so.end_len) { fprintf(stderr, "ERROR: -j above the end length asks for the MEM pre-filter, which is not implemented\n"); return 1; }
+	seeded = min_mem_len > 0 && min_mem_len > so.end_len; /* bwa-sw.c:536 */
+	if (seeded && !prefilter) { fprintf(stderr, "ERROR: -j above the end length asks for the MEM pre-filter: add --prefilter\n"); return 1; }
 	if ((h = open_index(device, argv[optind], 0)) == 0) return 1;
 	rb3gpu_get_acc(h, acc);
 	if (!no_ssa) { /* the two files beside the index, each only if it is there and belongs to this index */
@@ -2149,31 +2205,43 @@ static int main_sw(int argc, char *argv[])
 			if (n_q == -2) { fprintf(stderr, "ERROR: a query times -N is too large\n"); ret = 1; }
 			if (rb3h_seq_error(fp) && rb3h_verbose >= 1 && b.eof) fprintf(stderr, "ERROR: FASTX parsing error (code %d)\n", rb3h_seq_error(fp));
 			if (n_q <= 0 || ret != 0) continue;
+			if (seeded) { /* only the queries with a seed are aligned (bwa-sw.c:536-539): the batch without the others */
+				rb3gpu_seed_stats_t ss;
+				const int r = sw_seed_filter(h, n_q, off, sym.s, min_mem_len, &sf[0], &ss);
+				if (r > 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; continue; }
+				if (r < 0) { fprintf(stderr, "ERROR: the GPU engine failed to look for seeds: %s\n", rb3gpu_strerror(r)); ret = 1; continue; }
+				n_filtered += n_q - ss.n_present, n_seed_walkers += ss.n_walkers, n_seed_steps += ss.n_steps, ms_seed += ss.ms_walk, ms_engine += ss.ms_total;
+			}
 			if (local) { /* the graphs of the batch on the host, the nodes as rows on the device, one hit per query at most with its place on the query */
 				rb3h_dawg_t dg;
 				rb3gpu_swl_stats_t st;
 				rb3gpu_locate_stats_t ls;
 				const double t_dg = rb3h_realtime();
+				const int64_t a_n = seeded ? sf[0].n : n_q, *a_off = seeded ? sf[0].off : off; /* what is aligned: the graphs are built for these queries only */
+				const uint8_t *a_sym = seeded ? sf[0].sym.s : sym.s;
+				int64_t a; /* the query's number among the aligned ones */
 				int r;
 				if (n_q + 1 > m_node_off) {
 					m_node_off = n_q + 1;
 					node_off = (int64_t*)realloc(node_off, (size_t)m_node_off * 8), hit_node = (int32_t*)realloc(hit_node, (size_t)m_node_off * 4);
 				}
-				if (node_off == 0 || hit_node == 0 || (r = rb3h_dawg_batch(n_q, off, sym.s, &dg, node_off)) < 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; continue; }
+				if (node_off == 0 || hit_node == 0 || (r = rb3h_dawg_batch(a_n, a_off, a_sym, &dg, node_off)) < 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; continue; }
 				ms_dawg += (rb3h_realtime() - t_dg) * 1e3;
 				o[0].m_q = n_q, o[0].n_hits = o[0].n_steps = o[0].n_pos = 0, o[0].err = 0;
-				r = rb3gpu_sw_local(h, n_q, off, sym.s, node_off, dg.sym, dg.pre_off, dg.pre, &so, sw_sink, &o[0], hit_node, &st, &ls);
+				r = rb3gpu_sw_local(h, a_n, a_off, a_sym, node_off, dg.sym, dg.pre_off, dg.pre, &so, sw_sink, &o[0], hit_node, &st, &ls);
 				if (r != 0 && o[0].err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
 				else if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to align the queries: %s\n", rb3gpu_strerror(r)); ret = 1; }
 				n_ext += st.sw.n_ext, n_hits += st.sw.n_hits, n_tier2 += st.sw.n_tier2, n_slices += st.sw.n_slices, ms_dp += st.sw.ms_dp, ms_bt += st.sw.ms_backtrack, ms_engine += st.sw.ms_total;
 				ms_locate += ls.ms_locate, n_nodes += st.n_nodes, n_edges += st.n_edges;
-				for (q = 0; q < n_q && ret == 0; ++q) {
+				if (seeded && ret == 0) sw_seed_spread(&sf[0], n_q, o[0].n_hit, hit_node);
+				for (q = 0, a = 0; q < n_q && ret == 0; ++q) {
 					const char *nm = name_off[q] >= 0 ? (const char*)names.s + name_off[q] : 0;
-					const int64_t g = o[0].n_hit[q] > 0 ? node_off[q] + hit_node[q] : 0;
-					if (o[0].n_hit[q] > 1 || (o[0].n_hit[q] == 1 && (hit_node[q] < 0 || g >= node_off[q + 1]))) r = -3;
+					const int64_t g = o[0].n_hit[q] > 0 ? node_off[a] + hit_node[q] : 0;
+					if (o[0].n_hit[q] > 1 || (o[0].n_hit[q] == 1 && (hit_node[q] < 0 || g >= node_off[a + 1]))) r = -3;
 					else r = rb3h_sw_format_paf_at(&out, nm, id + q, off[q + 1] - off[q], sym.s + off[q], o[0].n_hit[q], o[0].hits + at[0], o[0].steps, o[0].pos, sid, unmapped, with_rs,
 							dg.qoff0 + g, dg.n_qoff + g);
 					at[0] += o[0].n_hit[q];
+					if (!seeded || sf[0].present[q]) ++a;
 					if (r == -2) { fprintf(stderr, "ERROR: a position names a sequence that the name list does not have\n"); ret = 1; break; }
 					if (r == -3) { fprintf(stderr, "ERROR: the GPU engine returned a hit that is not on the query\n"); ret = 1; break; }
 					if (r < 0) ret = 1;
@@ -2196,12 +2264,21 @@ static int main_sw(int argc, char *argv[])
 					memcpy(rev.s, sym.s, (size_t)sym.l);
 					for (q = 0; q < n_q; ++q) rb3h_revcomp6(off[q + 1] - off[q], rev.s + off[q]);
 					codes = rev.s;
+					if (seeded) { /* the reference's second rb3_sw call sees the reverse-complemented query (search.c:94-98) */
+						rb3gpu_seed_stats_t ss;
+						r = sw_seed_filter(h, n_q, off, codes, min_mem_len, &sf[1], &ss);
+						if (r > 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+						if (r < 0) { fprintf(stderr, "ERROR: the GPU engine failed to look for seeds: %s\n", rb3gpu_strerror(r)); ret = 1; break; }
+						n_filtered += n_q - ss.n_present, n_seed_walkers += ss.n_walkers, n_seed_steps += ss.n_steps, ms_seed += ss.ms_walk, ms_engine += ss.ms_total;
+					}
 				}
 				o[pass].m_q = n_q, o[pass].n_hits = o[pass].n_steps = o[pass].n_pos = 0, o[pass].err = 0;
-				r = rb3gpu_sw_e2e(h, n_q, off, codes, &so, sw_sink, &o[pass], &st, &ls);
+				if (seeded) r = rb3gpu_sw_e2e(h, sf[pass].n, sf[pass].off, sf[pass].sym.s, &so, sw_sink, &o[pass], &st, &ls);
+				else r = rb3gpu_sw_e2e(h, n_q, off, codes, &so, sw_sink, &o[pass], &st, &ls);
 				if (r != 0 && o[pass].err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
 				else if (r != 0) { fprintf(stderr, "ERROR: the GPU engine failed to align the queries: %s\n", rb3gpu_strerror(r)); ret = 1; }
 				n_ext += st.n_ext, n_hits += st.n_hits, n_tier2 += st.n_tier2, n_slices += st.n_slices, ms_dp += st.ms_dp, ms_bt += st.ms_backtrack, ms_engine += st.ms_total, ms_locate += ls.ms_locate;
+				if (seeded && ret == 0) sw_seed_spread(&sf[pass], n_q, o[pass].n_hit, 0);
 			}
 			for (q = 0; q < n_q && ret == 0; ++q) {
 				const char *nm = name_off[q] >= 0 ? (const char*)names.s + name_off[q] : 0;
@@ -2223,12 +2300,16 @@ static int main_sw(int argc, char *argv[])
 		rb3h_seq_close(fp);
 	}
 	if (fflush(stdout) != 0 && ret == 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
-	if (rb3h_verbose >= 3 && ret == 0)
-		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld hits in %lld slice(s), %lld extensions, %lld queries with a table in global memory; %.3f ms in the engine, the DP kernel %.3f ms, the backtrack %.3f ms, the locate kernels %.3f ms\n",
-				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_hits, (long long)n_slices, (long long)n_ext, (long long)n_tier2, ms_engine, ms_dp, ms_bt, ms_locate);
+	if (rb3h_verbose >= 3 && ret == 0) {
+		char pre[256] = "";
+		if (seeded) snprintf(pre, sizeof(pre), "; the pre-filter: %lld queries without a seed of %d symbols were not aligned; %lld walkers, %lld extension steps, the seed kernel %.3f ms",
+				(long long)n_filtered, min_mem_len, (long long)n_seed_walkers, (long long)n_seed_steps, ms_seed);
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld queries in %lld batch(es): %lld hits in %lld slice(s), %lld extensions, %lld queries with a table in global memory; %.3f ms in the engine, the DP kernel %.3f ms, the backtrack %.3f ms, the locate kernels %.3f ms%s\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)id, (long long)n_batches, (long long)n_hits, (long long)n_slices, (long long)n_ext, (long long)n_tier2, ms_engine, ms_dp, ms_bt, ms_locate, pre);
+	}
 	if (rb3h_verbose >= 3 && ret == 0 && local)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] the graphs: %lld nodes, %lld edges, %.3f ms on the host\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)n_nodes, (long long)n_edges, ms_dawg);
-	for (j = 0; j < 2; ++j) { free(o[j].n_hit); free(o[j].hits); free(o[j].steps); free(o[j].pos); }
+	for (j = 0; j < 2; ++j) { free(o[j].n_hit); free(o[j].hits); free(o[j].steps); free(o[j].pos); free(sf[j].off); free(sf[j].map); free(sf[j].present); free(sf[j].sym.s); }
 	free(out.s); free(rev.s); free(node_off); free(hit_node);
 	rb3h_qbatch_free(&b);
 	rb3gpu_destroy(h);

@@ -158,6 +158,8 @@ struct Tune {
 	int64_t sw_slice = 0;    // rb3gpu_sw_e2e: queries per launch and per piece handed to the callback (0: 16 K; fewer where the backtrack matrices of a slice would not fit)
 	int64_t sw_table = 0;    // rb3gpu_sw_e2e: slots of a query's candidate table in LDS (0: 256, at most 256), as hapdiv_table
 	int64_t suffix_slice = 0;// rb3gpu_suffix: queries per launch (0: 4 M)
+	int64_t seed_chunk = 0;  // rb3gpu_seed_present: window starts per walker where the caller names none (0: 2048)
+	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
 	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
 	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
@@ -678,6 +680,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "sw_table")) t.sw_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
 	else if (!strcmp(key, "suffix_slice")) t.suffix_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "seed_chunk")) t.seed_chunk = v < 0 ? 0 : v;
+	else if (!strcmp(key, "seed_slice")) t.seed_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
 	else if (!strcmp(key, "locate_slice")) t.locate_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sh_host_rounds")) t.sh_host_rounds = v < 0 ? -1 : v != 0; // (-1: rounds on the device whatever the number of chains)
@@ -717,7 +721,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -5406,10 +5410,12 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 	return ret;
 }
 
-/* ---- suffix and get: the two plain walks (rb3gpu_walk.h) ----------------------------------------- */
+/* ---- suffix, get and the seed test: the plain walks (rb3gpu_walk.h) ----------------------------------------- */
 
 #define RB3_SUFFIX_SLICE ((int64_t)1 << 22)   // queries per launch
 #define RB3_GET_SLICE ((int64_t)1 << 26)      // symbols of an emit slice (a byte of device and of page-locked host memory each)
+#define RB3_SEED_CHUNK ((int64_t)2048)        // window starts per walker
+#define RB3_SEED_SLICE ((int64_t)1 << 20)     // walkers per launch
 
 struct WalkWs {
 	std::vector<void*> dv;
@@ -5479,6 +5485,87 @@ int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_steps = (int64_t)ws.h_ctr[1], st->n_slices = n_slices;
+	return 0;
+}
+
+int rb3gpu_seed_present(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, int64_t min_len, int64_t chunk, uint8_t *present, rb3gpu_seed_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || n_query < 0 || min_len < 2 || (n_query > 0 && (!offsets || !present))) return RB3GPU_EINVAL; // (at 1 the reference's loop finds a seed in any query, whatever the index holds)
+	int64_t total;
+	if (!queries_ok(n_query, offsets, symbols, 0x7fffffffLL, &total)) return RB3GPU_EINVAL; // (the kernel keeps a position in 32 bits)
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	if (st) st->n_queries = n_query;
+	if (n_query > 0) memset(present, 0, (size_t)n_query);
+	if (chunk <= 0) chunk = h->tn.seed_chunk > 0 ? h->tn.seed_chunk : RB3_SEED_CHUNK;
+	if (chunk > 0x7fffffffLL) chunk = 0x7fffffffLL;
+	// the walkers: chunk after chunk of the window starts [0, len - min_len + 1) of every query that has one
+	int64_t n_walkers = 0;
+	for (int64_t q = 0; q < n_query; ++q) {
+		const int64_t ns = offsets[q + 1] - offsets[q] - min_len + 1;
+		if (ns > 0) n_walkers += (ns + chunk - 1) / chunk;
+	}
+	if (st) st->n_walkers = n_walkers;
+	if (n_walkers == 0) { // no query as long as a seed
+		if (st) st->ms_total = (now_s() - t0) * 1e3;
+		return 0;
+	}
+	const int64_t slice = std::min(n_walkers, h->tn.seed_slice > 0 ? h->tn.seed_slice : RB3_SEED_SLICE);
+	WalkWs ws;
+	uint8_t *d_sym = nullptr, *d_present = nullptr;
+	int64_t *d_qoff = nullptr;
+	SeedWalker *d_wk = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+	HIPCHK(dalloc(&d_sym, (size_t)total + 64));
+	HIPCHK(dalloc(&d_qoff, (size_t)(n_query + 1) * 8));
+	HIPCHK(dalloc(&d_present, (size_t)n_query + 64));
+	HIPCHK(dalloc(&d_wk, (size_t)slice * sizeof(SeedWalker)));
+	HIPCHK(dalloc(&d_ctr, 64));
+	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 64, hipHostMallocDefault));
+	HIPCHK(hipHostMalloc(&ws.h_out, (size_t)slice * sizeof(SeedWalker), hipHostMallocDefault));
+	HIPCHK(hipEventCreate(&ws.e0));
+	HIPCHK(hipEventCreate(&ws.e1));
+	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(d_present, 0, (size_t)n_query + 64, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+	const IdxView ix = view_of(h);
+	const Acc7 acc = acc7_of(h);
+	SeedWalker *wk = (SeedWalker*)ws.h_out;
+	double ms_walk = 0;
+	int64_t n_slices = 0, q = 0, a = 0; // the next walker starts at window a of query q
+	for (int64_t w0 = 0; w0 < n_walkers; ++n_slices) {
+		int64_t nw = 0;
+		while (nw < slice && q < n_query) {
+			const int64_t ns = offsets[q + 1] - offsets[q] - min_len + 1;
+			if (a >= ns) { ++q, a = 0; continue; }
+			SeedWalker &s = wk[nw++];
+			s.q = q, s.a = (int32_t)a, s.b = (int32_t)std::min(ns, a + chunk);
+			a += chunk;
+		}
+		if (nw <= 0 || w0 + nw > n_walkers) return RB3GPU_EINTERNAL;
+		HIPCHK(hipMemcpyAsync(d_wk, wk, (size_t)nw * sizeof(SeedWalker), hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
+		const int64_t nb = std::min<int64_t>((nw * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(ws.e0, h->st));
+		hipLaunchKernelGGL(k_seed_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_qoff, (const SeedWalker*)d_wk, nw, (int32_t)min_len, d_present, d_ctr);
+		HIPCHK(hipEventRecord(ws.e1, h->st));
+		HIPCHK(hipStreamSynchronize(h->st)); // (the walkers of the next slice are written where these were read from)
+		HIPCHK(hipGetLastError());
+		ms_walk += ev_ms(ws.e0, ws.e1);
+		w0 += nw;
+	}
+	HIPCHK(hipMemcpyAsync(present, d_present, (size_t)n_query, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	if (st) {
+		int64_t np = 0;
+		for (int64_t i = 0; i < n_query; ++i) np += present[i] != 0;
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_present = np, st->n_steps = (int64_t)ws.h_ctr[1], st->n_slices = n_slices;
+	}
 	return 0;
 }
 

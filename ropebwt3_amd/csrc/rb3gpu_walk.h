@@ -1,9 +1,10 @@
 /*
- * rb3gpu_walk.h -- the two plain walks over the index: `suffix`, the longest suffix of a query that occurs in the index
+ * rb3gpu_walk.h -- the plain walks over the index: `suffix`, the longest suffix of a query that occurs in the index
  * (main_suffix, main.c:167-217 of the reference, on the one-sided backward extension rb3_fmi_extend1, fm-index.h:140-147),
- * and `get`, the i-th indexed string spelled out (rb3_fmi_retrieve, fm-index.c:552-567).
+ * `get`, the i-th indexed string spelled out (rb3_fmi_retrieve, fm-index.c:552-567), and the seed test of `sw -j`: does
+ * any stretch of min_len symbols of the query occur in the index (rb3_fmd_smem_present, fm-index.c:483-498 and 530-538).
  *
- * Both are dependent chains of ranks: a step cannot start before the step in front of it has ended, so one chain runs at the
+ * All are dependent chains of ranks: a step cannot start before the step in front of it has ended, so one chain runs at the
  * latency of a rank and the throughput comes from the chains in flight.  An octet of lanes per chain, as everywhere in the
  * engine; an octet that has finished its chain takes the next one from a counter, so the lanes of a wave stay busy whatever
  * the chains' lengths (k_mem_walk, k_ssa_walk).
@@ -15,6 +16,10 @@
  *                  notes the length of the walk and the row it met the sentinel at, EMIT walks again and stores symbol t of
  *                  the walk at off + len - 1 - t, so the string lands in text order.  Between them lies an exclusive scan
  *                  of the lengths of a slice of rows (the driver).
+ *   k_seed_walk    the step of k_suffix_walk, in windows of min_len symbols: a window is walked from its last symbol to its
+ *                  first; where the interval empties at symbol i, the next window starts at i + 1 (no window that holds
+ *                  q[i .. x + min_len - 1] can occur), and a window that reaches its first symbol is a seed.  A query is cut
+ *                  into walkers of `chunk` window starts each; the answer is the OR of the walkers' answers.
  */
 #ifndef RB3GPU_WALK_H
 #define RB3GPU_WALK_H
@@ -109,6 +114,56 @@ template<bool EMIT> __global__ void __launch_bounds__(256) k_get_walk(IdxView ix
 					if (j == 0 && p >= 0 && p < cap) out[p] = (uint8_t)c;
 				}
 				++t, k = k2;
+			}
+		}
+	}
+	if (j == 0 && steps) atomicAdd(ctr + 1, steps);
+}
+
+/* one walker of k_seed_walk: the window starts [a, b) of query q (the driver keeps b <= len - min_len + 1) */
+struct SeedWalker { int64_t q; int32_t a, b; };
+
+/* the walkers wk[0, nw) over windows of min_len >= 2 symbols (queries of fewer than 2^31 symbols: the driver refuses longer ones).  A walker that finds
+ * a window whose min_len symbols occur sets present[q] = 1 (zeroed by the driver; every writer stores the same byte) and ends; it also ends without
+ * looking further when another walker of its query has already done so.  ctr[0]: the next walker to hand out (0 at launch), ctr[1] += extension steps */
+__global__ void __launch_bounds__(256) k_seed_walk(IdxView ix, Acc7 acc, const uint8_t *sym, const int64_t *qoff, const SeedWalker *wk, int64_t nw, int32_t min_len, uint8_t *present,
+		unsigned long long *ctr)
+{
+	const int j = threadIdx.x & 7;
+	bool act = false, done = false;
+	int64_t q = 0, qb = 0, k = 0, l = 0;
+	int32_t len = 0, x = 0, b = 0, i = -1;
+	unsigned long long steps = 0;
+	// the window that starts at x: false if there is none left for this walker; else the interval of its last symbol (no rank needed), the cursor in front of it
+	auto window = [&]() -> bool {
+		if (len - x < min_len || x >= b) return false; // (fm-index.c:489; the end of the walker's start range)
+		if (*(const volatile uint8_t*)(present + q)) return false;
+		const int c = min((int)sym[qb + x + min_len - 1], 5);
+		k = acc.a[c], l = acc.a[c + 1], i = x + min_len - 2;
+		return true;
+	};
+	for (;;) {
+		while (!act && !done) { // (the same in the eight lanes of an octet)
+			const int64_t w = walk_take(ctr, j);
+			if (w >= nw) { done = true; break; }
+			const SeedWalker s = wk[w];
+			q = s.q, qb = qoff[q], len = (int32_t)(qoff[q + 1] - qb), x = s.a, b = s.b;
+			act = window();
+		}
+		if (__ballot(act) == 0ull) break;
+		// one extension by q[i] (fm-index.c:491-496): the ranks of that symbol at both ends
+		const int c = act ? min((int)sym[qb + i], 5) : 0;
+		RankLoad rl, ru;
+		oct_rank_issue(ix, act ? k : 0, j, rl); // (a finished octet: a valid address, the result unused)
+		oct_rank_issue(ix, act ? l : 0, j, ru);
+		const int64_t nk = oct_rank_finish(rl, c, j, ix.abs), nl = oct_rank_finish(ru, c, j, ix.abs);
+		if (act) {
+			++steps;
+			k = nk, l = nl;
+			if (l - k <= 0) x = i + 1, act = window(); // q[i .. x + min_len - 1] does not occur: the next window starts behind i (fm-index.c:497)
+			else if (--i < x) { // the whole window occurs: a seed
+				if (j == 0) present[q] = 1;
+				act = false;
 			}
 		}
 	}

@@ -129,6 +129,14 @@ class SuffixStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SeedStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_queries", ctypes.c_int64), ("n_present", ctypes.c_int64), ("n_walkers", ctypes.c_int64),
+                ("n_steps", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RetrieveStats(ctypes.Structure):
     _fields_ = [("ms_total", ctypes.c_double), ("ms_count", ctypes.c_double), ("ms_emit", ctypes.c_double), ("n_rows", ctypes.c_int64), ("n_symbols", ctypes.c_int64),
                 ("n_steps", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
@@ -256,6 +264,7 @@ SYMBOLS = {
                                        ctypes.POINTER(SwOpt), SW_F, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SwlStats), ctypes.POINTER(LocateStats)]),
     "rb3gpu_mem": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, MEM_F, ctypes.c_void_p, ctypes.POINTER(MemStats)]),
     "rb3gpu_suffix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SuffixStats)]),
+    "rb3gpu_seed_present": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(SeedStats)]),
     "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
 }
 
@@ -875,6 +884,23 @@ class Rb3Gpu:
         out = np.zeros(len(qs), dtype=SUFFIX_OUT)
         out["query"], out["start"], out["length"], out["size"] = np.arange(len(qs)), rec["start"], off[1:] - off[:-1], rec["size"]
         return out
+
+    def seed_present(self, queries, min_len, chunk=None, stats=None):
+        """rb3gpu_seed_present: per query (forms as for suffix) whether a stretch of at least min_len symbols of it occurs in the index, the test behind the
+        reference's `sw -j` (rb3_fmd_smem_present): a bool array, one entry per query in input order; False for a query shorter than min_len.  chunk: window
+        starts per walker (None: the engine's default; the answer does not depend on it); stats: a dict that receives rb3gpu_seed_stats_t"""
+        qs = [nt6_of(q) for q in queries]
+        off = np.zeros(len(qs) + 1, dtype=np.int64)
+        if qs:
+            off[1:] = np.cumsum([q.size for q in qs])
+        sym = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+        flag = np.zeros(len(qs), dtype=np.uint8)
+        st = SeedStats()
+        self._chk(self._lib.rb3gpu_seed_present(self._h, len(qs), off.ctypes.data, sym.ctypes.data if sym.size else None, int(min_len), 0 if chunk is None else int(chunk),
+                                                flag.ctypes.data if flag.size else None, ctypes.byref(st)), "rb3gpu_seed_present")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return flag != 0
 
     def retrieve(self, rows, stats=None):
         """rb3gpu_retrieve: for every row asked for, in the order asked, the string in front of the suffix of that row (for a sentinel's row k < acc[1]
