@@ -328,6 +328,27 @@ int rb3gpu_from_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, c
  * (`ropebwt3 merge`, main.c:84-133, with the right-hand index taken as its BWT) */
 int rb3gpu_merge_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, const int64_t mcnt[RB3GPU_ASIZE]);
 
+/* BRE, the run-length interchange format of the reference (bre.c / bre.h; `build -e`: mr_print_bre, build.c:85-106; read wherever an index is read:
+ * rld_restore, rld0.c:245-283).  A RECORD is one symbol byte followed by b_per_run length bytes, little-endian; a run longer than 2^(8 b_per_run) - 1 is
+ * split into records of that length and a remainder, and a reader joins consecutive records of one symbol.  These calls handle the records; the file's
+ * header and footer are the host's (rb3h_bre_*).
+ *   rb3gpu_export_bre  the records of the index in order, packed on the device a piece of the runs at a time (rb3gpu_tune "bre_piece": runs per piece,
+ *                      default 64 M; a piece ends with a whole group of 8192 symbols) and handed to emit in consecutive slabs of bytes (host memory valid
+ *                      during the call only; a nonzero return stops the export: RB3GPU_EINVAL).  b_per_run 1..4.  st (may be NULL): n_rec records written,
+ *                      n_sym symbols, n_run maximal runs -- the footer's three counts --, n_pieces, ms_scan (record counts + scan) and ms_pack (the kernel
+ *                      that writes the records).
+ *   rb3gpu_from_bre    the index of n_rec records (host memory, n_rec * (1 + b_per_run) bytes), decoded on the device; b_per_run 1..8.  st: the counts the
+ *                      DEVICE found -- the caller holds them against the file's footer --, ms_scan, ms_fill (symbols written, where the index is built in
+ *                      one piece), n_pieces (chunks of the two-pass builder above rb3gpu_tune "load_chunk" groups, as for an FMD stream).
+ *   rb3gpu_merge_bre   the same records merged into the handle's index as one batch, like rb3gpu_merge_fmd_words.
+ * RB3GPU_ESYMBOL: a record with a symbol above 5, of no symbols or of 2^56 and more; RB3GPU_EINVAL: NULL, n_rec <= 0, b_per_run out of range.
+ * A caller that may still refuse the file for its footer can keep the handle quiet meanwhile: rb3gpu_tune "verbose" sets the level of rb3gpu_opt_t. */
+typedef struct { int64_t n_rec, n_sym, n_run, n_pieces; double ms_scan, ms_pack, ms_fill; } rb3gpu_bre_stats_t;
+typedef int (*rb3gpu_emit_bytes_f)(void *data, int64_t n, const uint8_t *bytes);
+int rb3gpu_export_bre(rb3gpu_t *h, int b_per_run, rb3gpu_emit_bytes_f emit, void *data, rb3gpu_bre_stats_t *st); /* records only, in order */
+int rb3gpu_from_bre(rb3gpu_t *h, int b_per_run, int64_t n_rec, const uint8_t *records, rb3gpu_bre_stats_t *st);
+int rb3gpu_merge_bre(rb3gpu_t *h, int b_per_run, int64_t n_rec, const uint8_t *records, rb3gpu_bre_stats_t *st);
+
 /* rb3_fmi_merge(fa, fb), fm-index.c:251-277 (`ropebwt3 merge`, main.c:84-133) between two handles: every string of the index in
  * `src` is merged into `h` as one batch (its sentinels rank after those of `h`, fm-index.c:147).  The two may sit on different
  * GPUs: the plain BWT of `src` goes device to device (xGMI).  This is the tree step of a partitioned multi-GPU build

@@ -277,16 +277,45 @@ int rb3h_fmr_read_runs(FILE *fp, rb3h_run_f emit, void *data)
 	return d.err;
 }
 
-int rb3h_index_read_runs(const char *fn, rb3h_run_f emit, void *data)
+/* the first four bytes of an index file, which say what it is: "-" is stdin.  A caller that treats the kinds differently opens the file ONCE
+ * with this and hands the stream on (a pipe cannot be opened twice, nor can stdin be rewound); NULL: no such file, or shorter than that */
+FILE *rb3h_index_open(const char *fn, char magic[4])
 {
 	FILE *fp = strcmp(fn, "-") == 0 ? stdin : fopen(fn, "rb");
+	if (fp == 0) return 0;
+	if (fread(magic, 1, 4, fp) != 4) {
+		if (fp != stdin) fclose(fp);
+		return 0;
+	}
+	return fp;
+}
+
+int rb3h_index_kind(const char magic[4])
+{
+	if (memcmp(magic, "RLD\3", 4) == 0) return RB3H_INDEX_FMD;
+	if (memcmp(magic, "RB\2", 3) == 0) return RB3H_INDEX_FMR;
+	if (memcmp(magic, "BRE\1", 4) == 0) return RB3H_INDEX_BRE;
+	return RB3H_INDEX_NONE;
+}
+
+/* the runs of a stream whose magic rb3h_index_open has consumed */
+int rb3h_index_read_runs_fp(FILE *fp, const char magic[4], rb3h_run_f emit, void *data)
+{
+	switch (rb3h_index_kind(magic)) {
+	case RB3H_INDEX_FMD: return rb3h_fmd_read_runs(fp, emit, data, 0);
+	case RB3H_INDEX_FMR: return rb3h_fmr_read_runs(fp, emit, data);
+	case RB3H_INDEX_BRE: return rb3h_bre_read_runs(fp, emit, data);
+	default: return -2;
+	}
+}
+
+int rb3h_index_read_runs(const char *fn, rb3h_run_f emit, void *data)
+{
 	char magic[4];
+	FILE *fp = rb3h_index_open(fn, magic);
 	int ret;
 	if (fp == 0) return -1;
-	if (fread(magic, 1, 4, fp) != 4) ret = -1;
-	else if (memcmp(magic, "RLD\3", 4) == 0) ret = rb3h_fmd_read_runs(fp, emit, data, 0);
-	else if (memcmp(magic, "RB\2", 3) == 0) ret = rb3h_fmr_read_runs(fp, emit, data);
-	else ret = -2;
+	ret = rb3h_index_read_runs_fp(fp, magic, emit, data);
 	if (fp != stdin) fclose(fp);
 	return ret;
 }

@@ -25,7 +25,7 @@
 #define BF_NO_REV 0x2
 #define BF_LINE   0x4
 
-enum { FMT_PLAIN = 0, FMT_FMD, FMT_FMR };
+enum { FMT_PLAIN = 0, FMT_FMD, FMT_FMR, FMT_BRE };
 
 typedef struct {
 	int64_t flag, batch_size;
@@ -92,6 +92,8 @@ static int usage_build(FILE *fp, const bopt_t *opt)
 	fprintf(fp, "  Output:\n");
 	fprintf(fp, "    -o FILE     output to FILE [stdout]\n");
 	fprintf(fp, "    -d          dump in the fermi-delta format (FMD)\n");
+	fprintf(fp, "    -e          dump in the BRE format (records packed on the GPU)\n");
+	fprintf(fp, "    --bre-run-bytes INT  bytes of a BRE record's run length, 1..4 [2]\n");
 	fprintf(fp, "    -b          dump in the ropebwt format (FMR)\n");
 	fprintf(fp, "    -S FILE     save the current index to FILE after each input file []\n");
 	fprintf(fp, "  String order:\n");
@@ -234,6 +236,35 @@ static int write_fmd(rb3gpu_t *h, FILE *fp)
 }
 static int sink_fmr(void *data, int c, int64_t l) { return rb3h_fmrw_enc((rb3h_fmrw_t*)data, l, c); }
 
+/* the .bre of the index (mr_print_bre, build.c:85-106): header, the records packed on the GPU, footer with the counts the device found; with
+ * --host-fmd the GPU finds the runs and the host's packer writes the records */
+static int g_bre_run_bytes = 2; /* --bre-run-bytes */
+
+static int sink_bre_bytes(void *data, int64_t n, const uint8_t *bytes) { return fwrite(bytes, 1, (size_t)n, (FILE*)data) == (size_t)n ? 0 : -1; }
+static int sink_bre_words(void *data, int64_t n, const uint64_t *words, int64_t end) { return rb3h_brew_enc_words((rb3h_brew_t*)data, n, words, end); }
+
+static int write_bre_host(rb3gpu_t *h, rb3gpu_shard_t *sh, FILE *fp)
+{
+	rb3h_brew_t *w = rb3h_brew_init(fp, g_bre_run_bytes);
+	int ret;
+	if (w == 0) return -1;
+	ret = sh ? rb3gpu_shard_export_run_words(sh, sink_bre_words, w) : rb3gpu_export_run_words(h, sink_bre_words, w);
+	if (ret == 0) ret = rb3h_brew_finish(w);
+	rb3h_brew_destroy(w);
+	return ret;
+}
+
+static int write_bre(rb3gpu_t *h, FILE *fp)
+{
+	rb3gpu_bre_stats_t st;
+	int ret;
+	if (g_host_fmd) return write_bre_host(h, 0, fp);
+	if (rb3h_bre_write_header(fp, g_bre_run_bytes) < 0) return -1;
+	if ((ret = rb3gpu_export_bre(h, g_bre_run_bytes, sink_bre_bytes, fp, &st)) < 0) return ret;
+	if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] packed %ld BRE records on the GPU\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), (long)st.n_rec);
+	return rb3h_bre_write_footer(fp, g_bre_run_bytes, st.n_rec, st.n_sym, st.n_run);
+}
+
 static int sink_plain(void *data, int c, int64_t l) /* mr_print_bwt, mrope.c:201-214 */
 {
 	FILE *fp = (FILE*)data;
@@ -284,11 +315,12 @@ static int index_order(const char *fn)
 /* an existing index into HBM (build.c:172-184, rb3_fmi_restore): an FMD file is decoded on the device
  * (rb3gpu_from_fmd_words); an FMR file, a stream, or an FMD the device declined goes through the host decoder */
 /* an index file in host memory, before a device has seen it: the undecoded words of an FMD file (z != NULL) or the runs of any index file */
-typedef struct { uint64_t *z; int64_t nw, mc[6]; runvec_t rv; } index_host_t;
+typedef struct { uint64_t *z; int64_t nw, mc[6]; runvec_t rv; rb3h_bre_t bre; } index_host_t; /* bre.rec != NULL: the raw records of a BRE file */
 
 static void index_host_free(index_host_t *x)
 {
 	free(x->z); free(x->rv.a);
+	rb3h_bre_free(&x->bre);
 	x->z = 0, x->rv.a = 0, x->rv.n = x->rv.m = 0;
 }
 
@@ -298,19 +330,35 @@ static int index_host_runs(const char *fn, index_host_t *x)
 	return 0;
 }
 
+/* ONE open of the file -- it may be a pipe, or stdin --, then by its magic: the records of a BRE file and the words of an FMD file stay as they are
+ * for the device; an FMR file, anything with --host-fmd and an FMD on stdin (which the fallback of index_upload could not read again) become runs */
 static int index_host_read(const char *fn, index_host_t *x)
 {
-	const int r = g_host_fmd ? 1 : rb3h_fmd_read_words(fn, &x->z, &x->nw, x->mc);
-	if (r < 0) return -1;
-	if (r != 0) x->z = 0;
-	return r == 0 ? 0 : index_host_runs(fn, x);
+	char magic[4];
+	FILE *fp = rb3h_index_open(fn, magic);
+	const int kind = fp ? rb3h_index_kind(magic) : RB3H_INDEX_NONE;
+	int r;
+	if (fp == 0) return -1;
+	if (!g_host_fmd && kind == RB3H_INDEX_BRE) r = rb3h_bre_read_fp(fp, &x->bre) == 0 ? 0 : -1;
+	else if (!g_host_fmd && kind == RB3H_INDEX_FMD && fp != stdin) {
+		r = rb3h_fmd_read_words_fp(fp, &x->z, &x->nw, x->mc) == 0 ? 0 : -1;
+		if (r != 0) x->z = 0;
+	} else r = rb3h_index_read_runs_fp(fp, magic, sink_runvec, &x->rv) < 0 || x->rv.n == 0 ? -1 : 0;
+	if (fp != stdin) fclose(fp);
+	if (r != 0) index_host_free(x);
+	return r;
 }
 
 /* the number of sentinels (acc[1]) and of symbols (acc[6]) of the index that was read */
 static int64_t index_host_sentinels(const index_host_t *x, int64_t *n_sym)
 {
 	int64_t i, m = 0, n = 0;
-	if (x->z) {
+	if (x->bre.rec) { /* (the footer's total; the sentinels are counted in the records) */
+		const int rs = 1 + x->bre.b_per_run;
+		for (i = 0; i < x->bre.n_rec; ++i)
+			if (x->bre.rec[i * rs] == 0) { int j; uint64_t l = 0; for (j = 0; j < x->bre.b_per_run; ++j) l |= (uint64_t)x->bre.rec[i * rs + 1 + j] << (8 * j); m += (int64_t)l; }
+		n = x->bre.ftr[1];
+	} else if (x->z) {
 		for (i = 0; i < 6; ++i) n += x->mc[i];
 		m = x->mc[0];
 	} else for (i = 0; i < x->rv.n; ++i) {
@@ -324,6 +372,24 @@ static int64_t index_host_sentinels(const index_host_t *x, int64_t *n_sym)
 static int index_upload(rb3gpu_t *h, const char *fn, index_host_t *x)
 {
 	int r;
+	if (x->bre.rec) {
+		rb3gpu_bre_stats_t st;
+		rb3gpu_tune(h, "verbose", 0); /* (the file may still be refused: the engine says nothing about it until its counts are accepted) */
+		r = rb3gpu_from_bre(h, x->bre.b_per_run, x->bre.n_rec, x->bre.rec, &st);
+		rb3gpu_tune(h, "verbose", rb3h_verbose);
+		if (r == 0 && (st.n_rec != x->bre.ftr[0] || st.n_sym != x->bre.ftr[1] || st.n_run != x->bre.ftr[2])) r = RB3GPU_ESYMBOL; /* the footer disagrees with what the device counted */
+		if (r == RB3GPU_ESYMBOL) { index_host_free(x); return -1; } /* not a valid file: the host decoder would say the same */
+		if (r == 0) {
+			if (rb3h_verbose >= 3)
+				fprintf(stderr, "[M::%s::%.3f*%.2f] %ld BRE records of %d bytes unpacked on the GPU: %ld symbols in %ld runs (scan %.3f ms, fill %.3f ms, %ld piece%s)\n", __func__, rb3h_realtime(), rb3h_percent_cpu(),
+						(long)st.n_rec, 1 + x->bre.b_per_run, (long)st.n_sym, (long)st.n_run, st.ms_scan, st.ms_fill, (long)st.n_pieces, st.n_pieces == 1 ? "" : "s");
+			index_host_free(x);
+			return 0;
+		}
+		if (rb3h_verbose >= 2) fprintf(stderr, "[W::%s] the GPU did not decode '%s' (%s); decoding it on the host\n", __func__, fn, rb3gpu_strerror(r));
+		if (rb3h_bre_decode_runs(&x->bre, sink_runvec, &x->rv) < 0 || x->rv.n == 0) { index_host_free(x); return -1; }
+		rb3h_bre_free(&x->bre);
+	}
 	if (x->z) {
 		r = rb3gpu_from_fmd_words(h, x->nw, x->z, x->mc);
 		free(x->z), x->z = 0;
@@ -893,6 +959,7 @@ static const struct option long_opts[] = {
 	{ "host-fmd", no_argument, 0, 308 },
 	{ "gpus", required_argument, 0, 309 },
 	{ "interval", no_argument, 0, 310 },
+	{ "bre-run-bytes", required_argument, 0, 311 },
 	{ 0, 0, 0, 0 }
 };
 
@@ -920,10 +987,12 @@ int main_build(int argc, char *argv[])
 		else if (c == '2') {
 			fprintf(stderr, "ERROR: -%c selects the ropebwt2 insertion algorithm, which this build does not include; the default (suffix sorting + merge) gives the same BWT for -2\n", c);
 			return 1;
-		} else if (c == 'T' || c == 'e') {
+		} else if (c == 'T') {
 			fprintf(stderr, "ERROR: output format -%c is not available in this build; use -d (FMD), -b (FMR) or the default plain text\n", c);
 			return 1;
-		} else if (c == 'i') fn_in = optarg;
+		} else if (c == 'e') opt.fmt = FMT_BRE;
+		else if (c == 311) g_bre_run_bytes = atoi(optarg);
+		else if (c == 'i') fn_in = optarg;
 		else if (c == 'L') opt.flag |= BF_LINE;
 		else if (c == 'F') opt.flag |= BF_NO_FOR;
 		else if (c == 'R') opt.flag |= BF_NO_REV;
@@ -946,6 +1015,10 @@ int main_build(int argc, char *argv[])
 	if (opt.gpu_sort_limit > (int64_t)INT32_MAX - 16) opt.gpu_sort_limit = (int64_t)INT32_MAX - 16;
 	if (opt.gpu_batch <= 0 || opt.gpu_batch > opt.gpu_sort_limit - 1) opt.gpu_batch = opt.gpu_sort_limit - 1;
 	if (argc == optind && fn_in == 0) return usage_build(stderr, &opt);
+	if (g_bre_run_bytes < 1 || g_bre_run_bytes > 4) {
+		fprintf(stderr, "ERROR: --bre-run-bytes takes 1 to 4\n");
+		return 1;
+	}
 	if ((opt.flag & BF_NO_FOR) && (opt.flag & BF_NO_REV)) {
 		fprintf(stderr, "ERROR: -F and -R together leave nothing to index\n");
 		return 1;
@@ -1128,6 +1201,8 @@ int main_build(int argc, char *argv[])
 			if (ret == 0) ret = rb3h_fmdw_finish(w);
 			if (ret == 0) ret = rb3h_fmdw_dump(w, stdout);
 			if (w) rb3h_fmdw_destroy(w);
+		} else if (opt.fmt == FMT_BRE) { /* the intervals' runs in rank order into the host's packer */
+			ret = write_bre_host(h, g_iv.s, stdout);
 		} else {
 			ret = rb3gpu_shard_export_runs(g_iv.s, sink_plain, stdout);
 			fputc('\n', stdout);
@@ -1148,6 +1223,8 @@ int main_build(int argc, char *argv[])
 		ret = dump_fmr(h, &opt, stdout);
 	} else if (opt.fmt == FMT_FMD) {
 		ret = write_fmd(h, stdout);
+	} else if (opt.fmt == FMT_BRE) {
+		ret = write_bre(h, stdout);
 	} else {
 		ret = rb3gpu_export_runs(h, sink_plain, stdout);
 		fputc('\n', stdout);
@@ -1203,6 +1280,51 @@ static int sink_plainvec(void *data, int c, int64_t l)
 	return 0;
 }
 
+/* One further index into the handle's.  The file is opened ONCE (it may be a pipe, or stdin) and goes by its magic: the words of an FMD file and the
+ * records of a BRE file are decoded on the device and merged as one batch; an FMR file, anything with --host-fmd, an FMD on stdin and what the device
+ * declined are decoded to plain symbols on the host.  0, 1 (not a loadable index file) or the engine's negative code */
+static int merge_operand(rb3gpu_t *h, const char *fn)
+{
+	plainvec_t pv = {0, 0, 0};
+	char magic[4];
+	FILE *fp = rb3h_index_open(fn, magic);
+	const int kind = fp ? rb3h_index_kind(magic) : RB3H_INDEX_NONE;
+	int ret = 1, on_host = 0;
+	if (fp == 0) return 1;
+	if (!g_host_fmd && kind == RB3H_INDEX_FMD && fp != stdin) {
+		uint64_t *z = 0;
+		int64_t nw = 0, mc[6];
+		if (rb3h_fmd_read_words_fp(fp, &z, &nw, mc) == 0) {
+			ret = rb3gpu_merge_fmd_words(h, nw, z, mc);
+			free(z);
+			if (ret == RB3GPU_ESYMBOL || ret == RB3GPU_ENOMEM) { /* the device declined the stream: the host decoder reads the file again */
+				fclose(fp), fp = 0;
+				on_host = rb3h_index_read_runs(fn, sink_plainvec, &pv) == 0 && pv.l > 0;
+				ret = 1;
+			}
+		}
+	} else if (!g_host_fmd && kind == RB3H_INDEX_BRE) {
+		rb3h_bre_t b;
+		if (rb3h_bre_read_fp(fp, &b) == 0) {
+			rb3gpu_bre_stats_t st;
+			rb3gpu_tune(h, "verbose", 0); /* (the file may still be refused: see index_upload) */
+			ret = rb3gpu_merge_bre(h, b.b_per_run, b.n_rec, b.rec, &st);
+			rb3gpu_tune(h, "verbose", rb3h_verbose);
+			if (ret == 0 && (st.n_sym != b.ftr[1] || st.n_run != b.ftr[2])) ret = 1; /* the footer disagrees with what the device counted */
+			else if (ret == RB3GPU_ESYMBOL) ret = 1;
+			else if (ret == RB3GPU_ENOMEM) { /* no room on the device: the host decoder takes the records */
+				on_host = rb3h_bre_decode_runs(&b, sink_plainvec, &pv) == 0 && pv.l > 0;
+				ret = 1;
+			}
+			rb3h_bre_free(&b);
+		}
+	} else on_host = rb3h_index_read_runs_fp(fp, magic, sink_plainvec, &pv) == 0 && pv.l > 0;
+	if (fp && fp != stdin) fclose(fp);
+	if (on_host) ret = rb3gpu_merge_plain(h, pv.l, pv.s);
+	free(pv.s);
+	return ret;
+}
+
 int main_merge(int argc, char *argv[])
 {
 	int c, i, ret = 0, fmt = FMT_FMR, device = 0;
@@ -1241,32 +1363,8 @@ int main_merge(int argc, char *argv[])
 		return 1;
 	}
 	for (i = optind + 1; i < argc && ret == 0; ++i) {
-		plainvec_t pv = {0, 0, 0};
-		{ /* an FMD file: decoded on the device and merged as one batch */
-			uint64_t *z = 0;
-			int64_t nw = 0, mc[6];
-			if (!g_host_fmd && rb3h_fmd_read_words(argv[i], &z, &nw, mc) == 0) {
-				ret = rb3gpu_merge_fmd_words(h, nw, z, mc);
-				free(z);
-				if (ret == 0) {
-					if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] merged '%s'\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), argv[i]);
-					if (fn_tmp) {
-						FILE *fp = fopen(fn_tmp, "wb");
-						if (fp) { dump_fmr(h, &opt, fp); fclose(fp); }
-					}
-					continue;
-				}
-				if (ret != RB3GPU_ESYMBOL && ret != RB3GPU_ENOMEM) { fprintf(stderr, "ERROR: the GPU engine failed to merge '%s': %s\n", argv[i], rb3gpu_strerror(ret)); break; }
-				ret = 0; /* the device declined the stream: host decoder */
-			}
-		}
-		if (rb3h_index_read_runs(argv[i], sink_plainvec, &pv) < 0 || pv.l == 0) {
-			fprintf(stderr, "ERROR: failed to load FMR/FMD file '%s'\n", argv[i]);
-			free(pv.s); ret = 1;
-			break;
-		}
-		ret = rb3gpu_merge_plain(h, pv.l, pv.s);
-		free(pv.s);
+		ret = merge_operand(h, argv[i]);
+		if (ret > 0) { fprintf(stderr, "ERROR: failed to load FMR/FMD file '%s'\n", argv[i]); break; }
 		if (ret < 0) { fprintf(stderr, "ERROR: the GPU engine failed to merge '%s': %s\n", argv[i], rb3gpu_strerror(ret)); break; }
 		if (rb3h_verbose >= 3) fprintf(stderr, "[M::%s::%.3f*%.2f] merged '%s'\n", __func__, rb3h_realtime(), rb3h_percent_cpu(), argv[i]);
 		if (fn_tmp) {
@@ -2328,20 +2426,27 @@ static int sink_recode(void *data, int c, int64_t l)
 	return sink_runvec(&r->rv, c, l);
 }
 
+static const struct option recode_opts[] = {
+	{ "bre-run-bytes", required_argument, 0, 311 },
+	{ 0, 0, 0, 0 }
+};
+
 static int main_recode(int argc, char *argv[])
 {
 	int c, fmt = FMT_PLAIN, ret = 0, block_len = 0, max_nodes = 0;
 	int64_t i;
 	recode_t rc;
 	optind = 1;
-	while ((c = getopt(argc, argv, "dbo:l:n:")) >= 0) {
+	while ((c = getopt_long(argc, argv, "dbeo:l:n:", recode_opts, 0)) >= 0) {
 		if (c == 'd') fmt = FMT_FMD;
 		else if (c == 'b') fmt = FMT_FMR;
+		else if (c == 'e') fmt = FMT_BRE;
+		else if (c == 311) g_bre_run_bytes = atoi(optarg);
 		else if (c == 'l') block_len = atoi(optarg);
 		else if (c == 'n') max_nodes = atoi(optarg);
 		else if (c == 'o' && freopen(optarg, "wb", stdout) == 0) return 1;
 	}
-	if (argc - optind < 1) { fprintf(stderr, "Usage: ropebwt3-amd recode [-d|-b] [-o out] <in.fmd|in.fmr>\n"); return 1; }
+	if (argc - optind < 1 || g_bre_run_bytes < 1 || g_bre_run_bytes > 8) { fprintf(stderr, "Usage: ropebwt3-amd recode [-d|-b|-e [--bre-run-bytes 1..8]] [-o out] <in.fmd|in.fmr|in.bre>\n"); return 1; }
 	memset(&rc, 0, sizeof(rc));
 	if (rb3h_index_read_runs(argv[optind], sink_recode, &rc) < 0) { fprintf(stderr, "ERROR: failed to read '%s'\n", argv[optind]); free(rc.rv.a); return 1; }
 	if (fmt == FMT_FMD) {
@@ -2358,6 +2463,12 @@ static int main_recode(int argc, char *argv[])
 		for (i = 0; i < rc.rv.n && ret == 0; ++i) ret = rb3h_fmrw_enc(w, (int64_t)(rc.rv.a[i] >> 3), (int)(rc.rv.a[i] & 7));
 		if (ret == 0) ret = rb3h_fmrw_dump(w, stdout);
 		rb3h_fmrw_destroy(w);
+	} else if (fmt == FMT_BRE) {
+		rb3h_brew_t *w = rb3h_brew_init(stdout, g_bre_run_bytes);
+		if (w == 0) ret = -1;
+		for (i = 0; i < rc.rv.n && ret == 0; ++i) ret = rb3h_brew_enc(w, (int64_t)(rc.rv.a[i] >> 3), (int)(rc.rv.a[i] & 7));
+		if (ret == 0) ret = rb3h_brew_finish(w);
+		rb3h_brew_destroy(w);
 	} else {
 		for (i = 0; i < rc.rv.n && ret == 0; ++i) ret = sink_plain(stdout, (int)(rc.rv.a[i] & 7), (int64_t)(rc.rv.a[i] >> 3));
 		fputc('\n', stdout);

@@ -137,6 +137,7 @@ typedef int (*rb3h_run_f)(void *data, int c, int64_t l);
 /* decode every run of an FMD file in order (rld_restore + rld_dec, rld0.c:267-320, rld0.h:85-122) */
 int rb3h_fmd_read_runs(FILE *fp, rb3h_run_f emit, void *data, int64_t mcnt[6]);
 int rb3h_fmd_read_words(const char *fn, uint64_t **z, int64_t *n_words, int64_t mcnt[6]); /* undecoded, for rb3gpu_from_fmd_words */
+int rb3h_fmd_read_words_fp(FILE *fp, uint64_t **z, int64_t *n_words, int64_t mcnt[6]);    /* the same from a stream whose 4 bytes of magic have been consumed */
 
 /* ---- FMR (mrope) writer / reader ---- */
 struct rb3h_fmrw_s;
@@ -151,8 +152,40 @@ void rb3h_fmrw_destroy(rb3h_fmrw_t *w);
 /* decode an FMR file (mr_restore, mrope.c:161-177; rope_restore, rope.c:289-330) */
 int rb3h_fmr_read_runs(FILE *fp, rb3h_run_f emit, void *data);
 
-/* open an index file of either kind and stream its runs; returns 0, or <0 on error */
+/* ---- BRE, the reference's interchange format (bre.c) ---- */
+#define RB3H_BRE_EOPEN   (-1)  /* the file cannot be opened */
+#define RB3H_BRE_EMAGIC  (-2)  /* not "BRE\1" */
+#define RB3H_BRE_EHEADER (-3)  /* b_per_sym != 1, asize != 6, b_per_run outside 1..8, or the file ends in its header */
+#define RB3H_BRE_ERECORD (-4)  /* a record with a symbol above 5, or of no symbols in front of the footer */
+#define RB3H_BRE_EFOOTER (-5)  /* no all-zero record, fewer than 24 bytes behind it, counts that disagree with the records, or no records */
+#define RB3H_BRE_ENOMEM  (-6)
+/* a BRE file in host memory: rec points at n_rec raw records of 1 + b_per_run bytes (what rb3gpu_from_bre takes), ftr holds the footer's n_rec, n_sym, n_run */
+typedef struct { int b_per_run; int64_t n_rec, ftr[3]; const uint8_t *rec; uint8_t *buf; } rb3h_bre_t;
+int rb3h_bre_read(const char *fn, rb3h_bre_t *b);                           /* "-": stdin; 0 or an RB3H_BRE_E* code */
+int rb3h_bre_read_fp(FILE *fp, rb3h_bre_t *b);                              /* the 4 bytes of magic already consumed */
+void rb3h_bre_free(rb3h_bre_t *b);
+int rb3h_bre_decode_runs(const rb3h_bre_t *b, rb3h_run_f emit, void *data); /* maximal runs (records of one symbol joined); all three counts are held against the footer */
+int rb3h_bre_read_runs(FILE *fp, rb3h_run_f emit, void *data);              /* read_fp + decode_runs */
+int rb3h_bre_write_header(FILE *fp, int b_per_run);
+int rb3h_bre_write_footer(FILE *fp, int b_per_run, int64_t n_rec, int64_t n_sym, int64_t n_run); /* the all-zero record and the counts */
+/* the host's packer: header at init, records as runs arrive (adjacent runs of one symbol are joined, long ones split), footer at finish */
+struct rb3h_brew_s;
+typedef struct rb3h_brew_s rb3h_brew_t;
+rb3h_brew_t *rb3h_brew_init(FILE *fp, int b_per_run);
+int rb3h_brew_enc(rb3h_brew_t *w, int64_t l, int c);
+int rb3h_brew_enc_words(rb3h_brew_t *w, int64_t n, const uint64_t *words, int64_t end); /* bulk: start << 3 | sym of maximal runs */
+int rb3h_brew_finish(rb3h_brew_t *w);
+void rb3h_brew_destroy(rb3h_brew_t *w);
+
+/* open an index file of any kind and stream its runs; returns 0, or <0 on error */
 int rb3h_index_read_runs(const char *fn, rb3h_run_f emit, void *data);
+/* the same in two steps, for a caller that treats the kinds differently and must open the file only once (it may be a pipe, or stdin: "-"):
+ * rb3h_index_open reads the 4 bytes of magic and returns the stream behind them (NULL: no file, or shorter; close it unless it is stdin),
+ * rb3h_index_kind names them, rb3h_index_read_runs_fp / rb3h_fmd_read_words_fp / rb3h_bre_read_fp go on from there */
+enum { RB3H_INDEX_NONE = 0, RB3H_INDEX_FMD, RB3H_INDEX_FMR, RB3H_INDEX_BRE };
+FILE *rb3h_index_open(const char *fn, char magic[4]);
+int rb3h_index_kind(const char magic[4]);
+int rb3h_index_read_runs_fp(FILE *fp, const char magic[4], rb3h_run_f emit, void *data);
 
 #ifdef __cplusplus
 }

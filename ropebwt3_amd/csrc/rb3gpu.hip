@@ -63,6 +63,18 @@ int rb3fmd_decode_fill(rb3fmd_dec *ctx, uint8_t *d_plain);
 int rb3fmd_decode_range(rb3fmd_dec *ctx, int64_t p0, int64_t p1, uint8_t *d_out);
 void rb3fmd_decode_end(rb3fmd_dec *ctx);
 int64_t rb3fmd_decode_bytes(const rb3fmd_dec *ctx);
+/* the BRE record packer and unpacker live in rb3gpu_bre.hip */
+struct rb3bre_enc;
+int rb3bre_enc_begin(hipStream_t st, int bpr, int64_t cap_runs, int64_t win, uint8_t *stage[2], rb3bre_enc **e);
+uint64_t *rb3bre_enc_buffer(rb3bre_enc *e, int64_t *room);
+int rb3bre_enc_piece(rb3bre_enc *e, int64_t n_new, int64_t end, rb3gpu_emit_bytes_f emit, void *data);
+void rb3bre_enc_end(rb3bre_enc *e, rb3gpu_bre_stats_t *st);
+void rb3bre_enc_abort(rb3bre_enc *e);
+struct rb3bre_dec;
+int rb3bre_dec_begin(hipStream_t st, int bpr, int64_t n_rec, const uint8_t *d_rec, rb3bre_dec **ctx, int64_t *n_sym, int64_t *n_run, double *ms_scan);
+int rb3bre_dec_range(rb3bre_dec *ctx, int64_t p0, int64_t p1, uint8_t *d_out);
+void rb3bre_dec_end(rb3bre_dec *ctx);
+int64_t rb3bre_dec_bytes(const rb3bre_dec *ctx);
 
 struct Buf {
 	void *p = nullptr;
@@ -149,6 +161,7 @@ struct Tune {
 	int vmm_reserve = 0;     // (tests) MB of address space a new range reserves instead of 32 x its size (at least 16 GB)
 	int defer_free = 1;      // keep replaced buffers on a list and hipFree them in bulk (0: at once; hipFree waits for every stream of the device)
 	int64_t fmd_piece = 0;   // runs the FMD packer takes at a time (0: 64 M; rb3gpu_export_fmd_words)
+	int64_t bre_piece = 0;   // runs the BRE packer takes at a time (0: 64 M; rb3gpu_export_bre); a piece ends with a whole group, so it may hold up to 8191 more
 	int sh_host_rounds = 0;  // rb3gpu_sh_merge with ONE interval: the host reads the split sizes back after every round, as with several (0: the rounds run back to back on the device)
 	int sh_block = 0;        // threads per block of k_sh_round at eight states per octet: 256 or 1024; 0: 1024 below 3 M chains
 	int sh_states = 0;       // states per octet of k_sh_round (1, 2, 4, 8); 0: by the number of chains
@@ -673,6 +686,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "load_chunk")) t.load_chunk = v < 1 ? 1 : v;
 	else if (!strcmp(key, "lf_check")) t.lf_check = v < 0 ? 0 : v > (1 << 30) ? (1 << 30) : (int)v;
 	else if (!strcmp(key, "fmd_piece")) t.fmd_piece = v < 0 ? 0 : v;
+	else if (!strcmp(key, "bre_piece")) t.bre_piece = v < 0 ? 0 : v;
+	else if (!strcmp(key, "verbose")) h->opt.verbose = v < 0 ? 0 : v > 9 ? 9 : (int)v; // (the level of rb3gpu_opt_t on a live handle: a caller that may still refuse what the engine is doing keeps it quiet until then)
 	else if (!strcmp(key, "mem_slice")) t.mem_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "hapdiv_slice")) t.hapdiv_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "hapdiv_table")) t.hapdiv_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
@@ -721,7 +736,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -3324,6 +3339,23 @@ __global__ void __launch_bounds__(256) k_runs_before(const uint64_t *off8, int64
 	if (g <= ngrp) out[g] = g < ngrp ? off8[g * 8] : total;
 }
 
+/* An export packer is about to take `need` bytes of device memory: where that does not fit beside the merge scratch of the handle, the scratch goes (the next
+ * merge obtains it again).  Not inside a two-phase merge: its uncommitted index lives in the spare buffers. */
+static int export_make_room(rb3gpu_t *h, size_t need, int64_t nr, const char *who)
+{
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) == hipSuccess && need + ((size_t)64 << 20) > fr && !h->mg_active) {
+		HIPCHK(hipStreamSynchronize(h->st));
+		Buf *scratch[] = { &h->b2, &h->pos, &h->post, &h->tcnt, &h->tpre, &h->jg, &h->wl, &h->wls, &h->dl, &h->dlx, &h->wstat, &h->wplane, &h->wruns, &h->gslots, &h->glist, &h->pslots, &h->shc, &h->shn, &h->shs, &h->shr };
+		for (Buf *b : scratch) buf_release(h, *b);
+		ib_release(h, 1 - h->cur);
+		garbage_collect(h, true);
+		h->sid_dirty[0] = h->sid_dirty[1] = RB3_TENT_HALF; // (the stretch table is gone: a fresh one is cleared whole)
+		if (h->opt.verbose >= 3) fprintf(stderr, "[M::%s::%.3f] %lld runs: the merge scratch of the handle released for the packer's tables\n", who, now_s() - h->t0, (long long)nr);
+	} else (void)hipGetLastError();
+	return 0;
+}
+
 /* The FMD word stream of the index, packed on the device A PIECE OF THE RUNS AT A TIME (rb3gpu_fmdenc.hip, rb3fmd_enc_*; round 6): the runs of as many groups as
  * make `piece` runs are written behind what the packer carried over from the piece before, packed, and their words go to the host.  Device memory: 34 bytes per
  * run of a PIECE (64 M runs by default: 2.2 GB; rb3gpu_tune "fmd_piece"), not of the index -- 4.99 G runs of four human haplotypes held 40 GB of run starts and
@@ -3353,18 +3385,7 @@ int rb3gpu_export_fmd_words(rb3gpu_t *h, uint64_t **words, int64_t *n_words)
 	if (piece < 32768) piece = 32768; // (a piece must hold a few chunks of the packer's speculation -- rb3fmd_enc_piece --, and it ends with a whole group: up to 8192 runs short)
 	const bool one = nr <= piece;
 	const int64_t cap = one ? nr + 16 : piece + RB3_GRP + 8192 + 1024; // (a piece ends with a whole group: at most 8192 runs more; + what the packer carries over)
-	{ // the packer holds ~26 bytes per run of a piece beside the run starts (8): where that does not fit beside the merge scratch of the handle, the scratch goes (the next merge obtains it again)
-		size_t fr = 0, tot = 0;
-		if (hipMemGetInfo(&fr, &tot) == hipSuccess && (size_t)cap * 34 + ((size_t)64 << 20) > fr && !h->mg_active) { // (not inside a two-phase merge: its uncommitted index lives in the spare buffers)
-			HIPCHK(hipStreamSynchronize(h->st));
-			Buf *scratch[] = { &h->b2, &h->pos, &h->post, &h->tcnt, &h->tpre, &h->jg, &h->wl, &h->wls, &h->dl, &h->dlx, &h->wstat, &h->wplane, &h->wruns, &h->gslots, &h->glist, &h->pslots, &h->shc, &h->shn, &h->shs, &h->shr };
-			for (Buf *b : scratch) buf_release(h, *b);
-			ib_release(h, 1 - h->cur);
-			garbage_collect(h, true);
-			h->sid_dirty[0] = h->sid_dirty[1] = RB3_TENT_HALF; // (the stretch table is gone: a fresh one is cleared whole)
-			if (h->opt.verbose >= 3) fprintf(stderr, "[M::%s::%.3f] %lld runs: the merge scratch of the handle released for the packer's tables\n", __func__, now_s() - h->t0, (long long)nr);
-		} else (void)hipGetLastError();
-	}
+	if ((r = export_make_room(h, (size_t)cap * 34, nr, __func__)) < 0) return r; // the packer holds ~26 bytes per run of a piece beside the run starts (8)
 	rb3fmd_enc *enc = nullptr;
 	int fr = rb3fmd_enc_begin(h->st, h->n, cap, &enc);
 	if (fr == -1 && !h->garbage.empty()) { // no room for the packer's tables while replaced buffers are still held
@@ -3484,8 +3505,19 @@ static int fmd_words_to_b2(rb3gpu_t *h, int64_t n_words, const uint64_t *words, 
  * self-contained, so any range of positions can be decoded on its own), twice -- the first pass only counts the slots and symbols
  * of every group (k_pass1w + k_decide on the chunk), one scan over all groups then gives every slot its place and the directory
  * its counts, the second pass writes the slots of each chunk there (k_pass1w + k_pass2w).  Device memory beyond the stream and the
- * index: one chunk of symbols and its window scratch (~0.23 GB for the default chunk of 134 M symbols). */
-static int from_fmd_chunked(rb3gpu_t *h, rb3fmd_dec *ctx, int64_t n, const int64_t mcnt[RB3GPU_ASIZE])
+ * index: one chunk of symbols and its window scratch (~0.23 GB for the default chunk of 134 M symbols).
+ * What is asked of the stream is the symbols of a range of positions, so anything that can give those is a source of this builder: the FMD
+ * decoder (rb3fmd_decode_range) and the BRE fill (rb3bre_dec_range). */
+struct RangeSrc {
+	int (*range)(void *ctx, int64_t p0, int64_t p1, uint8_t *d_out); // symbols [p0, p1) into d_out, queued on the handle's stream; < 0: failed
+	void *ctx;
+	int64_t bytes;    // device memory the source holds beside the stream
+	const char *what;
+};
+static int fmd_range(void *ctx, int64_t p0, int64_t p1, uint8_t *d_out) { return rb3fmd_decode_range((rb3fmd_dec*)ctx, p0, p1, d_out); }
+static int bre_range(void *ctx, int64_t p0, int64_t p1, uint8_t *d_out) { return rb3bre_dec_range((rb3bre_dec*)ctx, p0, p1, d_out); }
+
+static int from_fmd_chunked(rb3gpu_t *h, const RangeSrc &src, int64_t n, const int64_t mcnt[RB3GPU_ASIZE])
 {
 	const int64_t ngrp = (n >> RB3_GRP_BITS) + 1, nwin = (n >> RB3_WIN_BITS) + 1, CG = h->tn.load_chunk;
 	const int64_t csym = CG << RB3_GRP_BITS, cwin = CG * RB3_GRP_WINS;
@@ -3508,7 +3540,7 @@ static int from_fmd_chunked(rb3gpu_t *h, rb3fmd_dec *ctx, int64_t n, const int64
 			const int64_t g1 = g0 + CG < ngrp ? g0 + CG : ngrp, p0 = g0 << RB3_GRP_BITS, p1 = (g1 << RB3_GRP_BITS) < n ? (g1 << RB3_GRP_BITS) : n;
 			const int64_t rem = n - p0;                                   // symbols from the chunk's start to the end of the index
 			const int64_t nw = g1 == ngrp ? (rem >> RB3_WIN_BITS) + 1 : (g1 - g0) * RB3_GRP_WINS; // (the last chunk ends with the window of position n)
-			if (rb3fmd_decode_range(ctx, p0, p1, (uint8_t*)h->b2.p) < 0) return RB3GPU_ENODEV;
+			if (src.range(src.ctx, p0, p1, (uint8_t*)h->b2.p) < 0) return RB3GPU_ENODEV;
 			const dim3 g1w((unsigned)((nw + RB3_REB_WAVES * RB3_REB_WPW - 1) / (RB3_REB_WAVES * RB3_REB_WPW))), b1w(64 * RB3_REB_WAVES);
 			hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pass1w<true, 3>), g1w, b1w, 0, h->st, none, (const int64_t*)nullptr, (const uint8_t*)h->b2.p, rem, rem, (const int64_t*)nullptr,
 					(uint4*)h->wstat.p, (uint32_t*)h->wplane.p, (uint16_t*)h->wruns.p, nw, (const unsigned long long*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
@@ -3541,9 +3573,9 @@ static int from_fmd_chunked(rb3gpu_t *h, rb3fmd_dec *ctx, int64_t n, const int64
 	acc[0] = 0;
 	for (int a = 0; a < 6; ++a) acc[a + 1] = acc[a] + (int64_t)total[a];
 	index_install(h, ngrp, onslots, n, acc);
-	if (h->bytes_owned + rb3fmd_decode_bytes(ctx) > h->stt.bytes_peak) h->stt.bytes_peak = h->bytes_owned + rb3fmd_decode_bytes(ctx);
+	if (h->bytes_owned + src.bytes > h->stt.bytes_peak) h->stt.bytes_peak = h->bytes_owned + src.bytes;
 	if (h->opt.verbose >= 3)
-		fprintf(stderr, "[M::%s::%.3f] built %lld symbols into %lld slots from the FMD stream in chunks of %lld symbols (%.3f ms)\n", __func__, now_s() - h->t0, (long long)n, (long long)onslots, (long long)csym, ev_ms(h->ev[0], h->ev[1]));
+		fprintf(stderr, "[M::%s::%.3f] built %lld symbols into %lld slots from the %s stream in chunks of %lld symbols (%.3f ms)\n", __func__, now_s() - h->t0, (long long)n, (long long)onslots, src.what, (long long)csym, ev_ms(h->ev[0], h->ev[1]));
 	return 0;
 }
 
@@ -3566,7 +3598,8 @@ int rb3gpu_from_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, c
 			if (tot != n_sym) { rb3fmd_decode_end(ctx); return RB3GPU_ESYMBOL; }
 		}
 		if (n_sym > (h->tn.load_chunk << RB3_GRP_BITS)) {
-			r = from_fmd_chunked(h, ctx, n_sym, mcnt);
+			const RangeSrc src = { fmd_range, ctx, rb3fmd_decode_bytes(ctx), "FMD" };
+			r = from_fmd_chunked(h, src, n_sym, mcnt);
 			rb3fmd_decode_end(ctx);
 			if (r < 0) index_drop(h);
 			return r;
@@ -3591,6 +3624,158 @@ int rb3gpu_merge_fmd_words(rb3gpu_t *h, int64_t n_words, const uint64_t *words, 
 	int r;
 	if ((r = fmd_words_to_b2(h, n_words, words, mcnt, &n_sym)) < 0) return r; // (checks the total against the header)
 	return merge_core(h, n_sym, (const uint8_t*)h->b2.p, 1, nullptr, nullptr, 0, 0, nullptr);
+}
+
+/* ---- BRE records (rb3gpu_bre.hip) ---- */
+
+/* The records of the index's BRE file, in order (mr_print_bre, build.c:85-106, without header and footer): the maximal runs the handle finds for the FMD
+ * packer (k_export_runs_g), a PIECE of them at a time -- the runs of as many whole groups as make bre_piece runs --, counted, scanned and written as records
+ * on the device; the bytes of a piece reach emit window by window through the pinned staging buffers.  Device memory: 16 bytes per run of a piece and two
+ * windows of records, not a function of the index. */
+int rb3gpu_export_bre(rb3gpu_t *h, int b_per_run, rb3gpu_emit_bytes_f emit, void *data, rb3gpu_bre_stats_t *st)
+{
+	if (!h || !emit || b_per_run < 1 || b_per_run > 4) return RB3GPU_EINVAL;
+	HIPCHK(hipSetDevice(h->dev));
+	if (h->grp == nullptr) return RB3GPU_ESTATE;
+	const double t = now_s();
+	const IdxView iv = view_of(h);
+	int r;
+	if (st) memset(st, 0, sizeof(*st));
+	if ((r = buf_ensure(h, h->misc, MISC_WORDS * 8)) < 0) return r;
+	const int64_t ngrp = (h->n + RB3_GRP - 1) >> RB3_GRP_BITS;
+	if ((r = buf_ensure(h, h->gstat, (size_t)ngrp * 32)) < 0) return r;
+	if ((r = buf_ensure(h, h->gpre, (size_t)ngrp * 64)) < 0) return r;
+	if ((r = buf_ensure(h, h->xbuf, (size_t)(ngrp + 1) * 8)) < 0) return r;
+	uint32_t *cnt8 = (uint32_t*)h->gstat.p;
+	uint64_t *off8 = (uint64_t*)h->gpre.p, total[8];
+	const dim3 blk(256);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_runs_g<false>), dim3((unsigned)((ngrp + 3) / 4)), blk, 0, h->st, iv, (int64_t)0, ngrp, cnt8, (const uint64_t*)nullptr, (uint64_t*)nullptr);
+	if ((r = scan_records(h, cnt8, ngrp, off8, (uint64_t*)h->misc.p + MISC_IX_TOT, total)) < 0) return r;
+	const int64_t nr = (int64_t)total[0];
+	if (nr <= 0) return RB3GPU_EINTERNAL;
+	std::vector<uint64_t> before((size_t)ngrp + 1); // the runs before every group
+	hipLaunchKernelGGL(k_runs_before, dim3((unsigned)((ngrp + 1 + 255) / 256)), dim3(256), 0, h->st, (const uint64_t*)off8, ngrp, (uint64_t)nr, (uint64_t*)h->xbuf.p);
+	HIPCHK(hipMemcpyAsync(before.data(), h->xbuf.p, (size_t)(ngrp + 1) * 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	int64_t piece = h->tn.bre_piece > 0 ? h->tn.bre_piece : ((int64_t)64 << 20);
+	if (piece > nr) piece = nr;
+	const int64_t cap = piece + RB3_GRP; // (a piece ends with a whole group: at most 8191 runs more)
+	int64_t win = (piece * 2 + 4095) & ~(int64_t)4095; // (a window of record bytes: what the staging buffers hold, less where pieces are small)
+	if (win > (int64_t)RB3_STAGE_BYTES) win = (int64_t)RB3_STAGE_BYTES;
+	if (h->stage[0] == nullptr)
+		for (int i = 0; i < 2; ++i)
+			if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage[i] = nullptr; break; }
+	if ((r = export_make_room(h, (size_t)cap * 16 + 2 * (size_t)win, nr, __func__)) < 0) return r; // (run starts and record offsets of a piece, two windows)
+	rb3bre_enc *enc = nullptr;
+	int fr = rb3bre_enc_begin(h->st, b_per_run, cap, win, h->stage, &enc);
+	if (fr == -1 && !h->garbage.empty()) { // no room while replaced buffers are still held
+		garbage_collect(h, true);
+		fr = rb3bre_enc_begin(h->st, b_per_run, cap, win, h->stage, &enc);
+	}
+	for (int64_t ga = 0; ga < ngrp && fr == 0;) {
+		int64_t room = 0;
+		uint64_t *dst = rb3bre_enc_buffer(enc, &room);
+		// [ga, gb): the fewest groups that hold `piece` runs, or all that are left
+		int64_t lo = ga + 1, hi = ngrp;
+		while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)(before[(size_t)mid] - before[(size_t)ga]) >= piece) hi = mid; else lo = mid + 1; }
+		const int64_t gb = lo, nn = (int64_t)(before[(size_t)gb] - before[(size_t)ga]);
+		if (nn > room) { fr = -3; break; }
+		if (nn > 0)
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(k_export_runs_g<true>), dim3((unsigned)((gb - ga + 3) / 4)), blk, 0, h->st, iv, ga, gb - ga, cnt8 + ga * 8, (const uint64_t*)(off8 + ga * 8), dst - before[(size_t)ga]);
+		fr = rb3bre_enc_piece(enc, nn, gb == ngrp ? h->n : -1, emit, data);
+		ga = gb;
+	}
+	rb3gpu_bre_stats_t s;
+	memset(&s, 0, sizeof(s));
+	if (enc) rb3bre_enc_end(enc, &s);
+	(void)hipGetLastError();
+	h->stt.ms_export += (now_s() - t) * 1e3;
+	if (fr < 0) return fr == -1 ? RB3GPU_ENOMEM : fr == -2 ? RB3GPU_ENODEV : fr == -4 ? RB3GPU_EINVAL : RB3GPU_EINTERNAL;
+	if (s.n_run != nr) return RB3GPU_EINTERNAL;
+	s.n_sym = h->n;
+	if (st) *st = s;
+	if (h->opt.verbose >= 3)
+		fprintf(stderr, "[M::%s::%.3f] packed %lld runs into %lld BRE records of %d bytes on the GPU in %.3f ms (%lld piece%s; scan %.3f ms, pack %.3f ms)\n", __func__, now_s() - h->t0, (long long)nr, (long long)s.n_rec, 1 + b_per_run,
+				(now_s() - t) * 1e3, (long long)s.n_pieces, s.n_pieces == 1 ? "" : "s", s.ms_scan, s.ms_pack);
+	return 0;
+}
+
+/* the raw records into HBM (h->xbuf), scanned: *ctx is open on them */
+static int bre_open(rb3gpu_t *h, int b_per_run, int64_t n_rec, const uint8_t *records, rb3bre_dec **ctx, rb3gpu_bre_stats_t *s)
+{
+	const size_t nb = (size_t)n_rec * (size_t)(1 + b_per_run);
+	int r;
+	memset(s, 0, sizeof(*s));
+	if ((r = buf_ensure(h, h->xbuf, nb + 16, true)) < 0) return r;
+	if (h->stage[0] == nullptr)
+		for (int i = 0; i < 2; ++i)
+			if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage[i] = nullptr; break; }
+	const double t0 = now_s();
+	hipEvent_t done[2] = { h->ev[4], h->ev[5] };
+	HIPCHK(h2d_copy(h->xbuf.p, records, nb, h->st, h->stage, done));
+	h->stt.ms_h2d += (now_s() - t0) * 1e3;
+	r = rb3bre_dec_begin(h->st, b_per_run, n_rec, (const uint8_t*)h->xbuf.p, ctx, &s->n_sym, &s->n_run, &s->ms_scan);
+	if (r < 0) return r == -1 ? RB3GPU_ENOMEM : r == -2 ? RB3GPU_ENODEV : RB3GPU_ESYMBOL;
+	s->n_rec = n_rec;
+	return 0;
+}
+
+/* every symbol of an open stream into h->b2, timed */
+static int bre_fill_b2(rb3gpu_t *h, rb3bre_dec *ctx, rb3gpu_bre_stats_t *s)
+{
+	int r;
+	if ((r = buf_ensure(h, h->b2, (size_t)s->n_sym + 16)) < 0) return r;
+	HIPCHK(hipEventRecord(h->ev[0], h->st));
+	if (rb3bre_dec_range(ctx, 0, s->n_sym, (uint8_t*)h->b2.p) < 0) return RB3GPU_ENODEV;
+	HIPCHK(hipEventRecord(h->ev[1], h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	s->ms_fill = ev_ms(h->ev[0], h->ev[1]);
+	return 0;
+}
+
+/* rld_restore's BRE branch (rld0.c:245-283) followed by rb3_enc_fmd2fmr (fm-index.c:56-85), on the device: the records are validated and scanned, then the
+ * symbols of a range are what the two builders of an FMD stream take as well -- whole into rb3gpu_from_plain_dev, or chunk by chunk (load_chunk groups) */
+int rb3gpu_from_bre(rb3gpu_t *h, int b_per_run, int64_t n_rec, const uint8_t *records, rb3gpu_bre_stats_t *st)
+{
+	if (!h || !records || n_rec <= 0 || b_per_run < 1 || b_per_run > 8) return RB3GPU_EINVAL;
+	HIPCHK(hipSetDevice(h->dev));
+	rb3bre_dec *ctx = nullptr;
+	rb3gpu_bre_stats_t s;
+	int r;
+	if ((r = bre_open(h, b_per_run, n_rec, records, &ctx, &s)) < 0) return r;
+	if (s.n_sym > (h->tn.load_chunk << RB3_GRP_BITS)) {
+		const RangeSrc src = { bre_range, ctx, rb3bre_dec_bytes(ctx), "BRE" };
+		r = from_fmd_chunked(h, src, s.n_sym, nullptr);
+		if (r < 0) index_drop(h);
+		s.n_pieces = ((s.n_sym >> RB3_GRP_BITS) + h->tn.load_chunk) / h->tn.load_chunk;
+	} else {
+		r = bre_fill_b2(h, ctx, &s);
+		s.n_pieces = 1;
+	}
+	rb3bre_dec_end(ctx);
+	if (r < 0) return r;
+	if (s.n_pieces == 1 && (r = rb3gpu_from_plain_dev(h, s.n_sym, (const uint8_t*)h->b2.p)) < 0) return r;
+	if (st) *st = s;
+	return 0;
+}
+
+/* the same stream merged into the index the handle holds as one batch, like rb3gpu_merge_fmd_words */
+int rb3gpu_merge_bre(rb3gpu_t *h, int b_per_run, int64_t n_rec, const uint8_t *records, rb3gpu_bre_stats_t *st)
+{
+	if (!h || !records || n_rec <= 0 || b_per_run < 1 || b_per_run > 8) return RB3GPU_EINVAL;
+	RB3_IO_ONLY(h);
+	HIPCHK(hipSetDevice(h->dev));
+	if (h->n <= 0) return RB3GPU_ESTATE;
+	rb3bre_dec *ctx = nullptr;
+	rb3gpu_bre_stats_t s;
+	int r;
+	if ((r = bre_open(h, b_per_run, n_rec, records, &ctx, &s)) < 0) return r;
+	r = bre_fill_b2(h, ctx, &s);
+	rb3bre_dec_end(ctx);
+	if (r < 0) return r;
+	s.n_pieces = 1;
+	if (st) *st = s;
+	return merge_core(h, s.n_sym, (const uint8_t*)h->b2.p, 1, nullptr, nullptr, 0, 0, nullptr);
 }
 
 /* rb3_fmi_merge (fm-index.c:251-277) between two handles, which may sit on different GPUs of the node: the index of `src` is

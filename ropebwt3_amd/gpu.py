@@ -45,6 +45,15 @@ class Stats(ctypes.Structure):
 EMIT_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64)
 EMITW_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64)
 EMIT_WORDS_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64)
+EMIT_BYTES_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint8))
+
+
+class BreStats(ctypes.Structure):
+    """rb3gpu_bre_stats_t"""
+    _fields_ = [("n_rec", ctypes.c_int64), ("n_sym", ctypes.c_int64), ("n_run", ctypes.c_int64), ("n_pieces", ctypes.c_int64),
+                ("ms_scan", ctypes.c_double), ("ms_pack", ctypes.c_double), ("ms_fill", ctypes.c_double)]
+
+
 KOUNT_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int64))
 
 
@@ -198,6 +207,9 @@ SYMBOLS = {
     "rb3gpu_from_runs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "rb3gpu_from_fmd_words": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_merge_fmd_words": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "rb3gpu_export_bre": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, EMIT_BYTES_F, ctypes.c_void_p, ctypes.POINTER(BreStats)]),
+    "rb3gpu_from_bre": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(BreStats)]),
+    "rb3gpu_merge_bre": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(BreStats)]),
     "rb3gpu_merge_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_tune": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
     "rb3gpu_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Stats)]),
@@ -550,6 +562,38 @@ class Rb3Gpu:
         out = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint64)), shape=(n.value,)).copy()
         self._lib.rb3gpu_host_free(p)
         return out
+
+    def export_bre(self, b_per_run=2, stats=None):
+        """the records of the index's BRE file (`build -e` without header and footer), packed on the GPU: bytes.  stats: a dict that
+        receives n_rec, n_sym, n_run (the footer's counts), n_pieces, ms_scan and ms_pack"""
+        parts = []
+
+        def emit(_data, n, p):
+            parts.append(ctypes.string_at(p, n))
+            return 0
+        st = BreStats()
+        self._chk(self._lib.rb3gpu_export_bre(self._h, int(b_per_run), EMIT_BYTES_F(emit), None, ctypes.byref(st)), "rb3gpu_export_bre")
+        if stats is not None:
+            stats.update({k: getattr(st, k) for k, _ in BreStats._fields_})
+        return b"".join(parts)
+
+    def _bre_call(self, fn, name, records, b_per_run, stats):
+        rec = np.frombuffer(bytes(records), dtype=np.uint8)
+        rs = 1 + int(b_per_run)
+        if rec.size % rs != 0:
+            raise ValueError("%d bytes are not whole records of %d bytes" % (rec.size, rs))
+        st = BreStats()
+        self._chk(fn(self._h, int(b_per_run), rec.size // rs, rec.ctypes.data if rec.size else None, ctypes.byref(st)), name)
+        if stats is not None:
+            stats.update({k: getattr(st, k) for k, _ in BreStats._fields_})
+
+    def from_bre(self, records, b_per_run=2, stats=None):
+        """index the records of a BRE file (read_bre), unpacked on the device; stats: the counts the device found, ms_scan, ms_fill, n_pieces"""
+        self._bre_call(self._lib.rb3gpu_from_bre, "rb3gpu_from_bre", records, b_per_run, stats)
+
+    def merge_bre(self, records, b_per_run=2, stats=None):
+        """merge the records of a BRE file into the index as one batch (rb3gpu_merge_bre)"""
+        self._bre_call(self._lib.rb3gpu_merge_bre, "rb3gpu_merge_bre", records, b_per_run, stats)
 
     def merge_index(self, other):
         """merge the whole index of another handle (any GPU of the node) into this one (rb3_fmi_merge, fm-index.c:251-277)"""
@@ -1274,6 +1318,41 @@ class Shard:
         r = self._lib.rb3gpu_shard_gather(s)
         if r < 0:
             raise Rb3GpuError(int(r), "rb3gpu_shard_gather")
+
+
+def read_bre(path):
+    """a BRE file (bre.h of the reference) -> (b_per_run, records, (n_rec, n_sym, n_run)): the raw records in front of the all-zero
+    record and the footer's three counts.  ValueError for anything the host library's reader refuses as well"""
+    raw = open(path, "rb").read()
+    if raw[:4] != b"BRE\x01" or len(raw) < 24:
+        raise ValueError("not a BRE file")
+    bps, bpr = raw[4], raw[5]
+    asize, l_aux = int.from_bytes(raw[8:16], "little"), int.from_bytes(raw[16:24], "little")
+    if bps != 1 or asize != 6 or not 1 <= bpr <= 8:
+        raise ValueError("BRE header: b_per_sym %d, b_per_run %d, asize %d" % (bps, bpr, asize))
+    body, rs = raw[24 + l_aux:], 1 + bpr
+    a = np.frombuffer(body[:len(body) // rs * rs], dtype=np.uint8).reshape(-1, rs)
+    zero = np.flatnonzero(~a.any(axis=1))
+    if zero.size == 0:
+        raise ValueError("BRE file without an all-zero record")
+    n_rec = int(zero[0])
+    if n_rec == 0 or int(a[:n_rec, 0].max()) > 5 or not a[:n_rec, 1:].any(axis=1).all():
+        raise ValueError("BRE file with no records, a symbol above 5 or a record of no symbols")
+    ftr = body[(n_rec + 1) * rs:]
+    if len(ftr) < 24:
+        raise ValueError("BRE file without a footer")
+    counts = tuple(int.from_bytes(ftr[8 * i:8 * i + 8], "little") for i in range(3))
+    if counts[0] != n_rec:
+        raise ValueError("BRE footer: %d records, the file holds %d" % (counts[0], n_rec))
+    return bpr, body[:n_rec * rs], counts
+
+
+def write_bre(path, records, b_per_run, counts):
+    """header, records, all-zero record and the three counts (n_rec, n_sym, n_run) as a BRE file"""
+    with open(path, "wb") as fp:
+        fp.write(b"BRE\x01" + bytes([1, int(b_per_run), 2, 0]) + (6).to_bytes(8, "little") + (0).to_bytes(8, "little"))
+        fp.write(bytes(records))
+        fp.write(bytes(1 + int(b_per_run)) + b"".join(int(c).to_bytes(8, "little") for c in counts))
 
 
 def kount_lines(kmers, counts):
