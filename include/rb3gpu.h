@@ -651,6 +651,18 @@ typedef int (*rb3gpu_retrieve_cb)(void *ud, int64_t i0, int64_t n, const int64_t
 typedef struct { double ms_total, ms_count, ms_emit; int64_t n_rows, n_symbols, n_steps, n_slices; } rb3gpu_retrieve_stats_t;
 int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_retrieve_stats_t *st);
 
+/* rb3gpu_retrieve in pieces: the same answers through the same callback, cut into the same slices by "get_slice", but no walker follows more
+ * than one piece of a string.  The rows of the index are cut by splitters -- the acc[1] sentinel rows and every row k >= acc[1] with (k - acc[1]) a multiple of
+ * 2^S, S = rb3gpu_tune "get_piece" (default 8) -- and the call walks the WHOLE index once, every piece from its splitter to the next at the same time, joins the
+ * pieces by pointer jumping, sorts them by (string, distance from its start) and then writes every slice of rows with all of the pieces of its strings side by
+ * side.  It pays where a string is long or much of the index is asked for; for a few short rows rb3gpu_retrieve does less.  n < 0 with rows NULL: all the
+ * strings, rows 0 .. acc[1] - 1 (the callback's i0 then counts strings).  The call holds about 48 bytes per piece (acc[1] + (acc[6] - acc[1]) / 2^S pieces),
+ * 8 per string and 60 per row asked for on the device besides the output of a slice; nothing is kept between calls.  Errors as rb3gpu_retrieve; RB3GPU_EUNSUP
+ * also for acc[1] >= 2^31 or 2^32 pieces or more.  st (may be NULL): ms_total wall time; ms_pieces, ms_join, ms_sort, ms_emit the phases (HIP events);
+ * n_pieces; max_piece_steps the longest piece; n_steps the LF steps of the pieces, of the rows down to their first splitter, and of the writing walks */
+typedef struct { double ms_total, ms_pieces, ms_join, ms_sort, ms_emit; int64_t n_rows, n_symbols, n_slices, n_pieces, n_steps, max_piece_steps; } rb3gpu_pieces_stats_t;
+int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_pieces_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -670,6 +682,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
  *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e and rb3gpu_sw_local; 0 = 16 K), "sw_table" N (as "hapdiv_table", for both);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
+ *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8);
  *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c

@@ -1865,8 +1865,10 @@ static int main_suffix(int argc, char *argv[])
 
 /* get <idx> <int> [...] (main_get, main.c:135-165 of the reference): for every argument, read with atol, the string in front of the suffix of that row --
  * for a sentinel's row the whole indexed string -- as `>row end_row` and a line of $ACGTN letters; rows outside the index print nothing.  All rows of the
- * command line go through ONE call of rb3gpu_retrieve.  Arguments that begin with `-` are options nobody knows and are passed over, wherever they stand. */
-typedef struct { const int64_t *rows; rb3h_buf_t out; int err; } get_out_t;
+ * command line go through ONE call of rb3gpu_retrieve.  Arguments that begin with `-` are options nobody knows and are passed over, wherever they stand.
+ * Two options of this command alone: --pieces sends the same rows through rb3gpu_retrieve_pieces (the whole index walked once in pieces: for long strings),
+ * --all takes no rows and prints every string of the index, rows 0 .. acc[1] - 1, through the same call. */
+typedef struct { const int64_t *rows; rb3h_buf_t out; int err; } get_out_t; /* rows == 0: row i is i (--all) */
 
 static int get_sink(void *ud, int64_t i0, int64_t n, const int64_t *end_row, const int64_t *off, const uint8_t *symbols)
 {
@@ -1883,7 +1885,7 @@ static int get_sink(void *ud, int64_t i0, int64_t n, const int64_t *end_row, con
 			o->out.s = t, o->out.m = m;
 		}
 		p = o->out.s + o->out.l;
-		p += sprintf((char*)p, ">%ld %ld\n", (long)o->rows[i0 + i], (long)end_row[i]);
+		p += sprintf((char*)p, ">%ld %ld\n", (long)(o->rows ? o->rows[i0 + i] : i0 + i), (long)end_row[i]);
 		for (k = 0; k < l; ++k) *p++ = (uint8_t)"$ACGTN"[symbols[off[i] + k] < 6 ? symbols[off[i] + k] : 5];
 		*p++ = '\n';
 		o->out.l = p - o->out.s;
@@ -1892,33 +1894,54 @@ static int get_sink(void *ud, int64_t i0, int64_t n, const int64_t *end_row, con
 	return o->err ? -1 : 0;
 }
 
+static const struct option get_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ "all", no_argument, 0, 501 },
+	{ "pieces", no_argument, 0, 502 },
+	{ 0, 0, 0, 0 }
+};
+
 static int main_get(int argc, char *argv[])
 {
-	int c, device = 0, ret = 0, i;
+	int c, device = 0, ret = 0, i, all = 0, pieces = 0;
 	int64_t *rows, n = 0;
 	rb3gpu_t *h;
 	rb3gpu_retrieve_stats_t st;
+	rb3gpu_pieces_stats_t pst;
 	get_out_t o;
 	optind = 1, opterr = 0;
-	while ((c = getopt_long(argc, argv, "", walk_long_opts, 0)) >= 0) {
+	while ((c = getopt_long(argc, argv, "", get_long_opts, 0)) >= 0) {
 		if (c == 301) device = atoi(optarg);
 		else if (c == 308) g_host_fmd = 1;
+		else if (c == 501) all = 1;
+		else if (c == 502) pieces = 1;
 	}
-	if (argc - optind < 2) {
+	if (argc - optind < (all ? 1 : 2)) {
 		fprintf(stdout, "Usage: ropebwt3-amd get <idx.fmr> <int> [...]\n");
 		return 0;
+	}
+	if (all && argc - optind > 1) {
+		fprintf(stderr, "ERROR: get --all prints every sequence of the index and takes no row\n");
+		return 1;
 	}
 	if ((h = open_index(device, argv[optind], 0)) == 0) return 1;
 	rows = (int64_t*)malloc((size_t)(argc - optind) * 8);
 	if (rows == 0) { fprintf(stderr, "ERROR: out of memory\n"); rb3gpu_destroy(h); return 1; }
 	for (i = optind + 1; i < argc; ++i) rows[n++] = atol(argv[i]); /* main.c:155: `abc` is row 0 */
 	memset(&o, 0, sizeof(o));
-	o.rows = rows;
-	c = rb3gpu_retrieve(h, n, rows, get_sink, &o, &st);
+	o.rows = all ? 0 : rows;
+	if (all) c = rb3gpu_retrieve_pieces(h, -1, 0, get_sink, &o, &pst);
+	else if (pieces) c = rb3gpu_retrieve_pieces(h, n, rows, get_sink, &o, &pst);
+	else c = rb3gpu_retrieve(h, n, rows, get_sink, &o, &st);
 	if (c == 0 && !o.err && out_flush(&o.out, 1) < 0) o.err = 1;
 	if (c != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to retrieve the sequences: %s\n", rb3gpu_strerror(c)); ret = 1; }
 	else if (o.err || fflush(stdout) != 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
-	if (rb3h_verbose >= 3 && ret == 0)
+	if (rb3h_verbose >= 3 && ret == 0 && (all || pieces))
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld rows, %lld symbols in %lld slice(s): %lld pieces, the longest of %lld steps, %lld LF steps; %.3f ms in the engine, pieces %.3f ms, join %.3f ms, sort %.3f ms, writing walk %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)pst.n_rows, (long long)pst.n_symbols, (long long)pst.n_slices, (long long)pst.n_pieces, (long long)pst.max_piece_steps, (long long)pst.n_steps,
+				pst.ms_total, pst.ms_pieces, pst.ms_join, pst.ms_sort, pst.ms_emit);
+	else if (rb3h_verbose >= 3 && ret == 0)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld rows, %lld symbols in %lld slice(s): %lld LF steps; %.3f ms in the engine, counting walk %.3f ms, writing walk %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_rows, (long long)st.n_symbols, (long long)st.n_slices, (long long)st.n_steps, st.ms_total, st.ms_count, st.ms_emit);
 	free(o.out.s); free(rows);

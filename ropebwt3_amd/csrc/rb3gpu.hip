@@ -174,6 +174,7 @@ struct Tune {
 	int64_t seed_chunk = 0;  // rb3gpu_seed_present: window starts per walker where the caller names none (0: 2048)
 	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
+	int get_piece = 0;       // rb3gpu_retrieve_pieces: log2 of the splitter spacing of the pieces (0: 8)
 	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
 	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
@@ -695,6 +696,7 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "sw_table")) t.sw_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
 	else if (!strcmp(key, "suffix_slice")) t.suffix_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "get_piece")) t.get_piece = v < 1 ? 0 : v > 20 ? 20 : (int)v;
 	else if (!strcmp(key, "seed_chunk")) t.seed_chunk = v < 0 ? 0 : v;
 	else if (!strcmp(key, "seed_slice")) t.seed_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
@@ -736,7 +738,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "get_piece", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -4519,6 +4521,7 @@ static bool queries_ok(int64_t n_query, const int64_t *offsets, const uint8_t *s
 /* ---- kount: k-mer counting over one or more indexes (rb3gpu_kount.h) ------------------------- */
 
 int rb3kount_scan(void *tmp, size_t *tmp_bytes, const uint32_t *cnt, int64_t *off, int64_t n, hipStream_t st); // rb3gpu_kount.hip
+int rb3kount_sort_pairs(void *tmp, size_t *tmp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, int64_t n, int end_bit, hipStream_t st);
 
 #define RB3_KOUNT_OUT_CHUNK ((int64_t)1 << 20) // output records per callback at most
 #define RB3_KOUNT_SYNC_UB   ((int64_t)1 << 20) // a frontier bounded by this many nodes is expanded without asking the host for its count
@@ -5858,6 +5861,189 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = ms_count, st->ms_emit = ms_emit, st->n_rows = n, st->n_symbols = n_sym, st->n_slices = n_slices;
 		st->n_steps = ws.h_ctr ? (int64_t)ws.h_ctr[1] : 0;
 	}
+	return ret;
+}
+
+/* `get` in pieces (rb3gpu_walk.h): the whole index walked once in pieces of about 2^S steps, all at the same time; the pieces joined by pointer
+ * jumping and sorted by (string, distance from its start) once per call; then every slice of rows written by all of its pieces side by side */
+#define RB3_GET_PIECE 8                       // log2 of the splitter spacing (not measured: DESIGN.md 7k)
+
+struct PieceEv {
+	hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	~PieceEv() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_pieces_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	const bool all = n < 0 && rows == nullptr;
+	if (!h || !cb || (n < 0 && !all) || (n > 0 && !rows)) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1];
+	if (all) n = m;
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	if (st) st->n_rows = n;
+	if (n == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
+	const int S = h->tn.get_piece > 0 ? h->tn.get_piece : RB3_GET_PIECE;
+	const int64_t nsp = m + ((h->n - m + ((int64_t)1 << S) - 1) >> S);
+	if (m >= ((int64_t)1 << 31) || nsp >= ((int64_t)1 << 32)) return RB3GPU_EUNSUP; // (the sort key holds the string in 31 bits, the sorted values are 32-bit piece ids)
+	std::vector<int64_t> vrow, vat; // as in rb3gpu_retrieve: only the rows that exist reach the device
+	for (int64_t i = 0; i < n; ++i) {
+		const int64_t k = all ? i : rows[i];
+		if (k >= 0 && k < h->n) vrow.push_back(k), vat.push_back(i);
+	}
+	const int64_t nv = (int64_t)vrow.size();
+	std::vector<int64_t> len((size_t)n, 0), end((size_t)n, -1), off;
+	const int64_t budget = h->tn.get_slice > 0 ? h->tn.get_slice : RB3_GET_SLICE;
+	WalkWs ws;
+	PieceEv ev;
+	double ms_pieces = 0, ms_join = 0, ms_sort = 0, ms_emit = 0;
+	int64_t n_sym = 0, n_slices = 0, out_cap = 0, n_steps = 0, max_piece = 0;
+	if (nv > 0) {
+		ulonglong2 *d_lnk[2] = { nullptr, nullptr }, *d_rq = nullptr;
+		int64_t *d_rows = nullptr, *d_len = nullptr, *d_end = nullptr, *d_off = nullptr, *d_ioff = nullptr, *d_endrow = nullptr;
+		uint32_t *d_len32 = nullptr, *d_cnt32 = nullptr, *d_first = nullptr, *d_val[2] = { nullptr, nullptr };
+		uint8_t *d_out = nullptr;
+		unsigned long long *d_ctr = nullptr;
+		void *d_tmp = nullptr;
+		size_t scan_bytes = 0, sort_bytes = 0;
+		int kbits = 1;
+		while (((int64_t)1 << kbits) < m) ++kbits;
+		const IdxView ix = view_of(h);
+		auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+		// the tables: two link words twice and two piece ids per piece (the keys of the sort take the place of the link table the join leaves free), 8 bytes per string
+		HIPCHK(dalloc(&d_lnk[0], (size_t)nsp * 16));
+		HIPCHK(dalloc(&d_lnk[1], (size_t)nsp * 16));
+		HIPCHK(dalloc(&d_val[0], (size_t)nsp * 4));
+		HIPCHK(dalloc(&d_val[1], (size_t)nsp * 4));
+		HIPCHK(dalloc(&d_endrow, (size_t)m * 8));
+		HIPCHK(dalloc(&d_rq, (size_t)nv * 16));
+		HIPCHK(dalloc(&d_rows, (size_t)nv * 8));
+		HIPCHK(dalloc(&d_len, (size_t)nv * 8));
+		HIPCHK(dalloc(&d_end, (size_t)nv * 8));
+		HIPCHK(dalloc(&d_len32, (size_t)(nv + 1) * 4));
+		HIPCHK(dalloc(&d_cnt32, (size_t)(nv + 1) * 4));
+		HIPCHK(dalloc(&d_first, (size_t)nv * 4));
+		HIPCHK(dalloc(&d_off, (size_t)(nv + 1) * 8));
+		HIPCHK(dalloc(&d_ioff, (size_t)(nv + 1) * 8));
+		HIPCHK(dalloc(&d_ctr, 64));
+		HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 128, hipHostMallocDefault));
+		for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+		{
+			int r = rb3kount_scan(nullptr, &scan_bytes, nullptr, nullptr, nv + 1, h->st);
+			if (r < 0) return scan_err(r);
+			r = rb3kount_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, nsp, 32 + kbits, h->st);
+			if (r < 0) return scan_err(r);
+			HIPCHK(dalloc(&d_tmp, std::max(scan_bytes, sort_bytes) + 256));
+		}
+		HIPCHK(hipMemcpyAsync(d_rows, vrow.data(), (size_t)nv * 8, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+		HIPCHK(hipMemsetAsync(d_endrow, 0xff, (size_t)m * 8, h->st));
+		HIPCHK(hipMemsetAsync(d_len32, 0, (size_t)(nv + 1) * 4, h->st));
+		HIPCHK(hipMemsetAsync(d_cnt32, 0, (size_t)(nv + 1) * 4, h->st));
+		PieceView pv;
+		pv.S = S, pv.nsp = nsp, pv.lnk = d_lnk[0], pv.rq = d_rq, pv.endrow = d_endrow, pv.rows = d_rows, pv.ioff = d_ioff, pv.off = d_off;
+		pv.first = d_first, pv.len32 = d_len32, pv.sorted = d_val[1];
+		// 1. the pieces, and the rows asked for down to the first splitter
+		HIPCHK(hipEventRecord(ev.e[0], h->st));
+		{
+			const int64_t nb = std::min<int64_t>(((nsp + nv) * 8 + 255) / 256, 4096);
+			hipLaunchKernelGGL(k_piece_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, pv, (int64_t)0, nv, (uint8_t*)nullptr, (int64_t)0, d_ctr);
+		}
+		HIPCHK(hipEventRecord(ev.e[1], h->st));
+		// 2. the join: after it every piece holds (RB3_SSA_END | its string, D)
+		int cur = 0, rounds = 1;
+		while (((int64_t)1 << (rounds - 1)) < nsp) ++rounds; // ceil(log2 nsp) + 1
+		for (int r = 0; r < rounds; ++r, cur ^= 1)
+			hipLaunchKernelGGL(k_ssa_jump, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, (const uint64_t*)d_lnk[cur], (uint64_t*)d_lnk[cur ^ 1]);
+		uint64_t *d_key[2] = { (uint64_t*)d_lnk[cur ^ 1], (uint64_t*)d_lnk[cur ^ 1] + nsp };
+		hipLaunchKernelGGL(k_piece_key, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, m, (const ulonglong2*)d_lnk[cur], d_key[0], d_val[0], d_ctr + 4);
+		HIPCHK(hipEventRecord(ev.e[2], h->st));
+		// 3. the order of the pieces, its inverse, and every row's lengths and range
+		{
+			size_t tb = sort_bytes;
+			const int r = rb3kount_sort_pairs(d_tmp, &tb, d_key[0], d_key[1], d_val[0], d_val[1], nsp, 32 + kbits, h->st);
+			if (r < 0) return scan_err(r);
+		}
+		hipLaunchKernelGGL(k_piece_inverse, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, (const uint32_t*)d_val[1], d_val[0]);
+		hipLaunchKernelGGL(k_piece_resolve, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->st, nv, nsp, m, (const ulonglong2*)d_lnk[cur], (const ulonglong2*)d_rq, (const int64_t*)d_endrow,
+				(const uint64_t*)d_key[1], (const uint32_t*)d_val[0], d_len, d_end, d_len32, d_cnt32, d_first, d_ctr + 4);
+		HIPCHK(hipEventRecord(ev.e[3], h->st));
+		pv.lnk = d_lnk[cur];
+		std::vector<int64_t> vlen((size_t)nv), vend((size_t)nv);
+		std::vector<uint32_t> vcnt((size_t)nv);
+		HIPCHK(hipMemcpyAsync(vlen.data(), d_len, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(vend.data(), d_end, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(vcnt.data(), d_cnt32, (size_t)nv * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 64, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_pieces = ev_ms(ev.e[0], ev.e[1]), ms_join = ev_ms(ev.e[1], ev.e[2]), ms_sort = ev_ms(ev.e[2], ev.e[3]);
+		n_steps = (int64_t)ws.h_ctr[1], max_piece = (int64_t)ws.h_ctr[3];
+		if (ws.h_ctr[2] != 0 || ws.h_ctr[4] != 0) { // a piece that met no splitter, a chain that ends in no string: not an index
+			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] get: %llu pieces too long, %llu broken links\n", ws.h_ctr[2], ws.h_ctr[4]);
+			return RB3GPU_EINTERNAL;
+		}
+		if (ws.h_ctr[5] != 0) return RB3GPU_EUNSUP; // a string of 2^32 symbols or more
+		for (int64_t v = 0; v < nv; ++v) {
+			if (vlen[(size_t)v] < 0 || vlen[(size_t)v] >= h->n || vend[(size_t)v] < 0 || vend[(size_t)v] >= h->n || vcnt[(size_t)v] == 0) return RB3GPU_EINTERNAL;
+			len[(size_t)vat[(size_t)v]] = vlen[(size_t)v], end[(size_t)vat[(size_t)v]] = vend[(size_t)v];
+		}
+		// 4. emit: slices of consecutive rows whose lengths sum to at most the budget, a longer row alone (as rb3gpu_retrieve cuts them)
+		int ret = 0;
+		for (int64_t i0 = 0, v0 = 0; i0 < n && ret == 0; ++n_slices) {
+			int64_t i1 = i0 + 1, tot = len[(size_t)i0];
+			while (i1 < n && tot + len[(size_t)i1] <= budget) tot += len[(size_t)i1++];
+			int64_t v1 = v0, items = 0;
+			while (v1 < nv && vat[(size_t)v1] < i1) items += vcnt[(size_t)v1++];
+			off.assign((size_t)(i1 - i0 + 1), 0);
+			for (int64_t i = i0; i < i1; ++i) off[(size_t)(i - i0 + 1)] = off[(size_t)(i - i0)] + len[(size_t)i];
+			if (tot > 0) {
+				if (tot > out_cap) { // (grows to the largest slice: the budget, or the one row that exceeds it)
+					if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
+					if (d_out) { for (void *&p : ws.dv) if (p == d_out) p = nullptr; HIPCHK(hipFree(d_out)); d_out = nullptr; }
+					out_cap = 0;
+					const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 20));
+					HIPCHK(dalloc(&d_out, (size_t)oc + 64));
+					HIPCHK(hipHostMalloc(&ws.h_out, (size_t)oc + 64, hipHostMallocDefault));
+					out_cap = oc;
+				}
+				size_t tb = scan_bytes + 256;
+				int r = rb3kount_scan(d_tmp, &tb, d_len32 + v0, d_off, v1 - v0 + 1, h->st); // (d_len32[nv] = d_cnt32[nv] = 0: the entry behind the last row)
+				if (r < 0) return scan_err(r);
+				tb = scan_bytes + 256;
+				r = rb3kount_scan(d_tmp, &tb, d_cnt32 + v0, d_ioff, v1 - v0 + 1, h->st);
+				if (r < 0) return scan_err(r);
+				HIPCHK(hipMemsetAsync(d_ctr, 0, 24, h->st));
+				HIPCHK(hipMemcpyAsync(ws.h_ctr + 8, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipMemcpyAsync(ws.h_ctr + 9, d_ioff + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
+				const int64_t nb = std::min<int64_t>((items * 8 + 255) / 256, 4096);
+				HIPCHK(hipEventRecord(ev.e[4], h->st));
+				hipLaunchKernelGGL(k_piece_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, pv, v0, v1 - v0, d_out, tot, d_ctr);
+				HIPCHK(hipEventRecord(ev.e[5], h->st));
+				HIPCHK(hipMemcpyAsync(ws.h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipStreamSynchronize(h->st));
+				HIPCHK(hipGetLastError());
+				ms_emit += ev_ms(ev.e[4], ev.e[5]);
+				n_steps += (int64_t)ws.h_ctr[1];
+				if ((int64_t)ws.h_ctr[8] != tot || (int64_t)ws.h_ctr[9] != items || ws.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // the scans on the device and the sums on the host are of the same numbers
+			}
+			n_sym += tot;
+			ret = cb(ud, i0, i1 - i0, end.data() + i0, off.data(), (const uint8_t*)ws.h_out);
+			i0 = i1, v0 = v1;
+		}
+		if (st) {
+			st->ms_total = (now_s() - t0) * 1e3, st->ms_pieces = ms_pieces, st->ms_join = ms_join, st->ms_sort = ms_sort, st->ms_emit = ms_emit;
+			st->n_symbols = n_sym, st->n_slices = n_slices, st->n_pieces = nsp, st->n_steps = n_steps, st->max_piece_steps = max_piece;
+		}
+		return ret;
+	}
+	// no row asked for exists: nothing is walked, and all the rows are one slice of empty answers, as in rb3gpu_retrieve
+	off.assign((size_t)(n + 1), 0);
+	const int ret = cb(ud, 0, n, end.data(), off.data(), (const uint8_t*)nullptr);
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->n_slices = 1;
 	return ret;
 }
 

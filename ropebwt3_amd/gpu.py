@@ -153,6 +153,14 @@ class RetrieveStats(ctypes.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+class PiecesStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_pieces", ctypes.c_double), ("ms_join", ctypes.c_double), ("ms_sort", ctypes.c_double), ("ms_emit", ctypes.c_double),
+                ("n_rows", ctypes.c_int64), ("n_symbols", ctypes.c_int64), ("n_slices", ctypes.c_int64), ("n_pieces", ctypes.c_int64), ("n_steps", ctypes.c_int64),
+                ("max_piece_steps", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
     "rb3gpu_opt_init": (None, [ctypes.POINTER(Opt)]),
@@ -278,6 +286,7 @@ SYMBOLS = {
     "rb3gpu_suffix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(SuffixStats)]),
     "rb3gpu_seed_present": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(SeedStats)]),
     "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
+    "rb3gpu_retrieve_pieces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(PiecesStats)]),
 }
 
 # rb3gpu_comm_t (include/rb3gpu.h): the two collectives of the interval-sharded merge
@@ -946,12 +955,20 @@ class Rb3Gpu:
             stats.update(st.as_dict())
         return flag != 0
 
-    def retrieve(self, rows, stats=None):
+    def retrieve(self, rows, stats=None, pieces=False):
         """rb3gpu_retrieve: for every row asked for, in the order asked, the string in front of the suffix of that row (for a sentinel's row k < acc[1]
         the whole of indexed string k) as the reference's `get` spells it: (end_rows, seqs) -- end_rows an int64 array, the row each walk met the
         sentinel at (-1 for a row outside the index), seqs a list of uint8 arrays of nt6 codes in text order (empty for such a row).  stats: a dict
-        that receives rb3gpu_retrieve_stats_t"""
+        that receives rb3gpu_retrieve_stats_t.  pieces=True: the same answers through rb3gpu_retrieve_pieces (the whole index walked once in pieces,
+        for long strings or much of the index; stats then receives rb3gpu_pieces_stats_t)"""
         rows = np.ascontiguousarray(list(rows) if not isinstance(rows, np.ndarray) else rows, dtype=np.int64).reshape(-1)
+        return self._retrieve(rows.size, rows.ctypes.data if rows.size else None, stats, pieces)
+
+    def retrieve_all(self, stats=None):
+        """rb3gpu_retrieve_pieces for all the strings of the index: what retrieve(range(acc[1]), pieces=True) returns, without the list of rows"""
+        return self._retrieve(-1, None, stats, True)
+
+    def _retrieve(self, n, rows_ptr, stats, pieces):
         ends, seqs = [], []
 
         def cb(_ud, _i0, n, end_row, off, symbols):
@@ -960,8 +977,12 @@ class Rb3Gpu:
             buf = np.frombuffer(ctypes.string_at(symbols, int(o[n])), dtype=np.uint8) if o[n] > 0 else np.zeros(0, dtype=np.uint8)
             seqs.extend(buf[int(o[i]):int(o[i + 1])].copy() for i in range(n))
             return 0
-        st = RetrieveStats()
-        self._chk(self._lib.rb3gpu_retrieve(self._h, rows.size, rows.ctypes.data if rows.size else None, RETRIEVE_F(cb), None, ctypes.byref(st)), "rb3gpu_retrieve")
+        if pieces:
+            st = PiecesStats()
+            self._chk(self._lib.rb3gpu_retrieve_pieces(self._h, n, rows_ptr, RETRIEVE_F(cb), None, ctypes.byref(st)), "rb3gpu_retrieve_pieces")
+        else:
+            st = RetrieveStats()
+            self._chk(self._lib.rb3gpu_retrieve(self._h, n, rows_ptr, RETRIEVE_F(cb), None, ctypes.byref(st)), "rb3gpu_retrieve")
         if stats is not None:
             stats.update(st.as_dict())
         return (np.concatenate(ends) if ends else np.zeros(0, dtype=np.int64)), seqs
