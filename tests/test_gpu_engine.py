@@ -394,8 +394,10 @@ def test_soak_with_every_buffer_a_growable_range():
 @pytest.mark.parametrize("seed,kind", [(81, "genomes"), (82, "reads"), (83, "copies"), (84, "tiny"), (85, "runs"), (86, "family")])
 def test_bwt_from_text_vs_host_sorter(oracle, seed, kind):
     """partial BWT of a batch on the GPU (rb3gpu_bwt_from_text, prefix doubling) against the host suffix sorter
-    (itself pinned to the reference's libsais output): BWT bytes and the sampled inverse suffix array"""
+    (itself pinned to the reference's libsais output): BWT bytes and the sampled inverse suffix array, every entry of which and the
+    number of doubling rounds are the sorter's restatement's (tests/sort_model.py)"""
     from ropebwt3_amd import Rb3Gpu, host
+    from tests import sort_model
     rng = np.random.default_rng(seed)
     if kind == "genomes":
         g0 = util.random_genome(rng, 150000)
@@ -416,8 +418,10 @@ def test_bwt_from_text_vs_host_sorter(oracle, seed, kind):
     for both in (True, False):
         text = util.make_text(seqs, True, both)
         want = host.build_bwt(text.copy())
+        model = sort_model.sort(text)
         h = Rb3Gpu(verbose=1)
         try:
+            rounds0 = h.stats()["n_sort_rounds"]
             for step in (0, 100):
                 p, ck = h.bwt_from_text(text, step)
                 got = h.dev_download(p, text.size)
@@ -428,7 +432,8 @@ def test_bwt_from_text_vs_host_sorter(oracle, seed, kind):
                     inner = w[w[:, 1] == -1]                # walkers strictly inside strings: their rows are ISA samples
                     assert set(inner[:, 0].tolist()) <= set(ck.tolist())
                     assert len(set(ck.tolist())) == ck.size and ck.min() >= 0 and ck.max() < text.size
-            assert h.stats()["n_sort_rounds"] >= 0
+                    assert np.array_equal(ck, model.ckrow(step)), (kind, both)
+            assert h.stats()["n_sort_rounds"] - rounds0 == 2 * model.rounds, (kind, both)
         finally:
             h.close()
 
