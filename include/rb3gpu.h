@@ -663,6 +663,21 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 typedef struct { double ms_total, ms_pieces, ms_join, ms_sort, ms_emit; int64_t n_rows, n_symbols, n_slices, n_pieces, n_steps, max_piece_steps; } rb3gpu_pieces_stats_t;
 int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_pieces_stats_t *st);
 
+/* strings taken OUT of the index the handle holds (no counterpart in the reference): the inverse of a merge.  rows[i] are string numbers in
+ * [0, acc[1]) -- there is none of rb3gpu_retrieve's "row inside a string" --, duplicates collapse.  String r occupies the rows the LF walk from row r stands
+ * on, the row whose symbol is the sentinel included; those rows are marked in a bitmap of one bit per row, counted, and the chunked builder of
+ * rb3gpu_from_fmd_words ("load_chunk") is fed with the rows that stay.  pieces == 0: one octet of lanes walks one string (a dependent chain of len + 1 LF
+ * steps); pieces != 0: the whole index is walked once in pieces as in rb3gpu_retrieve_pieces ("get_piece") and the pieces of the strings asked for mark their
+ * rows side by side -- for long strings.  The order of the strings that stay (rb3gpu_get_order) is what it was.  Before anything is replaced the marked rows are
+ * checked: as many as the strings' len + 1 sum to, one sentinel per string.  On success the handle holds the new index (acc included; a sampled suffix array
+ * kept on the handle is dropped); on ANY failure it still holds the old one.  RB3GPU_EINVAL for a row outside [0, acc[1]) and for a request that would leave no
+ * string (n == 0 succeeds and changes nothing); RB3GPU_ESTATE without an index; RB3GPU_EUNSUP with pieces for acc[1] >= 2^31, 2^32 pieces or more, or a string of
+ * 2^32 symbols or more; RB3GPU_EINTERNAL if the check fails.  Device memory beside the two indexes: the bitmap (acc[6] / 8 bytes), 12 bytes per 8192 rows, the
+ * builder's chunk, and with pieces 32 bytes per piece and 9 per string.  st (may be NULL): ms_total wall time, ms_mark the walks and ms_build the rebuild (HIP
+ * events), n_strings distinct strings, n_rows rows deleted, n_steps LF steps, n_pieces and max_piece_steps (pieces only), removed[c] deleted symbols per letter */
+typedef struct { double ms_total, ms_mark, ms_build; int64_t n_strings, n_rows, n_steps, n_pieces, max_piece_steps, removed[6]; } rb3gpu_remove_stats_t;
+int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gpu_remove_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);

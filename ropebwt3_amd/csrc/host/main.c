@@ -1949,6 +1949,122 @@ static int main_get(int argc, char *argv[])
 	return ret;
 }
 
+/* remove [-d|-b|-e] [-o FILE] [--pieces] [--pair] [-f FILE] <idx> [<int>|<int>-<int> ...] (no counterpart in the reference): the index without the
+ * sequences named, through ONE call of rb3gpu_remove, written like the output of `merge` (FMR unless -d or -e).  An argument is a string number (a row below acc[1])
+ * or an inclusive range; -f adds one per line; --pair reads every number i as sequence i of an index of both strands, rows 2i and 2i + 1 (input order only: in a sorted order the strands of a
+ * sequence stand where their order puts them, and --pair is refused).  Nothing is guessed: an
+ * argument that is no number or range, a row outside the index, no row at all and a request that leaves no sequence are one line on stderr each, exit 1, nothing
+ * written.  The index's .ssa and .len.gz do not fit the output and are not rewritten. */
+typedef struct { int64_t *a; int64_t n, m; } rowvec_t;
+
+static int rowvec_add(rowvec_t *v, const char *arg, int pair, int64_t n_str)
+{
+	int64_t a, b, i;
+	if (rb3h_parse_rows(arg, &a, &b) < 0) { fprintf(stderr, "ERROR: remove: '%s' is neither a row number nor a range A-B\n", arg); return -1; }
+	if (pair) { /* sequence i: rows 2i and 2i + 1 */
+		if (b >= n_str / 2) { fprintf(stderr, "ERROR: remove: sequence %ld is outside the index (%ld sequences)\n", (long)b, (long)(n_str / 2)); return -1; }
+		a *= 2, b = 2 * b + 1;
+	} else if (b >= n_str) { fprintf(stderr, "ERROR: remove: row %ld is outside the index (%ld strings)\n", (long)b, (long)n_str); return -1; }
+	if (v->n + (b - a + 1) > v->m) {
+		int64_t *t;
+		v->m = (v->n + (b - a + 1)) * 2;
+		if ((t = (int64_t*)realloc(v->a, (size_t)v->m * 8)) == 0) { fprintf(stderr, "ERROR: out of memory\n"); return -1; }
+		v->a = t;
+	}
+	for (i = a; i <= b; ++i) v->a[v->n++] = i;
+	return 0;
+}
+
+static const struct option remove_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ "bre-run-bytes", required_argument, 0, 311 },
+	{ "pieces", no_argument, 0, 502 },
+	{ "pair", no_argument, 0, 503 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_remove(int argc, char *argv[])
+{
+	int c, i, ret = 0, fmt = FMT_FMR, device = 0, pieces = 0, pair = 0;
+	const char *fn_out = 0, *fn_rows = 0;
+	int64_t acc[7];
+	rowvec_t rv = { 0, 0, 0 };
+	rb3gpu_remove_stats_t st;
+	rb3gpu_t *h;
+	bopt_t opt;
+	bopt_init(&opt);
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "dbeo:f:", remove_long_opts, 0)) >= 0) {
+		if (c == 'd') fmt = FMT_FMD;
+		else if (c == 'b') fmt = FMT_FMR;
+		else if (c == 'e') fmt = FMT_BRE;
+		else if (c == 'o') fn_out = optarg;
+		else if (c == 'f') fn_rows = optarg;
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+		else if (c == 311) g_bre_run_bytes = atoi(optarg);
+		else if (c == 502) pieces = 1;
+		else if (c == 503) pair = 1;
+		else if (c == '?') return 1;
+	}
+	if (argc - optind < 1) {
+		fprintf(stderr, "Usage: ropebwt3-amd remove [options] <idx.fmd|fmr|bre> [<int>|<int>-<int> ...]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -b / -d / -e   output FMR (default, as merge) / FMD / BRE\n");
+		fprintf(stderr, "  --bre-run-bytes INT  bytes of a run length in a BRE record, 1..4 [2]\n");
+		fprintf(stderr, "  -o FILE        output to FILE [stdout]\n");
+		fprintf(stderr, "  -f FILE        read further rows or ranges from FILE, one per line\n");
+		fprintf(stderr, "  --pair         a number i is sequence i of an index of both strands in input order: rows 2i and 2i+1\n");
+		fprintf(stderr, "  --pieces       mark the rows through the walk in pieces (long sequences)\n");
+		fprintf(stderr, "  --gpu INT      HIP device ordinal [0]\n");
+		return 1;
+	}
+	if (fmt == FMT_BRE && (g_bre_run_bytes < 1 || g_bre_run_bytes > 4)) { fprintf(stderr, "ERROR: --bre-run-bytes takes 1 to 4\n"); return 1; }
+	opt.so = index_order(argv[optind]); /* (an FMR output carries the order of its input) */
+	c = rb3h_verbose;
+	if (rb3h_verbose > 2) rb3h_verbose = 2; /* (the command may still refuse its rows with ONE line: the loading says nothing but errors and warnings until they are accepted) */
+	h = open_index(device, argv[optind], 0);
+	rb3h_verbose = c;
+	if (h == 0) return 1;
+	rb3gpu_tune(h, "verbose", rb3h_verbose);
+	rb3gpu_get_acc(h, acc);
+	if (pair && opt.so != RB3GPU_SO_IO) { fprintf(stderr, "ERROR: remove: --pair numbers the sequences in input order; the strings of this index are sorted (build -s / -r): name the rows\n"); ret = 1; }
+	else if (pair && !both_strands(acc)) ret = 1;
+	for (i = optind + 1; i < argc && ret == 0; ++i)
+		if (rowvec_add(&rv, argv[i], pair, acc[1]) < 0) ret = 1;
+	if (fn_rows && ret == 0) {
+		FILE *fp = strcmp(fn_rows, "-") == 0 ? stdin : fopen(fn_rows, "r");
+		char line[256];
+		if (fp == 0) { fprintf(stderr, "ERROR: remove: failed to open '%s'\n", fn_rows); ret = 1; }
+		while (ret == 0 && fgets(line, sizeof(line), fp)) {
+			size_t l = strlen(line);
+			while (l > 0 && (line[l - 1] == '\n' || line[l - 1] == '\r')) line[--l] = 0;
+			if (l == 0) continue;
+			if (rowvec_add(&rv, line, pair, acc[1]) < 0) ret = 1;
+		}
+		if (fp && fp != stdin) fclose(fp);
+	}
+	if (ret == 0 && rv.n == 0) { fprintf(stderr, "ERROR: remove: no row to remove\n"); ret = 1; }
+	if (ret == 0) {
+		c = rb3gpu_remove(h, rv.n, rv.a, pieces, &st);
+		if (c == RB3GPU_EINVAL) { fprintf(stderr, "ERROR: remove: nothing would be left of the index\n"); ret = 1; } /* (rows outside the index never get here) */
+		else if (c != 0) { fprintf(stderr, "ERROR: the GPU engine failed to remove the sequences: %s\n", rb3gpu_strerror(c)); ret = 1; }
+	}
+	if (ret == 0 && rb3h_verbose >= 3)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] removed %lld strings, %lld rows ($ACGTN: %lld %lld %lld %lld %lld %lld): %lld LF steps, %lld pieces, the longest of %lld steps; %.3f ms in the engine, marking %.3f ms, rebuild %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_strings, (long long)st.n_rows, (long long)st.removed[0], (long long)st.removed[1], (long long)st.removed[2], (long long)st.removed[3],
+				(long long)st.removed[4], (long long)st.removed[5], (long long)st.n_steps, (long long)st.n_pieces, (long long)st.max_piece_steps, st.ms_total, st.ms_mark, st.ms_build);
+	if (ret == 0 && fn_out && freopen(fn_out, "wb", stdout) == 0) { fprintf(stderr, "ERROR: remove: failed to open '%s' for writing\n", fn_out); ret = 1; }
+	if (ret == 0) {
+		c = fmt == FMT_FMR ? dump_fmr(h, &opt, stdout) : fmt == FMT_FMD ? write_fmd(h, stdout) : write_bre(h, stdout);
+		if (c != 0 || fflush(stdout) != 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	}
+	free(rv.a);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* hapdiv: the windows of every query (k symbols every w, search.c:384-393) through rb3gpu_hapdiv, batch by batch; the lines of write_hapdiv */
 typedef struct { int32_t *r; int64_t n; } hapdiv_out_t;
 
@@ -2553,6 +2669,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    mem        find super-maximal exact matches of queries (on an MI355X)\n");
 	fprintf(fp, "    suffix     find the longest matching suffix of queries (on an MI355X)\n");
 	fprintf(fp, "    get        retrieve the i-th sequence from a BWT (on an MI355X)\n");
+	fprintf(fp, "    remove     take sequences out of a BWT (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
@@ -2574,6 +2691,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "mem") == 0) ret = main_mem(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "suffix") == 0) ret = main_suffix(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "get") == 0) ret = main_get(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "remove") == 0) ret = main_remove(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);

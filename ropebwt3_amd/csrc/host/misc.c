@@ -18,6 +18,28 @@ int64_t rb3h_parse_num(const char *str) /* "7g", "500k", "2.5M" */
 	return (int64_t)(x + .499);
 }
 
+/* an argument of `remove`: a number `A` or an inclusive range `A-B` (A <= B), decimal digits only, each below 2^62; nothing in front, between or behind
+ * (so no sign, no blank, no empty side).  0 and (*a, *b), or -1: nothing is guessed */
+int rb3h_parse_rows(const char *str, int64_t *a, int64_t *b)
+{
+	int64_t v[2] = { 0, 0 };
+	int i = 0, nd = 0;
+	const char *p;
+	if (str == 0) return -1;
+	for (p = str; *p; ++p) {
+		if (*p >= '0' && *p <= '9') {
+			if (v[i] > ((int64_t)1 << 58)) return -1;
+			v[i] = v[i] * 10 + (*p - '0'), ++nd;
+		} else if (*p == '-' && i == 0 && nd > 0) i = 1, nd = 0;
+		else return -1;
+	}
+	if (nd == 0) return -1;
+	if (i == 0) v[1] = v[0];
+	if (v[1] < v[0]) return -1;
+	*a = v[0], *b = v[1];
+	return 0;
+}
+
 double rb3h_cputime(void)
 {
 	struct rusage r;

@@ -19,6 +19,7 @@ extern int rb3h_verbose;
 
 /* ---- misc (misc.c:7-16, 116-150) ---- */
 int64_t rb3h_parse_num(const char *str);
+int rb3h_parse_rows(const char *str, int64_t *a, int64_t *b);              /* `7` or `3-9` of `remove`: 0, or -1 for anything else */
 double rb3h_realtime(void);
 double rb3h_cputime(void);
 double rb3h_percent_cpu(void);

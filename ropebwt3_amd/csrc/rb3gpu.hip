@@ -27,6 +27,7 @@
 #include "rb3gpu_kount.h"
 #include "rb3gpu_mem.h"
 #include "rb3gpu_walk.h"
+#include "rb3gpu_remove.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
 #include "rb3gpu_swlocal.h"
@@ -6045,6 +6046,176 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 	const int ret = cb(ud, 0, n, end.data(), off.data(), (const uint8_t*)nullptr);
 	if (st) st->ms_total = (now_s() - t0) * 1e3, st->n_slices = 1;
 	return ret;
+}
+
+/* ---- remove: strings taken out of the index (rb3gpu_remove.h) ------------------------------------ */
+
+/* "the old index without the marked rows" as a source of from_fmd_chunked.  The view is of the index as it stood BEFORE the builder ran: the builder clears
+ * the handle's pointers after its first pass (index_drop) but the buffer they pointed to stays allocated while the other one is written. */
+struct RemoveSrc {
+	IdxView ix;
+	const uint32_t *bm;
+	const int64_t *d_pre;            // marked rows in front of every group, on the device ...
+	const int64_t *pre;              // ... and on the host: ngo + 1 entries
+	int64_t ngo;
+	hipStream_t st;
+};
+
+static int remove_range(void *ctx, int64_t p0, int64_t p1, uint8_t *d_out)
+{
+	const RemoveSrc *s = (const RemoveSrc*)ctx;
+	if (p1 <= p0) return 0;
+	auto kept = [&](int64_t g) { return std::min(g << RB3_GRP_BITS, s->ix.n) - s->pre[g]; }; // rows kept in front of group g (g = ngo: all that are kept)
+	if (p0 < 0 || p1 > kept(s->ngo)) return -1;
+	int64_t lo = 0, hi = s->ngo; // ga: the last group with at most p0 rows kept in front of it
+	while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (kept(mid) <= p0) lo = mid; else hi = mid; }
+	const int64_t ga = lo;
+	lo = ga + 1, hi = s->ngo;    // gb: the first group behind ga with at least p1 rows kept in front of it
+	while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (kept(mid) >= p1) hi = mid; else lo = mid + 1; }
+	const int64_t gb = lo;
+	hipLaunchKernelGGL(k_rm_compact, dim3((unsigned)(gb - ga)), dim3(256), 0, s->st, s->ix, s->bm, s->d_pre, ga, p0, p1, d_out);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gpu_remove_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || n < 0 || (n > 0 && !rows)) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1], n_old = h->n;
+	for (int64_t i = 0; i < n; ++i)
+		if (rows[i] < 0 || rows[i] >= m) return RB3GPU_EINVAL;
+	if (n == 0) return 0;
+	std::vector<int64_t> vr(rows, rows + n);
+	std::sort(vr.begin(), vr.end());
+	vr.erase(std::unique(vr.begin(), vr.end()), vr.end());
+	const int64_t nd = (int64_t)vr.size();
+	if (nd >= m) return RB3GPU_EINVAL; // nothing would be left
+	const int S = h->tn.get_piece > 0 ? h->tn.get_piece : RB3_GET_PIECE;
+	const int64_t nsp = m + ((n_old - m + ((int64_t)1 << S) - 1) >> S);
+	if (pieces && (m >= ((int64_t)1 << 31) || nsp >= ((int64_t)1 << 32))) return RB3GPU_EUNSUP; // (the limits of rb3gpu_retrieve_pieces)
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	const int64_t ngo = (n_old + RB3_GRP - 1) >> RB3_GRP_BITS; // groups of the bitmap: all of them whole
+	const IdxView ix = view_of(h);
+	WalkWs ws;
+	PieceEv ev;
+	uint32_t *d_bm = nullptr, *d_cnt = nullptr;
+	int64_t *d_pre = nullptr, *d_rows = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	void *d_tmp = nullptr;
+	size_t scan_bytes = 0;
+	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+	HIPCHK(dalloc(&d_bm, (size_t)ngo * RB3_RM_WORDS * 4));
+	HIPCHK(dalloc(&d_cnt, (size_t)(ngo + 1) * 4));
+	HIPCHK(dalloc(&d_pre, (size_t)(ngo + 1) * 8));
+	HIPCHK(dalloc(&d_rows, (size_t)nd * 8));
+	HIPCHK(dalloc(&d_ctr, 256)); // [0, 8): the pieces' walk, [8, 16): the marking walk, [16, 24): the flags, [24, 32): the letters
+	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 256, hipHostMallocDefault));
+	for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+	{
+		const int r = rb3kount_scan(nullptr, &scan_bytes, nullptr, nullptr, ngo + 1, h->st);
+		if (r < 0) return scan_err(r);
+		HIPCHK(dalloc(&d_tmp, scan_bytes + 256));
+	}
+	HIPCHK(hipMemsetAsync(d_bm, 0, (size_t)ngo * RB3_RM_WORDS * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(ngo + 1) * 4, h->st)); // (entry ngo stays 0: the scan's entry behind the last group is the total)
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 256, h->st));
+	HIPCHK(hipMemcpyAsync(d_rows, vr.data(), (size_t)nd * 8, hipMemcpyHostToDevice, h->st));
+	// 1. mark
+	HIPCHK(hipEventRecord(ev.e[0], h->st));
+	if (!pieces) {
+		const int64_t nb = std::min<int64_t>((nd * 8 + 255) / 256, 4096);
+		hipLaunchKernelGGL(k_mark_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, nd, d_bm, d_ctr + 8);
+	} else {
+		ulonglong2 *d_lnk[2] = { nullptr, nullptr };
+		int64_t *d_endrow = nullptr;
+		uint8_t *d_flag = nullptr;
+		HIPCHK(dalloc(&d_lnk[0], (size_t)nsp * 16));
+		HIPCHK(dalloc(&d_lnk[1], (size_t)nsp * 16));
+		HIPCHK(dalloc(&d_endrow, (size_t)m * 8));
+		HIPCHK(dalloc(&d_flag, (size_t)m));
+		HIPCHK(hipMemsetAsync(d_flag, 0, (size_t)m, h->st));
+		PieceView pv;
+		memset(&pv, 0, sizeof(pv));
+		pv.S = S, pv.nsp = nsp, pv.lnk = d_lnk[0], pv.endrow = d_endrow;
+		const int64_t nb = std::min<int64_t>((nsp * 8 + 255) / 256, 4096);
+		hipLaunchKernelGGL(k_piece_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, pv, (int64_t)0, (int64_t)0, (uint8_t*)nullptr, (int64_t)0, d_ctr); // (no rows: a string's row is a splitter's)
+		HIPCHK(hipEventRecord(ev.e[2], h->st));
+		int cur = 0, rounds = 1;
+		while (((int64_t)1 << (rounds - 1)) < nsp) ++rounds; // ceil(log2 nsp) + 1
+		for (int r = 0; r < rounds; ++r, cur ^= 1)
+			hipLaunchKernelGGL(k_ssa_jump, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, (const uint64_t*)d_lnk[cur], (uint64_t*)d_lnk[cur ^ 1]);
+		hipLaunchKernelGGL(k_mark_flag, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->st, nd, (const int64_t*)d_rows, m, (const ulonglong2*)d_lnk[cur], d_flag, d_ctr + 16);
+		HIPCHK(hipEventRecord(ev.e[3], h->st));
+		hipLaunchKernelGGL(k_mark_pieces, dim3((unsigned)nb), dim3(256), 0, h->st, ix, S, nsp, (const ulonglong2*)d_lnk[cur], (const uint8_t*)d_flag, d_bm, d_ctr + 8);
+	}
+	HIPCHK(hipEventRecord(ev.e[1], h->st));
+	// 2. the rank of the compaction, and the check: nothing has been destroyed so far
+	hipLaunchKernelGGL(k_mark_count, dim3((unsigned)ngo), dim3(256), 0, h->st, ix, (const uint32_t*)d_bm, d_cnt, d_ctr + 24);
+	{
+		size_t tb = scan_bytes + 256;
+		const int r = rb3kount_scan(d_tmp, &tb, d_cnt, d_pre, ngo + 1, h->st);
+		if (r < 0) return scan_err(r);
+	}
+	std::vector<int64_t> pre((size_t)ngo + 1);
+	HIPCHK(hipMemcpyAsync(pre.data(), d_pre, (size_t)(ngo + 1) * 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 256, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipGetLastError());
+	const unsigned long long *cp = ws.h_ctr, *cm = ws.h_ctr + 8, *cf = ws.h_ctr + 16, *cl = ws.h_ctr + 24;
+	const double ms_mark = ev_ms(ev.e[0], ev.e[1]);
+	if (h->opt.verbose >= 3) {
+		if (pieces)
+			fprintf(stderr, "[M::%s::%.3f] marked %lld rows of %lld strings in pieces: counting walk %.3f ms (%llu steps), join %.3f ms, marking walk %.3f ms (%llu steps)\n", __func__, now_s() - h->t0, (long long)pre[(size_t)ngo],
+					(long long)nd, ev_ms(ev.e[0], ev.e[2]), cp[1], ev_ms(ev.e[2], ev.e[3]), ev_ms(ev.e[3], ev.e[1]), cm[1]);
+		else fprintf(stderr, "[M::%s::%.3f] marked %lld rows of %lld strings: marking walk %.3f ms (%llu steps)\n", __func__, now_s() - h->t0, (long long)pre[(size_t)ngo], (long long)nd, ms_mark, cm[1]);
+	}
+	if (pieces && cf[1] != 0) return RB3GPU_EUNSUP; // a string of 2^32 symbols or more
+	const int64_t n_rows = pre[(size_t)ngo], expect = pieces ? (int64_t)cf[2] : (int64_t)cm[1];
+	int64_t n_let = 0;
+	for (int a = 0; a < 6; ++a) n_let += (int64_t)cl[a];
+	if (cp[2] != 0 || cm[2] != 0 || cf[0] != 0 || cl[6] != 0 || (int64_t)cm[1] != n_rows || n_rows != expect || n_let != n_rows || (int64_t)cl[0] != nd || n_rows >= n_old) {
+		if (h->opt.verbose >= 1)
+			fprintf(stderr, "[E::rb3gpu] remove: %lld rows marked by %llu steps for %lld strings of %lld rows, %llu sentinels among them; %llu walks did not end, %llu links broken\n", (long long)n_rows, cm[1], (long long)nd,
+					(long long)expect, cl[0], cp[2] + cm[2], cf[0]);
+		return RB3GPU_EINTERNAL;
+	}
+	// 3. rebuild: the chunked builder fed with the rows that stay
+	int64_t mcnt[RB3GPU_ASIZE];
+	for (int a = 0; a < RB3GPU_ASIZE; ++a) mcnt[a] = h->acc[a + 1] - h->acc[a] - (int64_t)cl[a];
+	const int64_t n_new = n_old - n_rows;
+	RemoveSrc rs = { ix, d_bm, d_pre, pre.data(), ngo, h->st };
+	const RangeSrc src = { remove_range, &rs, (int64_t)((size_t)ngo * (RB3_RM_WORDS * 4 + 12)), "remove" };
+	// what index_drop clears, kept: a failure behind it puts the old index back; its sampled suffix array goes only with it
+	rb3_grp_t *const o_grp = h->grp;
+	rb3_slot_t *const o_slots = h->slots;
+	const int64_t o_ngrp = h->ngrp, o_nslots = h->nslots, o_bytes = h->stt.bytes_index, o_ssa_m = h->ssa_m, o_ssa_n = h->ssa_n, o_chunk = h->tn.load_chunk;
+	const int o_ssa_ss = h->ssa_ss, o_ssa_ms = h->ssa_ms;
+	uint64_t *const o_ssa = h->ssa_dev;
+	int64_t o_acc[7];
+	memcpy(o_acc, h->acc, sizeof(o_acc));
+	h->ssa_dev = nullptr, h->ssa_m = h->ssa_n = 0, h->ssa_ss = h->ssa_ms = 0;
+	if (h->tn.load_chunk > (n_new >> RB3_GRP_BITS) + 1) h->tn.load_chunk = (n_new >> RB3_GRP_BITS) + 1; // (the builder's scratch is sized by the chunk, not by the index)
+	const double ms_build0 = h->stt.ms_build;
+	const int r = from_fmd_chunked(h, src, n_new, mcnt);
+	h->tn.load_chunk = o_chunk;
+	if (r < 0) {
+		(void)hipStreamSynchronize(h->st);
+		(void)hipGetLastError();
+		ssa_drop(h);
+		h->grp = o_grp, h->slots = o_slots, h->ngrp = o_ngrp, h->nslots = o_nslots, h->n = n_old, h->stt.bytes_index = o_bytes;
+		memcpy(h->acc, o_acc, sizeof(o_acc));
+		h->ssa_dev = o_ssa, h->ssa_m = o_ssa_m, h->ssa_n = o_ssa_n, h->ssa_ss = o_ssa_ss, h->ssa_ms = o_ssa_ms;
+		return r == RB3GPU_ESYMBOL ? RB3GPU_EINTERNAL : r; // (the builder counted other symbols than the check above)
+	}
+	if (o_ssa) dev_free(h, o_ssa, (size_t)(o_ssa_m + o_ssa_n) * 8);
+	if (st) {
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_mark = ms_mark, st->ms_build = h->stt.ms_build - ms_build0;
+		st->n_strings = nd, st->n_rows = n_rows, st->n_steps = (int64_t)(cp[1] + cm[1]), st->n_pieces = pieces ? nsp : 0, st->max_piece_steps = (int64_t)cp[3];
+		for (int a = 0; a < 6; ++a) st->removed[a] = (int64_t)cl[a];
+	}
+	return 0;
 }
 
 } // extern "C"

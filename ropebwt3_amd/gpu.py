@@ -161,6 +161,14 @@ class PiecesStats(ctypes.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+
+class RemoveStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_mark", ctypes.c_double), ("ms_build", ctypes.c_double), ("n_strings", ctypes.c_int64), ("n_rows", ctypes.c_int64),
+                ("n_steps", ctypes.c_int64), ("n_pieces", ctypes.c_int64), ("max_piece_steps", ctypes.c_int64), ("removed", ctypes.c_int64 * 6)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "removed" else getattr(self, k)) for k, _ in self._fields_}
+
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
     "rb3gpu_opt_init": (None, [ctypes.POINTER(Opt)]),
@@ -287,6 +295,7 @@ SYMBOLS = {
     "rb3gpu_seed_present": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(SeedStats)]),
     "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
     "rb3gpu_retrieve_pieces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(PiecesStats)]),
+    "rb3gpu_remove": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RemoveStats)]),
 }
 
 # rb3gpu_comm_t (include/rb3gpu.h): the two collectives of the interval-sharded merge
@@ -986,6 +995,16 @@ class Rb3Gpu:
         if stats is not None:
             stats.update(st.as_dict())
         return (np.concatenate(ends) if ends else np.zeros(0, dtype=np.int64)), seqs
+
+    def remove(self, rows, pieces=False, stats=None):
+        """rb3gpu_remove: the strings rows (numbers in [0, acc[1]); duplicates collapse) taken out of the index on the handle; the strings that stay keep their
+        order.  pieces=True marks the rows through the walk in pieces (for long strings).  An empty list changes nothing; a row outside the range, or a request
+        that would leave no string, raises with RB3GPU_EINVAL and the index as it was.  stats: a dict that receives rb3gpu_remove_stats_t"""
+        rows = np.ascontiguousarray(list(rows) if not isinstance(rows, np.ndarray) else rows, dtype=np.int64).reshape(-1)
+        st = RemoveStats()
+        self._chk(self._lib.rb3gpu_remove(self._h, rows.size, rows.ctypes.data if rows.size else None, 1 if pieces else 0, ctypes.byref(st)), "rb3gpu_remove")
+        if stats is not None:
+            stats.update(st.as_dict())
 
     def hapdiv(self, queries, k=101, w=50, n_best=25, min_sc=30, match=1, mis=3, gap_open=5, gap_ext=2, e2e_drop=-1, stats=None):
         """rb3gpu_hapdiv on the windows of the queries (k symbols every w, as the reference's `hapdiv` cuts them; queries as for mem): an (n, 9) int32

@@ -44,6 +44,17 @@ def load_library():
     return L
 
 
+def parse_rows(arg):
+    """rb3h_parse_rows: an argument of `remove`, `A` or `A-B`, as (A, B); None for anything else"""
+    L = load_library()
+    L.rb3h_parse_rows.restype = ctypes.c_int
+    L.rb3h_parse_rows.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+    if L.rb3h_parse_rows(arg.encode() if isinstance(arg, str) else arg, ctypes.byref(a), ctypes.byref(b)) != 0:
+        return None
+    return int(a.value), int(b.value)
+
+
 class _Buf(ctypes.Structure):
     _fields_ = [("l", ctypes.c_int64), ("m", ctypes.c_int64), ("s", ctypes.c_void_p)]
 
