@@ -678,6 +678,30 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 typedef struct { double ms_total, ms_mark, ms_build; int64_t n_strings, n_rows, n_steps, n_pieces, max_piece_steps, removed[6]; } rb3gpu_remove_stats_t;
 int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gpu_remove_stats_t *st);
 
+/* regions of the indexed strings, read through the sampled suffix array the handle holds (rb3gpu_ssa_set / rb3gpu_ssa_keep; no counterpart in the reference;
+ * DESIGN.md 7m): random access into the indexed text.  A region is (row r, beg, end): the symbols [beg, end) of string r, the string rb3gpu_retrieve spells for
+ * row r < acc[1]; 0-based, end exclusive; valid iff 0 <= r < acc[1] and 0 <= beg < end <= the length of the string.  Sample x of the sampled suffix array says that
+ * row acc[1] + (x << ssa_shift) is the suffix of string s at text offset o; sorted by (s, o) -- a table of 4 bytes per sample, made by the first call and kept with
+ * the sampled suffix array until that is dropped or replaced -- the samples are an index from text coordinates to rows.  A region is read by its anchor, the sample
+ * of r with the smallest offset >= end (sentinel row r, at the length of the string, where there is none), and by every sample of r with beg < o < end, each an
+ * octet of lanes that walks LF down to beg or to the row of the next sample: o_anchor - beg steps per region, no chain longer than one gap between samples
+ * whatever the length of the string, nothing outside the region touched.  A region without an anchor needs the length of its string: it is measured by a walk
+ * from row r to the first sample (or the sentinel), and only such regions are.  ALL regions are validated before the callback sees anything.  The answers
+ * reach cb in the order asked, duplicates and overlaps answered independently, a slice at a time (host memory valid during the call only): the n regions from i0
+ * on, region i0 + i at symbols[off[i], off[i + 1]) (nt6 codes, text order; n + 1 offsets, off[0] = 0); a slice is as many consecutive regions as
+ * rb3gpu_tune "fetch_slice" symbols admit (default 64 M; a longer region is a slice of its own).  A nonzero return from cb stops the call and is returned.
+ * n == 0 succeeds.  RB3GPU_EINVAL for a NULL callback and for an invalid region: *bad (may be NULL; -1 otherwise) receives the index of the first one, and
+ * nothing has reached the callback; RB3GPU_ESTATE without an index or without a sampled suffix array on the handle; RB3GPU_EUNSUP for 2^32 - 1 samples or more;
+ * RB3GPU_EINTERNAL, and no output for the slice, where a walker lands on a sample that does not say (its string, its offset) or reads the start of its string
+ * above beg: the sampled suffix array is not of this index.  The handle is unchanged by any outcome, apart from the table.  The call holds 68 bytes per region
+ * and the output of a slice on the device; while the table is made, 24 bytes per sample more.  st (may be NULL): ms_total wall time; ms_table (0 unless this call
+ * made the table), ms_plan (plan and measuring), ms_walk the phases (HIP events); n_walkers; n_measured regions without an anchor; n_steps LF steps of the
+ * measuring walks and of the walkers; max_walk_steps the longest walk of a walker */
+typedef struct { int64_t row, beg, end; } rb3gpu_region_t;
+typedef int (*rb3gpu_fetch_cb)(void *ud, int64_t i0, int64_t n, const int64_t *off, const uint8_t *symbols); /* nt6 codes, text order; n + 1 offsets */
+typedef struct { double ms_total, ms_table, ms_plan, ms_walk; int64_t n_regions, n_symbols, n_walkers, n_measured, n_steps, max_walk_steps, n_slices; } rb3gpu_fetch_stats_t;
+int rb3gpu_fetch(rb3gpu_t *h, int64_t n, const rb3gpu_region_t *reg, int64_t *bad, rb3gpu_fetch_cb cb, void *ud, rb3gpu_fetch_stats_t *st);
+
 /* the HIP device and stream of a handle (for communicators implemented outside the library) */
 int rb3gpu_device_of(const rb3gpu_t *h);
 void *rb3gpu_stream_of(const rb3gpu_t *h);
@@ -697,7 +721,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
  *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e and rb3gpu_sw_local; 0 = 16 K), "sw_table" N (as "hapdiv_table", for both);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
- *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8);
+ *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8); "fetch_slice" N (symbols of a slice of regions of rb3gpu_fetch; 0 = 64 M);
  *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);
  *   the full table with defaults is in docs/LAB_NOTEBOOK.md section 8c

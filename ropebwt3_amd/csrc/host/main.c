@@ -2065,6 +2065,233 @@ static int main_remove(int argc, char *argv[])
 	return ret;
 }
 
+/* fetch [-f FILE] [--row] [-s INT] <idx> [region ...] (no counterpart in the reference): regions of the indexed sequences through the sampled suffix array,
+ * ONE call of rb3gpu_fetch.  A region is the word name:beg-end[:+|:-] (rb3h_region_parse: 0-based, end-exclusive, the name cut at the last colons); -f adds BED lines.
+ * Named regions need <idx>.ssa and <idx>.len.gz and an index of both strands in input order: sequence i forward is row 2i, region as given; strand - is row 2i + 1,
+ * region [len - end, len - beg), the reverse complement of the forward region read straight off the index.  --row: the name is a string number of `get`, only the .ssa
+ * is needed and any index will do.  -s INT: where <idx>.ssa is absent the samples are made on the device at that rate.  Per region `>` and the region as it was asked
+ * (a BED line as name:beg-end[:strand]), then a line of $ACGTN letters.  Nothing is guessed: a word that is no region, an unknown name, an end beyond the sequence and no
+ * region at all are one line on stderr each, exit 1, nothing on stdout. */
+typedef struct { char *label; int64_t name_len, beg, end; int strand; } fetch_req_t;
+typedef struct { const fetch_req_t *q; rb3h_buf_t out; int err; } fetch_out_t;
+
+static int fetch_sink(void *ud, int64_t i0, int64_t n, const int64_t *off, const uint8_t *symbols)
+{
+	fetch_out_t *o = (fetch_out_t*)ud;
+	int64_t i, k;
+	for (i = 0; i < n && !o->err; ++i) {
+		const char *label = o->q[i0 + i].label;
+		const int64_t l = off[i + 1] - off[i], ll = (int64_t)strlen(label), need = l + ll + 8;
+		uint8_t *p;
+		if (o->out.l + need > o->out.m) {
+			const int64_t m = (o->out.l + need) * 2;
+			uint8_t *t = (uint8_t*)realloc(o->out.s, (size_t)m);
+			if (t == 0) { o->err = 1; break; }
+			o->out.s = t, o->out.m = m;
+		}
+		p = o->out.s + o->out.l;
+		*p++ = '>';
+		memcpy(p, label, (size_t)ll), p += ll;
+		*p++ = '\n';
+		for (k = 0; k < l; ++k) *p++ = (uint8_t)"$ACGTN"[symbols[off[i] + k] < 6 ? symbols[off[i] + k] : 5];
+		*p++ = '\n';
+		o->out.l = p - o->out.s;
+		if (out_flush(&o->out, 0) < 0) o->err = 1;
+	}
+	return o->err ? -1 : 0;
+}
+
+typedef struct { fetch_req_t *a; int64_t n, m; } fetch_vec_t;
+
+static int fetch_add(fetch_vec_t *v, const char *str, int bed)
+{
+	rb3h_region_t r;
+	fetch_req_t *q;
+	if (rb3h_region_parse(str, bed, &r) < 0) {
+		size_t l = strlen(str);
+		while (l > 0 && (str[l - 1] == '\n' || str[l - 1] == '\r')) --l;
+		fprintf(stderr, "ERROR: fetch: '%.*s' is no region%s\n", (int)l, str, bed ? " (BED: name, beg, end in columns 1-3, beg < end)" : " name:beg-end (0-based, beg < end)");
+		return -1;
+	}
+	if (v->n == v->m) {
+		fetch_req_t *t;
+		v->m = v->m ? v->m * 2 : 64;
+		if ((t = (fetch_req_t*)realloc(v->a, (size_t)v->m * sizeof(*t))) == 0) { fprintf(stderr, "ERROR: out of memory\n"); return -1; }
+		v->a = t;
+	}
+	q = &v->a[v->n];
+	q->name_len = r.name_len, q->beg = r.beg, q->end = r.end, q->strand = r.strand;
+	if (bed) {
+		if ((q->label = (char*)malloc((size_t)r.name_len + 64)) == 0) { fprintf(stderr, "ERROR: out of memory\n"); return -1; }
+		memcpy(q->label, str, (size_t)r.name_len);
+		sprintf(q->label + r.name_len, ":%ld-%ld%s", (long)r.beg, (long)r.end, !r.stranded ? "" : r.strand < 0 ? ":-" : ":+");
+	} else if ((q->label = strdup(str)) == 0) { fprintf(stderr, "ERROR: out of memory\n"); return -1; }
+	++v->n;
+	return 0;
+}
+
+static const rb3h_sid_t *g_fetch_sid; /* (qsort and bsearch take no context) */
+
+static int fetch_name_cmp(const void *a, const void *b) { return strcmp(g_fetch_sid->name[*(const int64_t*)a], g_fetch_sid->name[*(const int64_t*)b]); }
+
+/* the sequence of that name, -1 if there is none (of several of one name: any) */
+static int64_t fetch_lookup(const rb3h_sid_t *sid, const int64_t *by_name, const char *name, int64_t name_len)
+{
+	int64_t lo = 0, hi = sid->n_seq;
+	while (lo < hi) {
+		const int64_t mid = (lo + hi) >> 1;
+		const char *s = sid->name[by_name[mid]];
+		int c = strncmp(s, name, (size_t)name_len);
+		if (c == 0 && s[name_len] != 0) c = 1;
+		if (c == 0) return by_name[mid];
+		if (c < 0) lo = mid + 1; else hi = mid;
+	}
+	return -1;
+}
+
+static const struct option fetch_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "host-fmd", no_argument, 0, 308 },
+	{ "row", no_argument, 0, 504 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_fetch(int argc, char *argv[])
+{
+	int c, i, ret = 0, device = 0, by_row = 0, ss = -1, ms;
+	const char *fn_bed = 0;
+	int64_t acc[7], m, n_sym, k, bad = -1, *by_name = 0;
+	fetch_vec_t rv = { 0, 0, 0 };
+	rb3gpu_region_t *reg = 0;
+	rb3gpu_fetch_stats_t st;
+	rb3h_ssa_t *sa = 0;
+	rb3h_sid_t *sid = 0;
+	index_host_t ih;
+	rb3gpu_t *h = 0;
+	fetch_out_t o;
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "f:s:", fetch_long_opts, 0)) >= 0) {
+		if (c == 'f') fn_bed = optarg;
+		else if (c == 's') ss = atoi(optarg);
+		else if (c == 301) device = atoi(optarg);
+		else if (c == 308) g_host_fmd = 1;
+		else if (c == 504) by_row = 1;
+		else if (c == '?') return 1;
+	}
+	if (argc - optind < 1) {
+		fprintf(stdout, "Usage: ropebwt3-amd fetch [options] <idx.fmd|fmr|bre> [name:beg-end[:+|:-] ...]\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -f FILE     read further regions from the BED file FILE (columns 1-3, strand from column 6)\n");
+		fprintf(stderr, "  --row       the name of a region is a string number of `get`; needs <idx>.ssa only\n");
+		fprintf(stderr, "  -s INT      where <idx>.ssa is absent, sample the suffix array at rate 2^INT on the device\n");
+		fprintf(stderr, "  --gpu INT   HIP device ordinal [0]\n");
+		fprintf(stderr, "Regions are 0-based and end-exclusive; named regions need <idx>.ssa and <idx>.len.gz\n");
+		return 0;
+	}
+	if (ss > 40) { fprintf(stderr, "ERROR: fetch: -s takes 0 to 40\n"); return 1; }
+	memset(&ih, 0, sizeof(ih));
+	memset(&o, 0, sizeof(o));
+	/* 1. the regions as they are written: nothing else is looked at before every one of them is one */
+	for (i = optind + 1; i < argc && ret == 0; ++i)
+		if (fetch_add(&rv, argv[i], 0) < 0) ret = 1;
+	if (fn_bed && ret == 0) {
+		FILE *fp = strcmp(fn_bed, "-") == 0 ? stdin : fopen(fn_bed, "r");
+		char *line = 0;
+		size_t cap = 0;
+		if (fp == 0) { fprintf(stderr, "ERROR: fetch: failed to open '%s'\n", fn_bed); ret = 1; }
+		while (ret == 0 && getline(&line, &cap, fp) >= 0) {
+			if (line[0] == '\n' || line[0] == '\r' || line[0] == 0 || line[0] == '#') continue;
+			if (fetch_add(&rv, line, 1) < 0) ret = 1;
+		}
+		free(line);
+		if (fp && fp != stdin) fclose(fp);
+	}
+	if (ret == 0 && rv.n == 0) { fprintf(stderr, "ERROR: fetch: no region to fetch\n"); ret = 1; }
+	for (k = 0; k < rv.n && ret == 0 && by_row; ++k) { /* --row: the name is a number, and a string has no other strand */
+		int64_t a, b;
+		char t[32];
+		if (rv.a[k].name_len > 20 || rv.a[k].strand < 0) a = -1;
+		else {
+			memcpy(t, rv.a[k].label, (size_t)rv.a[k].name_len), t[rv.a[k].name_len] = 0;
+			if (rb3h_parse_rows(t, &a, &b) < 0 || a != b) a = -1;
+		}
+		if (a < 0) { fprintf(stderr, "ERROR: fetch: '%s' is no region row:beg-end of --row (a string number, no strand)\n", rv.a[k].label); ret = 1; }
+	}
+	if (ret) goto done;
+	/* 2. the files beside the index, held against the index before anything is asked of a device (as mem -p does) */
+	side_read(argv[optind], &sa, &sid);
+	if ((sa == 0 && ss < 0) || (sid == 0 && !by_row)) goto no_side;
+	if (index_host_read(argv[optind], &ih) < 0) {
+		if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load index '%s'\n", argv[optind]);
+		ret = 1;
+		goto done;
+	}
+	m = index_host_sentinels(&ih, &n_sym);
+	for (ms = 1; (1LL << ms) < m; ++ms) {}
+	if (sa && (sa->m != m || sa->ms != ms || sa->ss > 40 || sa->n_ssa != (n_sym - m + (1LL << sa->ss) - 1) >> sa->ss)) goto no_side;
+	if (!by_row && sid->n_seq * 2 != m) goto no_side;
+	c = rb3h_verbose;
+	if (rb3h_verbose > 2) rb3h_verbose = 2; /* (the command may still refuse its regions with ONE line: the loading says nothing but errors and warnings until they are accepted) */
+	h = open_index(device, argv[optind], &ih);
+	rb3h_verbose = c;
+	if (h == 0) { index_host_free(&ih); ret = 1; goto done; }
+	rb3gpu_get_acc(h, acc);
+	if ((reg = (rb3gpu_region_t*)malloc((size_t)rv.n * sizeof(*reg))) == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; goto done; }
+	if (by_row) {
+		for (k = 0; k < rv.n; ++k) reg[k].row = atol(rv.a[k].label), reg[k].beg = rv.a[k].beg, reg[k].end = rv.a[k].end;
+	} else { /* 3. names to rows */
+		if (index_order(argv[optind]) != RB3GPU_SO_IO) {
+			fprintf(stderr, "ERROR: fetch: sequences are numbered in input order; the strings of this index are sorted (build -s / -r): use --row\n");
+			ret = 1;
+			goto done;
+		}
+		if (!both_strands(acc)) { ret = 1; goto done; }
+		if ((by_name = (int64_t*)malloc((size_t)(sid->n_seq + 1) * 8)) == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; goto done; }
+		for (k = 0; k < sid->n_seq; ++k) by_name[k] = k;
+		g_fetch_sid = sid;
+		qsort(by_name, (size_t)sid->n_seq, 8, fetch_name_cmp);
+		for (k = 0; k < rv.n; ++k) {
+			const fetch_req_t *q = &rv.a[k];
+			const int64_t s = fetch_lookup(sid, by_name, q->label, q->name_len);
+			if (s < 0) { fprintf(stderr, "ERROR: fetch: no sequence '%.*s' in the index (region '%s')\n", (int)q->name_len, q->label, q->label); ret = 1; goto done; }
+			if (q->end > sid->len[s]) { fprintf(stderr, "ERROR: fetch: region '%s' ends beyond its sequence of %ld symbols\n", q->label, (long)sid->len[s]); ret = 1; goto done; }
+			if (q->strand > 0) reg[k].row = 2 * s, reg[k].beg = q->beg, reg[k].end = q->end;
+			else reg[k].row = 2 * s + 1, reg[k].beg = sid->len[s] - q->end, reg[k].end = sid->len[s] - q->beg;
+		}
+	}
+	/* 4. the samples: the file's, or made on the device */
+	rb3gpu_tune(h, "verbose", rb3h_verbose > 2 ? 2 : rb3h_verbose);
+	if (sa) {
+		if (sa->m != acc[1] || rb3gpu_ssa_set(h, sa->ss, sa->ms, sa->m, sa->n_ssa, sa->r2i, sa->ssa) != 0) goto no_side;
+	} else if ((c = rb3gpu_ssa_keep(h, ss)) != 0) {
+		fprintf(stderr, "ERROR: the GPU engine failed to sample the suffix array: %s\n", rb3gpu_strerror(c));
+		ret = 1;
+		goto done;
+	}
+	o.q = rv.a;
+	c = rb3gpu_fetch(h, rv.n, reg, &bad, fetch_sink, &o, &st);
+	if (c == 0 && !o.err && out_flush(&o.out, 1) < 0) o.err = 1;
+	if (c == RB3GPU_EINVAL && bad >= 0 && !o.err) { fprintf(stderr, "ERROR: fetch: region '%s' lies outside the index (no such string, or an end beyond it)\n", rv.a[bad].label); ret = 1; }
+	else if (c == RB3GPU_EINTERNAL && !o.err) { fprintf(stderr, "ERROR: fetch: the suffix array samples do not belong to this index\n"); ret = 1; }
+	else if (c != 0 && !o.err) { fprintf(stderr, "ERROR: the GPU engine failed to fetch the regions: %s\n", rb3gpu_strerror(c)); ret = 1; }
+	else if (o.err || fflush(stdout) != 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (rb3h_verbose >= 3 && ret == 0)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld regions, %lld symbols in %lld slice(s): %lld walkers, %lld regions measured, %lld LF steps, the longest walk of %lld; %.3f ms in the engine, table %.3f ms, plan %.3f ms, walk %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_regions, (long long)st.n_symbols, (long long)st.n_slices, (long long)st.n_walkers, (long long)st.n_measured, (long long)st.n_steps,
+				(long long)st.max_walk_steps, st.ms_total, st.ms_table, st.ms_plan, st.ms_walk);
+done:
+	for (k = 0; k < rv.n; ++k) free(rv.a[k].label);
+	free(rv.a); free(reg); free(by_name); free(o.out.s);
+	if (h) rb3gpu_destroy(h);
+	rb3h_ssa_destroy(sa); rb3h_sid_destroy(sid);
+	return ret;
+no_side:
+	index_host_free(&ih);
+	if (rb3h_verbose >= 1) fprintf(stderr, "ERROR: failed to load suffix array samples or sequence names/lengths\n");
+	ret = 1;
+	goto done;
+}
+
 /* hapdiv: the windows of every query (k symbols every w, search.c:384-393) through rb3gpu_hapdiv, batch by batch; the lines of write_hapdiv */
 typedef struct { int32_t *r; int64_t n; } hapdiv_out_t;
 
@@ -2670,6 +2897,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    suffix     find the longest matching suffix of queries (on an MI355X)\n");
 	fprintf(fp, "    get        retrieve the i-th sequence from a BWT (on an MI355X)\n");
 	fprintf(fp, "    remove     take sequences out of a BWT (on an MI355X)\n");
+	fprintf(fp, "    fetch      retrieve regions of sequences through the sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
 	fprintf(fp, "    recode     convert an FMD/FMR file to plain text, FMD (-d) or FMR (-b) (host only)\n");
@@ -2692,6 +2920,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "suffix") == 0) ret = main_suffix(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "get") == 0) ret = main_get(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "remove") == 0) ret = main_remove(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "fetch") == 0) ret = main_fetch(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "recode") == 0) ret = main_recode(argc - 1, argv + 1);

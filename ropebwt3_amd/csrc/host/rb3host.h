@@ -20,6 +20,8 @@ extern int rb3h_verbose;
 /* ---- misc (misc.c:7-16, 116-150) ---- */
 int64_t rb3h_parse_num(const char *str);
 int rb3h_parse_rows(const char *str, int64_t *a, int64_t *b);              /* `7` or `3-9` of `remove`: 0, or -1 for anything else */
+typedef struct { int64_t name_len, beg, end; int strand, stranded; } rb3h_region_t; /* the name is the first name_len bytes of what was parsed; strand +1 or -1, stranded: it was named */
+int rb3h_region_parse(const char *str, int bed, rb3h_region_t *r);           /* `name:beg-end[:+|:-]` of `fetch`, or a BED line: 0, or -1 for anything else */
 double rb3h_realtime(void);
 double rb3h_cputime(void);
 double rb3h_percent_cpu(void);

@@ -28,6 +28,7 @@
 #include "rb3gpu_mem.h"
 #include "rb3gpu_walk.h"
 #include "rb3gpu_remove.h"
+#include "rb3gpu_fetch.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
 #include "rb3gpu_swlocal.h"
@@ -176,6 +177,7 @@ struct Tune {
 	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
 	int get_piece = 0;       // rb3gpu_retrieve_pieces: log2 of the splitter spacing of the pieces (0: 8)
+	int64_t fetch_slice = 0; // rb3gpu_fetch: symbols of a slice of regions, i.e. bytes of output held on the device at once (0: 64 M; a region longer than that is a slice of its own)
 	int64_t locate_heap = 0; // rb3gpu_locate: entries of an octet's heap in LDS (0: 32; at most 80); an interval that needs more takes a heap in global memory
 	int64_t locate_slice = 0;// rb3gpu_locate: bytes of global-memory heaps held at once (0: 256 MB; a slice always takes at least one interval)
 	int lf_check = 4096;     // sampled LF-consistency check of pos[] after every merge: every n-th row (0: off)
@@ -267,6 +269,7 @@ struct rb3gpu_s {
 	uint64_t *ssa_dev = nullptr;     // the sampled suffix array of the index in place (rb3gpu_ssa_set / _keep): r2i[ssa_m], then ssa[ssa_n]
 	int ssa_ss = 0, ssa_ms = 0;
 	int64_t ssa_m = 0, ssa_n = 0;
+	uint32_t *ssa_tab = nullptr;     // the samples of ssa_dev by (string, offset), made by the first rb3gpu_fetch and dropped with ssa_dev: ssa_n entries
 	rb3order_ws *ows = nullptr;      // scratch of the string order (rb3gpu_order.hip), created on first use
 };
 
@@ -698,6 +701,7 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "suffix_slice")) t.suffix_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_piece")) t.get_piece = v < 1 ? 0 : v > 20 ? 20 : (int)v;
+	else if (!strcmp(key, "fetch_slice")) t.fetch_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "seed_chunk")) t.seed_chunk = v < 0 ? 0 : v;
 	else if (!strcmp(key, "seed_slice")) t.seed_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "locate_heap")) t.locate_heap = v < 0 ? 0 : v > 80 ? 80 : v;
@@ -739,7 +743,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "get_piece", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -779,8 +783,15 @@ rb3gpu_t *rb3gpu_create(const rb3gpu_opt_t *opt)
 }
 
 /* the sampled suffix array belongs to ONE index: whatever replaces the index gives it up */
+static void ssa_tab_drop(rb3gpu_t *h)
+{
+	if (h->ssa_tab) dev_free(h, h->ssa_tab, (size_t)h->ssa_n * 4);
+	h->ssa_tab = nullptr;
+}
+
 static void ssa_drop(rb3gpu_t *h)
 {
+	ssa_tab_drop(h);
 	if (h->ssa_dev) dev_free(h, h->ssa_dev, (size_t)(h->ssa_m + h->ssa_n) * 8);
 	h->ssa_dev = nullptr, h->ssa_m = h->ssa_n = 0, h->ssa_ss = h->ssa_ms = 0;
 }
@@ -6048,6 +6059,169 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 	return ret;
 }
 
+/* ---- fetch: regions of the indexed strings through the sampled suffix array (rb3gpu_fetch.h) ------- */
+
+#define RB3_FETCH_SLICE ((int64_t)64 << 20)   // symbols of a slice of regions
+
+/* the samples of the handle's sampled suffix array by (string, offset): made once, kept until the sampled suffix array goes (ssa_drop) */
+static int fetch_table(rb3gpu_t *h, double *ms)
+{
+	*ms = 0;
+	if (h->ssa_tab || h->ssa_n == 0) return 0;
+	const int64_t ns = h->ssa_n;
+	int obits = 1, r;
+	while (obits < 63 && ((int64_t)1 << obits) < h->n) ++obits; // (an offset is below the number of rows)
+	if (obits + h->ssa_ms > 64) return RB3GPU_EUNSUP;
+	WalkWs ws;
+	uint64_t *d_key[2] = { nullptr, nullptr };
+	uint32_t *d_val = nullptr, *d_tab = nullptr;
+	void *d_tmp = nullptr;
+	size_t sort_bytes = 0;
+	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+	HIPCHK(dalloc(&d_key[0], (size_t)ns * 8));
+	HIPCHK(dalloc(&d_key[1], (size_t)ns * 8));
+	HIPCHK(dalloc(&d_val, (size_t)ns * 4));
+	if ((r = rb3kount_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, ns, obits + h->ssa_ms, h->st)) < 0) return scan_err(r);
+	HIPCHK(dalloc(&d_tmp, sort_bytes + 256));
+	if ((r = dev_malloc(h, (void**)&d_tab, (size_t)ns * 4)) < 0) return r;
+	HIPCHK(hipEventRecord(h->ev[0], h->st));
+	hipLaunchKernelGGL(k_fetch_key, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->st, ns, h->ssa_ms, obits, (const uint64_t*)(h->ssa_dev + h->ssa_m), d_key[0], d_val);
+	size_t tb = sort_bytes;
+	r = rb3kount_sort_pairs(d_tmp, &tb, d_key[0], d_key[1], d_val, d_tab, ns, obits + h->ssa_ms, h->st);
+	hipError_t e = r < 0 ? hipSuccess : hipEventRecord(h->ev[1], h->st);
+	if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+	if (e == hipSuccess) e = hipGetLastError();
+	if (r < 0 || e != hipSuccess) {
+		dev_free(h, d_tab, (size_t)ns * 4);
+		if (r < 0) return scan_err(r);
+		HIPCHK(e);
+	}
+	*ms = ev_ms(h->ev[0], h->ev[1]);
+	h->ssa_tab = d_tab;
+	return 0;
+}
+
+int rb3gpu_fetch(rb3gpu_t *h, int64_t n, const rb3gpu_region_t *reg, int64_t *bad, rb3gpu_fetch_cb cb, void *ud, rb3gpu_fetch_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (bad) *bad = -1;
+	if (!h || !cb || n < 0 || (n > 0 && !reg)) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr || h->ssa_dev == nullptr) return RB3GPU_ESTATE;
+	double t0, ms_table = 0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	if (st) st->n_regions = n;
+	if (n == 0) { if (st) st->ms_total = (now_s() - t0) * 1e3; return 0; }
+	if (h->ssa_n >= ((int64_t)1 << 32) - 1) return RB3GPU_EUNSUP; // (the table holds 32-bit sample numbers, a region counts its walkers in 32 bits)
+	if (const int e = fetch_table(h, &ms_table)) return e;
+	const int64_t m = h->acc[1], budget = h->tn.fetch_slice > 0 ? h->tn.fetch_slice : RB3_FETCH_SLICE;
+	const IdxView ix = view_of(h);
+	WalkWs ws;
+	PieceEv ev;
+	FetchRegion *d_reg = nullptr;
+	int64_t *d_ak = nullptr, *d_ao = nullptr, *d_mlist = nullptr, *d_ioff = nullptr, *d_off = nullptr;
+	uint32_t *d_first = nullptr, *d_cnt32 = nullptr;
+	uint8_t *d_out = nullptr;
+	unsigned long long *d_ctr = nullptr;
+	void *d_tmp = nullptr;
+	size_t scan_bytes = 0;
+	static_assert(sizeof(FetchRegion) == sizeof(rb3gpu_region_t), "the regions go to the device as they come");
+	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
+	HIPCHK(dalloc(&d_reg, (size_t)n * sizeof(FetchRegion)));
+	HIPCHK(dalloc(&d_ak, (size_t)n * 8));
+	HIPCHK(dalloc(&d_ao, (size_t)n * 8));
+	HIPCHK(dalloc(&d_mlist, (size_t)n * 8));
+	HIPCHK(dalloc(&d_ioff, (size_t)(n + 1) * 8));
+	HIPCHK(dalloc(&d_off, (size_t)(n + 1) * 8));
+	HIPCHK(dalloc(&d_first, (size_t)n * 4));
+	HIPCHK(dalloc(&d_cnt32, (size_t)(n + 1) * 4));
+	HIPCHK(dalloc(&d_ctr, 64));
+	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 128, hipHostMallocDefault));
+	for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+	{
+		const int r = rb3kount_scan(nullptr, &scan_bytes, nullptr, nullptr, n + 1, h->st);
+		if (r < 0) return scan_err(r);
+		HIPCHK(dalloc(&d_tmp, scan_bytes + 256));
+	}
+	FetchView fv;
+	fv.ss = h->ssa_ss, fv.ms = h->ssa_ms, fv.n_ssa = h->ssa_n, fv.ssa = h->ssa_dev + h->ssa_m, fv.tab = h->ssa_tab, fv.reg = d_reg, fv.ak = d_ak, fv.ao = d_ao;
+	fv.first = d_first, fv.cnt32 = d_cnt32, fv.mlist = d_mlist, fv.ioff = d_ioff, fv.off = d_off;
+	// 1. the plan of every region, the lengths of the strings whose regions have no anchor; nothing is emitted before all regions are known to be valid
+	HIPCHK(hipMemcpyAsync(d_reg, reg, (size_t)n * sizeof(FetchRegion), hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
+	HIPCHK(hipMemsetAsync(d_ctr + 5, 0xff, 8, h->st));
+	HIPCHK(hipMemsetAsync(d_cnt32 + n, 0, 4, h->st)); // (the entry behind the last region, for the scan)
+	HIPCHK(hipEventRecord(ev.e[0], h->st));
+	hipLaunchKernelGGL(k_fetch_plan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, fv, n, m, d_ctr);
+	{
+		const int64_t nb = std::min<int64_t>((n * 8 + 255) / 256, 4096);
+		hipLaunchKernelGGL(k_fetch_len, dim3((unsigned)nb), dim3(256), 0, h->st, ix, fv, d_ctr);
+	}
+	HIPCHK(hipEventRecord(ev.e[1], h->st));
+	std::vector<uint32_t> vcnt((size_t)n);
+	HIPCHK(hipMemcpyAsync(vcnt.data(), d_cnt32, (size_t)n * 4, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 64, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipGetLastError());
+	const double ms_plan = ev_ms(ev.e[0], ev.e[1]);
+	const int64_t n_measured = (int64_t)ws.h_ctr[4];
+	int64_t n_steps = (int64_t)ws.h_ctr[1], n_walkers = 0, n_sym = 0, n_slices = 0, max_walk = 0, out_cap = 0;
+	double ms_walk = 0;
+	if (ws.h_ctr[2] != 0) { // a sample of another string on the way from a sentinel's row: not the sampled suffix array of this index
+		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] fetch: %llu strings measured through samples that are not theirs\n", ws.h_ctr[2]);
+		return RB3GPU_EINTERNAL;
+	}
+	if (ws.h_ctr[5] != ~0ull) { // an invalid region: the first one
+		if (bad) *bad = (int64_t)ws.h_ctr[5];
+		return RB3GPU_EINVAL;
+	}
+	// 2. slices of consecutive regions whose lengths sum to at most the budget, a longer region alone
+	std::vector<int64_t> off;
+	int ret = 0;
+	for (int64_t i0 = 0; i0 < n && ret == 0; ++n_slices) {
+		int64_t i1 = i0 + 1, tot = reg[i0].end - reg[i0].beg, items = vcnt[(size_t)i0];
+		while (i1 < n && tot + (reg[i1].end - reg[i1].beg) <= budget) tot += reg[i1].end - reg[i1].beg, items += vcnt[(size_t)i1], ++i1;
+		off.assign((size_t)(i1 - i0 + 1), 0);
+		for (int64_t i = i0; i < i1; ++i) off[(size_t)(i - i0 + 1)] = off[(size_t)(i - i0)] + (reg[i].end - reg[i].beg);
+		if (tot > out_cap) { // (grows to the largest slice: the budget, or the one region that exceeds it)
+			if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
+			if (d_out) { for (void *&p : ws.dv) if (p == d_out) p = nullptr; HIPCHK(hipFree(d_out)); d_out = nullptr; }
+			out_cap = 0;
+			const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 20));
+			HIPCHK(dalloc(&d_out, (size_t)oc + 64));
+			HIPCHK(hipHostMalloc(&ws.h_out, (size_t)oc + 64, hipHostMallocDefault));
+			out_cap = oc;
+		}
+		size_t tb = scan_bytes + 256;
+		const int r = rb3kount_scan(d_tmp, &tb, d_cnt32 + i0, d_ioff, i1 - i0 + 1, h->st); // (the scan reads the count behind the slice's last region and does not use it)
+		if (r < 0) return scan_err(r);
+		HIPCHK(hipMemcpyAsync(d_off, off.data(), (size_t)(i1 - i0 + 1) * 8, hipMemcpyHostToDevice, h->st));
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 32, h->st));
+		HIPCHK(hipMemcpyAsync(ws.h_ctr + 9, d_ioff + (i1 - i0), 8, hipMemcpyDeviceToHost, h->st));
+		const int64_t nb = std::min<int64_t>((items * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(ev.e[4], h->st));
+		hipLaunchKernelGGL(k_fetch_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, fv, i0, i1 - i0, d_out, tot, d_ctr);
+		HIPCHK(hipEventRecord(ev.e[5], h->st));
+		HIPCHK(hipMemcpyAsync(ws.h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 32, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_walk += ev_ms(ev.e[4], ev.e[5]);
+		n_steps += (int64_t)ws.h_ctr[1], n_walkers += items, n_sym += tot, max_walk = std::max(max_walk, (int64_t)ws.h_ctr[3]);
+		if ((int64_t)ws.h_ctr[9] != items) return RB3GPU_EINTERNAL; // the scan on the device and the sum on the host are of the same numbers
+		if (ws.h_ctr[2] != 0) { // a walker met a sample that is not (its string, its offset), or the start of its string above beg
+			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] fetch: %llu walkers met rows the sampled suffix array does not describe\n", ws.h_ctr[2]);
+			return RB3GPU_EINTERNAL;
+		}
+		ret = cb(ud, i0, i1 - i0, off.data(), (const uint8_t*)ws.h_out);
+		i0 = i1;
+	}
+	if (st) {
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_table = ms_table, st->ms_plan = ms_plan, st->ms_walk = ms_walk;
+		st->n_symbols = n_sym, st->n_walkers = n_walkers, st->n_measured = n_measured, st->n_steps = n_steps, st->max_walk_steps = max_walk, st->n_slices = n_slices;
+	}
+	return ret;
+}
+
 /* ---- remove: strings taken out of the index (rb3gpu_remove.h) ------------------------------------ */
 
 /* "the old index without the marked rows" as a source of from_fmd_chunked.  The view is of the index as it stood BEFORE the builder ran: the builder clears
@@ -6195,6 +6369,7 @@ int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gp
 	uint64_t *const o_ssa = h->ssa_dev;
 	int64_t o_acc[7];
 	memcpy(o_acc, h->acc, sizeof(o_acc));
+	ssa_tab_drop(h); // (made again by the next rb3gpu_fetch if the old index comes back)
 	h->ssa_dev = nullptr, h->ssa_m = h->ssa_n = 0, h->ssa_ss = h->ssa_ms = 0;
 	if (h->tn.load_chunk > (n_new >> RB3_GRP_BITS) + 1) h->tn.load_chunk = (n_new >> RB3_GRP_BITS) + 1; // (the builder's scratch is sized by the chunk, not by the index)
 	const double ms_build0 = h->stt.ms_build;

@@ -169,6 +169,18 @@ class RemoveStats(ctypes.Structure):
     def as_dict(self):
         return {k: (list(getattr(self, k)) if k == "removed" else getattr(self, k)) for k, _ in self._fields_}
 
+
+class FetchStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_table", ctypes.c_double), ("ms_plan", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_regions", ctypes.c_int64),
+                ("n_symbols", ctypes.c_int64), ("n_walkers", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_steps", ctypes.c_int64), ("max_walk_steps", ctypes.c_int64),
+                ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+FETCH_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p)
+
 # name -> (restype, argtypes); every symbol declared in include/rb3gpu.h
 SYMBOLS = {
     "rb3gpu_opt_init": (None, [ctypes.POINTER(Opt)]),
@@ -296,6 +308,7 @@ SYMBOLS = {
     "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
     "rb3gpu_retrieve_pieces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(PiecesStats)]),
     "rb3gpu_remove": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RemoveStats)]),
+    "rb3gpu_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), FETCH_F, ctypes.c_void_p, ctypes.POINTER(FetchStats)]),
 }
 
 # rb3gpu_comm_t (include/rb3gpu.h): the two collectives of the interval-sharded merge
@@ -1005,6 +1018,29 @@ class Rb3Gpu:
         self._chk(self._lib.rb3gpu_remove(self._h, rows.size, rows.ctypes.data if rows.size else None, 1 if pieces else 0, ctypes.byref(st)), "rb3gpu_remove")
         if stats is not None:
             stats.update(st.as_dict())
+
+    def fetch(self, rows, begs, ends, stats=False):
+        """rb3gpu_fetch: the symbols [begs[i], ends[i]) of string rows[i] (0-based, end exclusive; string r is what retrieve([r]) spells), read through the
+        sampled suffix array on the handle (ssa_keep / ssa_set): a list of uint8 arrays of nt6 codes in text order, in the order asked.  stats=True: (that list,
+        rb3gpu_fetch_stats_t as a dict).  An invalid region raises with RB3GPU_EINVAL, the index of the first one in the message and in the error's `bad`"""
+        reg = np.empty((len(rows), 3), dtype=np.int64)
+        if len(rows) != len(begs) or len(rows) != len(ends):
+            raise ValueError("rows, begs and ends must be of one length")
+        reg[:, 0], reg[:, 1], reg[:, 2] = rows, begs, ends
+        seqs = []
+
+        def cb(_ud, _i0, n, off, symbols):
+            o = np.ctypeslib.as_array(off, shape=(n + 1,)).copy()
+            buf = np.frombuffer(ctypes.string_at(symbols, int(o[n])), dtype=np.uint8) if o[n] > 0 else np.zeros(0, dtype=np.uint8)
+            seqs.extend(buf[int(o[i]):int(o[i + 1])].copy() for i in range(n))
+            return 0
+        st, bad = FetchStats(), ctypes.c_int64(-1)
+        r = self._lib.rb3gpu_fetch(self._h, reg.shape[0], reg.ctypes.data if reg.size else None, ctypes.byref(bad), FETCH_F(cb), None, ctypes.byref(st))
+        if r < 0:
+            e = Rb3GpuError(r, "rb3gpu_fetch" if bad.value < 0 else "rb3gpu_fetch (region %d)" % bad.value)
+            e.bad = bad.value
+            raise e
+        return (seqs, st.as_dict()) if stats else seqs
 
     def hapdiv(self, queries, k=101, w=50, n_best=25, min_sc=30, match=1, mis=3, gap_open=5, gap_ext=2, e2e_drop=-1, stats=None):
         """rb3gpu_hapdiv on the windows of the queries (k symbols every w, as the reference's `hapdiv` cuts them; queries as for mem): an (n, 9) int32

@@ -55,6 +55,23 @@ def parse_rows(arg):
     return int(a.value), int(b.value)
 
 
+class _Region(ctypes.Structure):
+    _fields_ = [("name_len", ctypes.c_int64), ("beg", ctypes.c_int64), ("end", ctypes.c_int64), ("strand", ctypes.c_int), ("stranded", ctypes.c_int)]
+
+
+def region_parse(arg, bed=False):
+    """rb3h_region_parse: a region of `fetch`, the word `name:beg-end[:+|:-]` or (bed=True) a BED line, as (name, beg, end, strand) with the name as bytes and
+    strand +1 or -1; None for anything else"""
+    L = load_library()
+    L.rb3h_region_parse.restype = ctypes.c_int
+    L.rb3h_region_parse.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(_Region)]
+    arg = arg.encode() if isinstance(arg, str) else arg
+    r = _Region()
+    if L.rb3h_region_parse(arg, 1 if bed else 0, ctypes.byref(r)) != 0:
+        return None
+    return arg[:r.name_len], int(r.beg), int(r.end), int(r.strand)
+
+
 class _Buf(ctypes.Structure):
     _fields_ = [("l", ctypes.c_int64), ("m", ctypes.c_int64), ("s", ctypes.c_void_p)]
 
