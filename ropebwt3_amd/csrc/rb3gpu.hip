@@ -33,6 +33,7 @@
 #include "rb3gpu_sw.h"
 #include "rb3gpu_swlocal.h"
 #include "rb3gpu_locate.h"
+#include "rb3gpu_scratch.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
 		if (h && h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] %s:%d: %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); \
@@ -506,6 +507,14 @@ static void buf_release(rb3gpu_t *h, Buf &b)
 {
 	if (b.p) dev_free(h, b.p, b.cap);
 	b.p = nullptr, b.cap = 0;
+}
+
+// the handle's two pinned staging buffers, made when first wanted; where there is no room for them stage[i] stays null and the callers do without
+static void stage_ensure(rb3gpu_t *h)
+{
+	if (h->stage[0] != nullptr) return;
+	for (int i = 0; i < 2; ++i)
+		if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage[i] = nullptr; break; }
 }
 
 static float ev_ms(hipEvent_t a, hipEvent_t b)
@@ -1887,9 +1896,7 @@ static int merge_core(rb3gpu_t *h, int64_t len, const uint8_t *d_b2, int commit,
 		hipLaunchKernelGGL(k_walkers_sentinel_rows, dim3((unsigned)((n_walkers + 255) / 256)), dim3(256), 0, h->st, (Walker*)h->wl.p, n_walkers);
 	} else { // walker list: through the pinned staging buffer when it fits (a pageable source is staged by the runtime, slowly)
 		const size_t wb = (size_t)n_walkers * 32;
-		if (h->stage[0] == nullptr)
-			for (int i = 0; i < 2; ++i)
-				if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { h->stage[i] = nullptr; break; }
+		stage_ensure(h);
 		// The list goes over the side stream, beside the LF kernels queued above (on the main stream its DMA sat between them and
 		// the walkers: ~45 us per merge with the chip idle); the host copies it into pinned memory while those kernels run.
 		const void *src = walkers;
@@ -2371,10 +2378,7 @@ static int upload_b2(rb3gpu_t *h, int64_t len, const uint8_t *bwt)
 {
 	int r;
 	if ((r = buf_ensure(h, h->b2, (size_t)len + 16)) < 0) return r;
-	if (h->stage[0] == nullptr) {
-		for (int i = 0; i < 2; ++i)
-			if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { h->stage[i] = nullptr; break; }
-	}
+	stage_ensure(h);
 	const double t0 = now_s();
 	hipEvent_t done[2] = { h->ev[4], h->ev[5] };
 	HIPCHK(h2d_copy(h->b2.p, bwt, (size_t)len, h->st, h->stage, done));
@@ -3298,9 +3302,7 @@ static int export_run_words(rb3gpu_t *h, rb3gpu_emit_words_f emit, void *data)
 	uint64_t *host = nullptr;
 	size_t host_cap = 0;
 	if ((ret = buf_ensure(h, h->misc, MISC_WORDS * 8)) < 0) return ret;
-	if (h->stage[0] == nullptr)
-		for (int i = 0; i < 2; ++i)
-			if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { h->stage[i] = nullptr; break; }
+	stage_ensure(h);
 	const int64_t ngrp = (h->n + RB3_GRP - 1) >> RB3_GRP_BITS, gchunk = RB3_RCHUNK_WINS / RB3_GRP_WINS;
 	(void)nwin;
 	for (int64_t g0 = 0; g0 < ngrp && ret == 0; g0 += gchunk) {
@@ -3676,9 +3678,7 @@ int rb3gpu_export_bre(rb3gpu_t *h, int b_per_run, rb3gpu_emit_bytes_f emit, void
 	const int64_t cap = piece + RB3_GRP; // (a piece ends with a whole group: at most 8191 runs more)
 	int64_t win = (piece * 2 + 4095) & ~(int64_t)4095; // (a window of record bytes: what the staging buffers hold, less where pieces are small)
 	if (win > (int64_t)RB3_STAGE_BYTES) win = (int64_t)RB3_STAGE_BYTES;
-	if (h->stage[0] == nullptr)
-		for (int i = 0; i < 2; ++i)
-			if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage[i] = nullptr; break; }
+	stage_ensure(h);
 	if ((r = export_make_room(h, (size_t)cap * 16 + 2 * (size_t)win, nr, __func__)) < 0) return r; // (run starts and record offsets of a piece, two windows)
 	rb3bre_enc *enc = nullptr;
 	int fr = rb3bre_enc_begin(h->st, b_per_run, cap, win, h->stage, &enc);
@@ -3721,9 +3721,7 @@ static int bre_open(rb3gpu_t *h, int b_per_run, int64_t n_rec, const uint8_t *re
 	int r;
 	memset(s, 0, sizeof(*s));
 	if ((r = buf_ensure(h, h->xbuf, nb + 16, true)) < 0) return r;
-	if (h->stage[0] == nullptr)
-		for (int i = 0; i < 2; ++i)
-			if (hipHostMalloc((void**)&h->stage[i], RB3_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->stage[i] = nullptr; break; }
+	stage_ensure(h);
 	const double t0 = now_s();
 	hipEvent_t done[2] = { h->ev[4], h->ev[5] };
 	HIPCHK(h2d_copy(h->xbuf.p, records, nb, h->st, h->stage, done));
@@ -4500,6 +4498,7 @@ int rb3gpu_sync(rb3gpu_t *h)
 }
 
 /* ---- what the query drivers below share: each keeps its own control flow and calls these in place ---- */
+/* what a call of a driver allocates lives in a Scratch (rb3gpu_scratch.h) and goes with it at every return; what the handle keeps goes through dev_malloc / buf_ensure */
 
 // both strands (rb3_fmi_is_symmetric, fm-index.h:135): the forward extension is a backward extension of the reverse complement
 static bool both_strands(const rb3gpu_t *h) { return (h->acc[1] & 1) == 0 && h->acc[2] - h->acc[1] == h->acc[5] - h->acc[4] && h->acc[3] - h->acc[2] == h->acc[4] - h->acc[3]; }
@@ -4553,30 +4552,16 @@ struct KountWs {
 	int64_t *h_small = nullptr;    // page-locked landing place of the counts the host asks for
 	std::vector<hipEvent_t> ev;    // pairs around k_kount_expand, read at the next synchronisation
 	size_t ev_used = 0;
-	~KountWs()
-	{
-		for (auto &l : lv) if (l.p) (void)hipFree(l.p);
-		if (tab) (void)hipFree(tab);
-		if (misc) (void)hipFree(misc);
-		if (tmp) (void)hipFree(tmp);
-		if (d_out) (void)hipFree(d_out);
-		if (h_out) (void)hipHostFree(h_out);
-		if (h_small) (void)hipHostFree(h_small);
-		for (auto e : ev) (void)hipEventDestroy(e);
-	}
 };
 
-static int kount_level_ensure(rb3gpu_t *h, KountLevel &l, int64_t need, int64_t cap, int W, int ni)
+static int kount_level_ensure(rb3gpu_t *h, Scratch &sc, KountLevel &l, int64_t need, int64_t cap, int W, int ni)
 {
 	if (l.cap >= need) return 0;
 	const int64_t c = std::max(need, std::min(cap, 2 * l.cap));
-	if (l.p) {
-		HIPCHK(hipStreamSynchronize(h->st));
-		HIPCHK(hipFree(l.p));
-		l.p = nullptr, l.cap = 0;
-	}
+	if (l.p) HIPCHK(hipStreamSynchronize(h->st));
+	l.cap = 0;
 	const size_t bytes = (size_t)c * (8 * W + 16 * ni + 64 * ni) + (size_t)(c + 1) * 12 + 64;
-	HIPCHK(hipMalloc(&l.p, bytes));
+	HIPCHK(sc.regrow(&l.p, (void**)nullptr, bytes));
 	l.cap = c;
 	l.code = (uint64_t*)l.p;
 	l.iv = (int64_t*)(l.code + c * W);
@@ -4614,25 +4599,26 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 	}
 	if (cap < 4) cap = 4; // (a parent has up to four children: every slice takes at least one)
 	const int64_t lim_out = std::min(cap, RB3_KOUNT_OUT_CHUNK), sync_ub = std::min(cap, RB3_KOUNT_SYNC_UB);
+	Scratch sc;
 	KountWs ws;
 	ws.lv.resize((size_t)k);
 	std::vector<IdxView> hv((size_t)ni);
 	for (int i = 0; i < ni; ++i) hv[i] = view_of(hs[i]);
-	HIPCHK(hipMalloc(&ws.tab, sizeof(IdxView) * ni));
+	HIPCHK(sc.dev(&ws.tab, sizeof(IdxView) * ni));
 	HIPCHK(hipMemcpyAsync(ws.tab, hv.data(), sizeof(IdxView) * ni, hipMemcpyHostToDevice, h->st));
-	HIPCHK(hipMalloc(&ws.misc, 64));
+	HIPCHK(sc.dev(&ws.misc, 64));
 	HIPCHK(hipMemsetAsync(ws.misc, 0, 64, h->st));
-	HIPCHK(hipHostMalloc((void**)&ws.h_small, 64, hipHostMallocDefault));
+	HIPCHK(sc.pinned(&ws.h_small, 64));
 	{
 		int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, cap + 1, h->st);
 		if (r < 0) return scan_err(r);
-		HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
+		HIPCHK(sc.dev(&ws.tmp, ws.tmp_bytes + 256));
 	}
 	double ms_expand = 0;
 	auto ev_get = [&]() -> hipEvent_t {
 		if (ws.ev_used == ws.ev.size()) {
 			hipEvent_t e;
-			if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+			if (sc.event(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
 			ws.ev.push_back(e);
 		}
 		return ws.ev[ws.ev_used++];
@@ -4659,7 +4645,7 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 	struct Frame { const int64_t *pn; int64_t nub, n, total, i, base; int phase; }; // phase 0: to expand, 1: slices of its children, 2: done
 	std::vector<Frame> F((size_t)k);
 	int r;
-	if ((r = kount_level_ensure(h, ws.lv[0], 1, cap, W, ni)) < 0) return r;
+	if ((r = kount_level_ensure(h, sc, ws.lv[0], 1, cap, W, ni)) < 0) return r;
 	hipLaunchKernelGGL(k_kount_root, dim3(1), dim3(64), 0, h->st, (const IdxView*)ws.tab, ni, W, ws.lv[0].code, ws.lv[0].iv, ws.misc);
 	F[0] = {ws.misc, 1, 0, 0, 0, 0, 0};
 	int64_t n_out = 0, n_split = 0;
@@ -4672,7 +4658,7 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 		if (f.phase == 0) {
 			if ((r = expand(d, f.pn, f.nub)) < 0) return r;
 			if (!leaf && 4 * f.nub <= sync_ub) { // every child fits: the next frontier without a word to the host
-				if ((r = kount_level_ensure(h, ws.lv[d + 1], 4 * f.nub, cap, W, ni)) < 0) return r;
+				if ((r = kount_level_ensure(h, sc, ws.lv[d + 1], 4 * f.nub, cap, W, ni)) < 0) return r;
 				KountLevel &C = ws.lv[d + 1];
 				hipLaunchKernelGGL(k_kount_emit, dim3(grid(f.nub)), dim3(256), 0, h->st, (const uint64_t*)P.code, (const int64_t*)P.ci, (const int64_t*)P.off, W, ni, d, k,
 						min_occ, (int64_t)0, (int64_t)0, f.pn, 0, C.code, C.iv, (uint8_t*)nullptr, (int64_t*)nullptr);
@@ -4703,12 +4689,8 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 		if (leaf) {
 			if (c > ws.out_cap) {
 				const int64_t oc = std::max(c, std::min(lim_out, 2 * ws.out_cap));
-				if (ws.d_out) { HIPCHK(hipFree(ws.d_out)); ws.d_out = nullptr; }
-				if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
 				ws.out_cap = 0;
-				const size_t ob = ((size_t)oc * k + 7) / 8 * 8 + (size_t)oc * ni * 8;
-				HIPCHK(hipMalloc(&ws.d_out, ob));
-				HIPCHK(hipHostMalloc((void**)&ws.h_out, ob, hipHostMallocDefault));
+				HIPCHK(sc.regrow(&ws.d_out, &ws.h_out, ((size_t)oc * k + 7) / 8 * 8 + (size_t)oc * ni * 8));
 				ws.out_cap = oc;
 			}
 			const size_t coff = ((size_t)ws.out_cap * k + 7) / 8 * 8;
@@ -4722,7 +4704,7 @@ int rb3gpu_kount(rb3gpu_t *const *hs, int n_idx, int k, int64_t min_occ, int64_t
 			if (c > 0) ret = cb(ud, c, ni, k, ws.h_out, (const int64_t*)(ws.h_out + coff));
 			continue;
 		}
-		if ((r = kount_level_ensure(h, ws.lv[d + 1], c, cap, W, ni)) < 0) return r;
+		if ((r = kount_level_ensure(h, sc, ws.lv[d + 1], c, cap, W, ni)) < 0) return r;
 		KountLevel &C = ws.lv[d + 1];
 		hipLaunchKernelGGL(k_kount_emit, dim3(grid(j - f.i)), dim3(256), 0, h->st, (const uint64_t*)P.code, (const int64_t*)P.ci, (const int64_t*)P.off, W, ni, d, k,
 				min_occ, f.i, j, (const int64_t*)nullptr, 0, C.code, C.iv, (uint8_t*)nullptr, (int64_t*)nullptr);
@@ -4761,32 +4743,24 @@ struct LocWs {
 	std::vector<int64_t> h_size, h_off, h_idx, h_hoff; // of the slice: sizes (filled by the caller), places of the pairs; of a tier-2 slice: intervals, places of the heaps
 	double ms = 0;
 	int64_t pops = 0, n_iv = 0, n_t2 = 0, max_heap = 0, n_pairs = 0, n_slices = 0;
-	~LocWs()
-	{
-		void *dv[] = { src, iv, off, idx, hoff, cnt, flag, tmp, ctr, heap, d_pairs };
-		for (void *p : dv) if (p) (void)hipFree(p);
-		if (h_pairs) (void)hipHostFree(h_pairs);
-		if (h_small) (void)hipHostFree(h_small);
-		for (auto e : ev) if (e) (void)hipEventDestroy(e);
-	}
 };
 
-static int loc_init(rb3gpu_t *h, LocWs &ws, int64_t n_cap, bool own_src)
+static int loc_init(rb3gpu_t *h, Scratch &sc, LocWs &ws, int64_t n_cap, bool own_src)
 {
 	if (n_cap < 1) n_cap = 1;
 	ws.n_cap = n_cap;
-	if (own_src) HIPCHK(hipMalloc(&ws.src, (size_t)n_cap * 16));
-	HIPCHK(hipMalloc(&ws.iv, (size_t)n_cap * 16));
-	HIPCHK(hipMalloc(&ws.off, (size_t)(n_cap + 1) * 8));
-	HIPCHK(hipMalloc(&ws.cnt, (size_t)(n_cap + 1) * 4));
-	HIPCHK(hipMalloc(&ws.flag, (size_t)n_cap * 4));
-	HIPCHK(hipMalloc(&ws.ctr, LOC_CTR_WORDS * 8));
+	if (own_src) HIPCHK(sc.dev(&ws.src, (size_t)n_cap * 16));
+	HIPCHK(sc.dev(&ws.iv, (size_t)n_cap * 16));
+	HIPCHK(sc.dev(&ws.off, (size_t)(n_cap + 1) * 8));
+	HIPCHK(sc.dev(&ws.cnt, (size_t)(n_cap + 1) * 4));
+	HIPCHK(sc.dev(&ws.flag, (size_t)n_cap * 4));
+	HIPCHK(sc.dev(&ws.ctr, LOC_CTR_WORDS * 8));
 	HIPCHK(hipMemsetAsync(ws.ctr, 0, LOC_CTR_WORDS * 8, h->st));
-	HIPCHK(hipHostMalloc((void**)&ws.h_small, 128, hipHostMallocDefault));
-	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&ws.ev[i]));
+	HIPCHK(sc.pinned(&ws.h_small, 128));
+	for (int i = 0; i < 4; ++i) HIPCHK(sc.event(&ws.ev[i]));
 	const int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, n_cap + 1, h->st);
 	if (r < 0) return scan_err(r);
-	HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
+	HIPCHK(sc.dev(&ws.tmp, ws.tmp_bytes + 256));
 	return 0;
 }
 
@@ -4813,7 +4787,7 @@ static int64_t loc_heap_bound(int64_t size, int64_t max_pos, int ss)
 
 /* nn intervals whose bounds lie on the device (lo = d_src[i * stride], then the end or, with is_size, the size) and whose sizes the caller has put
  * in ws.h_size: their pairs to ws.h_pairs, pair k of interval i at ws.h_off[i] + k */
-static int loc_slice(rb3gpu_t *h, LocWs &ws, int64_t nn, const int64_t *d_src, int stride, int is_size, int64_t max_pos)
+static int loc_slice(rb3gpu_t *h, Scratch &sc, LocWs &ws, int64_t nn, const int64_t *d_src, int stride, int is_size, int64_t max_pos)
 {
 	if (nn < 1 || nn > ws.n_cap) return RB3GPU_EINTERNAL;
 	ws.h_off.resize((size_t)nn + 1);
@@ -4824,11 +4798,8 @@ static int loc_slice(rb3gpu_t *h, LocWs &ws, int64_t nn, const int64_t *d_src, i
 	if (tot == 0) return 0;
 	if (tot > ws.pair_cap) {
 		const int64_t pc = std::max(tot, std::min(RB3_LOC_SLICE_PAIRS, 2 * ws.pair_cap));
-		if (ws.d_pairs) { HIPCHK(hipFree(ws.d_pairs)); ws.d_pairs = nullptr; }
-		if (ws.h_pairs) { HIPCHK(hipHostFree(ws.h_pairs)); ws.h_pairs = nullptr; }
 		ws.pair_cap = 0;
-		HIPCHK(hipMalloc(&ws.d_pairs, (size_t)pc * sizeof(LocPair)));
-		HIPCHK(hipHostMalloc((void**)&ws.h_pairs, (size_t)pc * sizeof(LocPair), hipHostMallocDefault));
+		HIPCHK(sc.regrow(&ws.d_pairs, &ws.h_pairs, (size_t)pc * sizeof(LocPair)));
 		ws.pair_cap = pc;
 	}
 	const IdxView ix = view_of(h);
@@ -4874,17 +4845,14 @@ static int loc_slice(rb3gpu_t *h, LocWs &ws, int64_t nn, const int64_t *d_src, i
 			ws.h_hoff.push_back(ent);
 			seen += k;
 			if (k > ws.t2_cap) {
-				if (ws.idx) { HIPCHK(hipFree(ws.idx)); ws.idx = nullptr; }
-				if (ws.hoff) { HIPCHK(hipFree(ws.hoff)); ws.hoff = nullptr; }
 				ws.t2_cap = 0;
-				HIPCHK(hipMalloc(&ws.idx, (size_t)k * 8));
-				HIPCHK(hipMalloc(&ws.hoff, (size_t)(k + 1) * 8));
+				HIPCHK(sc.regrow(&ws.idx, (void**)nullptr, (size_t)k * 8));
+				HIPCHK(sc.regrow(&ws.hoff, (void**)nullptr, (size_t)(k + 1) * 8));
 				ws.t2_cap = k;
 			}
 			if (ent > ws.heap_cap) {
-				if (ws.heap) { HIPCHK(hipFree(ws.heap)); ws.heap = nullptr; }
 				ws.heap_cap = 0;
-				HIPCHK(hipMalloc(&ws.heap, (size_t)ent * sizeof(LocEnt)));
+				HIPCHK(sc.regrow(&ws.heap, (void**)nullptr, (size_t)ent * sizeof(LocEnt)));
 				ws.heap_cap = ent;
 			}
 			HIPCHK(hipMemcpyAsync(ws.idx, ws.h_idx.data(), (size_t)k * 8, hipMemcpyHostToDevice, h->st));
@@ -4928,9 +4896,10 @@ int rb3gpu_locate(rb3gpu_t *h, int64_t n, const int64_t *lo, const int64_t *hi, 
 	double t0;
 	if (const int e = drv_enter(h, &t0)) return e;
 	if (n == 0) return 0;
+	Scratch sc;
 	LocWs ws;
 	int r;
-	if ((r = loc_init(h, ws, std::min(n, RB3_LOC_SLICE_IV), true)) < 0) return r;
+	if ((r = loc_init(h, sc, ws, std::min(n, RB3_LOC_SLICE_IV), true)) < 0) return r;
 	std::vector<int64_t> size((size_t)n), pair;
 	for (int64_t i = 0; i < n; ++i) size[i] = hi[i] > lo[i] ? hi[i] - lo[i] : 0;
 	int ret = 0;
@@ -4940,7 +4909,7 @@ int rb3gpu_locate(rb3gpu_t *h, int64_t n, const int64_t *lo, const int64_t *hi, 
 		for (int64_t i = 0; i < nn; ++i) pair[2 * i] = lo[r0 + i], pair[2 * i + 1] = hi[r0 + i];
 		ws.h_size.assign(size.begin() + r0, size.begin() + r1);
 		HIPCHK(hipMemcpyAsync(ws.src, pair.data(), (size_t)nn * 16, hipMemcpyHostToDevice, h->st));
-		if ((r = loc_slice(h, ws, nn, ws.src, 2, 0, max_pos)) < 0) return r;
+		if ((r = loc_slice(h, sc, ws, nn, ws.src, 2, 0, max_pos)) < 0) return r;
 		ret = cb(ud, r0, nn, ws.h_off.data(), (const rb3gpu_pos_t*)ws.h_pairs);
 		r0 = r1;
 	}
@@ -4965,15 +4934,6 @@ struct MemWs {
 	MemOut *d_out = nullptr, *h_out = nullptr;
 	int64_t out_cap = 0;
 	hipEvent_t e0 = nullptr, e1 = nullptr;
-	~MemWs()
-	{
-		void *dv[] = { sym, qoff, off, wq, wa, ctr, raw, flag, tmp, d_out };
-		for (void *p : dv) if (p) (void)hipFree(p);
-		if (h_out) (void)hipHostFree(h_out);
-		if (h_small) (void)hipHostFree(h_small);
-		if (e0) (void)hipEventDestroy(e0);
-		if (e1) (void)hipEventDestroy(e1);
-	}
 };
 
 /* max_pos > 0: the records of a slice stay on the device until their intervals are located, and reach cbp with their positions */
@@ -5009,27 +4969,28 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 	auto w_end = [&](int64_t w) { return std::min(offsets[wq[w]] + wa[w] + chunk, offsets[wq[w] + 1]); };
 	int64_t cap = h->tn.mem_slice > 0 ? h->tn.mem_slice : RB3_MEM_SLICE;
 	cap = std::min(total, std::max(cap, std::min(chunk, max_len)));
+	Scratch sc;
 	MemWs ws;
 	LocWs lws;
 	if (max_pos > 0) {
-		const int r = loc_init(h, lws, std::min(cap, RB3_LOC_SLICE_IV), false);
+		const int r = loc_init(h, sc, lws, std::min(cap, RB3_LOC_SLICE_IV), false);
 		if (r < 0) return r;
 	}
-	HIPCHK(hipMalloc(&ws.sym, (size_t)total + 64));
-	HIPCHK(hipMalloc(&ws.qoff, (size_t)(n_query + 1) * 8));
-	HIPCHK(hipMalloc(&ws.wq, (size_t)nw * 4));
-	HIPCHK(hipMalloc(&ws.wa, (size_t)nw * 4));
-	HIPCHK(hipMalloc(&ws.ctr, 64));
-	HIPCHK(hipMalloc(&ws.raw, (size_t)cap * sizeof(MemRaw)));
-	HIPCHK(hipMalloc(&ws.flag, (size_t)(cap + 1) * 4));
-	HIPCHK(hipMalloc(&ws.off, (size_t)(cap + 1) * 8));
-	HIPCHK(hipHostMalloc((void**)&ws.h_small, 64, hipHostMallocDefault));
-	HIPCHK(hipEventCreate(&ws.e0));
-	HIPCHK(hipEventCreate(&ws.e1));
+	HIPCHK(sc.dev(&ws.sym, (size_t)total + 64));
+	HIPCHK(sc.dev(&ws.qoff, (size_t)(n_query + 1) * 8));
+	HIPCHK(sc.dev(&ws.wq, (size_t)nw * 4));
+	HIPCHK(sc.dev(&ws.wa, (size_t)nw * 4));
+	HIPCHK(sc.dev(&ws.ctr, 64));
+	HIPCHK(sc.dev(&ws.raw, (size_t)cap * sizeof(MemRaw)));
+	HIPCHK(sc.dev(&ws.flag, (size_t)(cap + 1) * 4));
+	HIPCHK(sc.dev(&ws.off, (size_t)(cap + 1) * 8));
+	HIPCHK(sc.pinned(&ws.h_small, 64));
+	HIPCHK(sc.event(&ws.e0));
+	HIPCHK(sc.event(&ws.e1));
 	{
 		const int r = rb3kount_scan(nullptr, &ws.tmp_bytes, nullptr, nullptr, cap + 1, h->st);
 		if (r < 0) return scan_err(r);
-		HIPCHK(hipMalloc(&ws.tmp, ws.tmp_bytes + 256));
+		HIPCHK(sc.dev(&ws.tmp, ws.tmp_bytes + 256));
 	}
 	HIPCHK(hipMemcpyAsync(ws.sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(ws.qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
@@ -5066,11 +5027,8 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 		if (c > 0) {
 			if (c > ws.out_cap) {
 				const int64_t oc = std::max(c, std::min(cap, 2 * ws.out_cap));
-				if (ws.d_out) { HIPCHK(hipFree(ws.d_out)); ws.d_out = nullptr; }
-				if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
 				ws.out_cap = 0;
-				HIPCHK(hipMalloc(&ws.d_out, (size_t)oc * sizeof(MemOut)));
-				HIPCHK(hipHostMalloc((void**)&ws.h_out, (size_t)oc * sizeof(MemOut), hipHostMallocDefault));
+				HIPCHK(sc.regrow(&ws.d_out, &ws.h_out, (size_t)oc * sizeof(MemOut)));
 				ws.out_cap = oc;
 			}
 			hipLaunchKernelGGL(k_mem_gather, dim3((unsigned)std::min<int64_t>((ns + 255) / 256, 16384)), dim3(256), 0, h->st, (const MemRaw*)ws.raw, (const uint32_t*)ws.flag,
@@ -5085,7 +5043,7 @@ static int mem_run(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 					for (int64_t i = 0; i < lim; ++i) lws.h_size[i] = ws.h_out[r0 + i].size;
 					const int64_t nn = loc_slice_end(lws, lws.h_size.data(), 0, lim, max_pos);
 					lws.h_size.resize((size_t)nn);
-					const int r = loc_slice(h, lws, nn, (const int64_t*)(ws.d_out + r0) + 1, (int)(sizeof(MemOut) / 8), 1, max_pos);
+					const int r = loc_slice(h, sc, lws, nn, (const int64_t*)(ws.d_out + r0) + 1, (int)(sizeof(MemOut) / 8), 1, max_pos);
 					if (r < 0) return r;
 					ret = cbp(ud, nn, (const rb3gpu_mem_rec_t*)ws.h_out + r0, lws.h_off.data(), (const rb3gpu_pos_t*)lws.h_pairs);
 					r0 += nn;
@@ -5119,16 +5077,8 @@ int rb3gpu_mem_pos(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const u
 #define RB3_HD_SLICE ((int64_t)1 << 16)       // windows per launch
 #define RB3_HD_BLOCKS 2048                    // windows in flight at most: 8 single-wave blocks on each of 256 CUs (20 KB of LDS a block)
 
-// a device buffer that lives as long as dv's owner does (64 bytes to spare behind it)
-static hipError_t dv_alloc(std::vector<void*> &dv, void **p, size_t bytes)
-{
-	const hipError_t e = hipMalloc(p, bytes + 64);
-	if (e == hipSuccess) dv.push_back(*p);
-	return e;
-}
-
 /* the per-block workspace of the dynamic program (HdWs of rb3gpu_hapdiv.h) for hapdiv, sw -e and sw --local: hd_ws_size sets the capacities for n_best N
- * (everything else 0) and returns the bytes a block takes, without a backtrack matrix; hd_ws_alloc gives nb blocks their six arrays */
+ * (everything else 0) and returns the bytes a block takes, without a backtrack matrix; hd_ws_alloc gives nb blocks their six arrays (64 bytes to spare behind each) */
 static size_t hd_ws_size(HdWs &ws, int64_t N)
 {
 	int64_t cap0 = 4;
@@ -5140,31 +5090,16 @@ static size_t hd_ws_size(HdWs &ws, int64_t N)
 	return (size_t)ws.tab_cap * sizeof(HdCell) + (size_t)N * (sizeof(HdCell) + 5 * sizeof(HdExt) + 4) + (size_t)ws.stack_cap * sizeof(HdZ) + (size_t)ws.fpar_cap * 16 + 256;
 }
 
-static int hd_ws_alloc(rb3gpu_t *h, std::vector<void*> &dv, HdWs &ws, int64_t nb, int64_t N)
+static int hd_ws_alloc(rb3gpu_t *h, Scratch &sc, HdWs &ws, int64_t nb, int64_t N)
 {
-	HIPCHK(dv_alloc(dv, (void**)&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell)));
-	HIPCHK(dv_alloc(dv, (void**)&ws.row, (size_t)nb * N * sizeof(HdCell)));
-	HIPCHK(dv_alloc(dv, (void**)&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt)));
-	HIPCHK(dv_alloc(dv, (void**)&ws.heap, (size_t)nb * N * 4));
-	HIPCHK(dv_alloc(dv, (void**)&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ)));
-	HIPCHK(dv_alloc(dv, (void**)&ws.fpar, (size_t)nb * ws.fpar_cap * 16));
+	HIPCHK(sc.dev(&ws.tab, (size_t)nb * ws.tab_cap * sizeof(HdCell) + 64));
+	HIPCHK(sc.dev(&ws.row, (size_t)nb * N * sizeof(HdCell) + 64));
+	HIPCHK(sc.dev(&ws.ext, (size_t)nb * N * 5 * sizeof(HdExt) + 64));
+	HIPCHK(sc.dev(&ws.heap, (size_t)nb * N * 4 + 64));
+	HIPCHK(sc.dev(&ws.stack, (size_t)nb * ws.stack_cap * sizeof(HdZ) + 64));
+	HIPCHK(sc.dev(&ws.fpar, (size_t)nb * ws.fpar_cap * 16 + 64));
 	return 0;
 }
-
-struct HdHostWs {
-	std::vector<void*> dv;
-	int32_t *h_out = nullptr;
-	unsigned long long *h_ctr = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	~HdHostWs()
-	{
-		for (void *p : dv) if (p) (void)hipFree(p);
-		if (h_out) (void)hipHostFree(h_out);
-		if (h_ctr) (void)hipHostFree(h_ctr);
-		if (e0) (void)hipEventDestroy(e0);
-		if (e1) (void)hipEventDestroy(e1);
-	}
-};
 
 int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint8_t *symbols, int32_t k, const rb3gpu_hapdiv_opt_t *opt,
 		rb3gpu_hapdiv_cb cb, void *ud, rb3gpu_hapdiv_stats_t *st)
@@ -5195,22 +5130,22 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 	const size_t fixed = (size_t)total + (size_t)n_win * 8 + (size_t)slice * 36 + ((size_t)64 << 20);
 	if (fr / 2 < fixed + per_block) return RB3GPU_ENOMEM;
 	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr / 2 - fixed) / per_block)); // the windows in flight: by the free memory
-	HdHostWs hw;
-	auto dalloc = [&](void **p, size_t bytes) { return dv_alloc(hw.dv, p, bytes); };
+	Scratch sc;
 	uint8_t *d_sym = nullptr;
 	int64_t *d_off = nullptr;
-	int32_t *d_out = nullptr;
-	unsigned long long *d_ctr = nullptr;
-	HIPCHK(dalloc((void**)&d_sym, (size_t)total));
-	HIPCHK(dalloc((void**)&d_off, (size_t)n_win * 8));
-	HIPCHK(dalloc((void**)&d_out, (size_t)slice * 36));
-	HIPCHK(dalloc((void**)&d_ctr, 64));
-	HIPCHK(dalloc((void**)&ws.bt, (size_t)nb * ws.bt_stride * 4));
-	if (const int e = hd_ws_alloc(h, hw.dv, ws, nb, N)) return e;
-	HIPCHK(hipHostMalloc((void**)&hw.h_out, (size_t)slice * 36, hipHostMallocDefault));
-	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
-	HIPCHK(hipEventCreate(&hw.e0));
-	HIPCHK(hipEventCreate(&hw.e1));
+	int32_t *d_out = nullptr, *h_out = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	HIPCHK(sc.dev(&d_sym, (size_t)total + 64));
+	HIPCHK(sc.dev(&d_off, (size_t)n_win * 8 + 64));
+	HIPCHK(sc.dev(&d_out, (size_t)slice * 36 + 64));
+	HIPCHK(sc.dev(&d_ctr, 64 + 64));
+	HIPCHK(sc.dev(&ws.bt, (size_t)nb * ws.bt_stride * 4 + 64));
+	if (const int e = hd_ws_alloc(h, sc, ws, nb, N)) return e;
+	HIPCHK(sc.pinned(&h_out, (size_t)slice * 36));
+	HIPCHK(sc.pinned(&h_ctr, 64));
+	HIPCHK(sc.event(&e0));
+	HIPCHK(sc.event(&e1));
 	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_off, win_off, (size_t)n_win * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
@@ -5223,19 +5158,19 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 	int ret = 0;
 	for (int64_t w0 = 0; w0 < n_win && ret == 0; ++n_slices) {
 		const int64_t w1 = std::min(n_win, w0 + slice);
-		HIPCHK(hipEventRecord(hw.e0, h->st));
+		HIPCHK(hipEventRecord(e0, h->st));
 		hipLaunchKernelGGL(k_hapdiv, dim3((unsigned)std::min(nb, w1 - w0)), dim3(64), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_off, w0, w1, o, ws, lds_slots, d_out, d_ctr);
-		HIPCHK(hipEventRecord(hw.e1, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_out, d_out, (size_t)(w1 - w0) * 36, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(hw.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipEventRecord(e1, h->st));
+		HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)(w1 - w0) * 36, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
-		ms_dp += ev_ms(hw.e0, hw.e1);
-		if (hw.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a window could not be represented: no record of this slice goes out
-		ret = cb(ud, w0, w1 - w0, (const rb3gpu_hapdiv_rec_t*)hw.h_out);
+		ms_dp += ev_ms(e0, e1);
+		if (h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a window could not be represented: no record of this slice goes out
+		ret = cb(ud, w0, w1 - w0, (const rb3gpu_hapdiv_rec_t*)h_out);
 		w0 = w1;
 	}
-	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->n_ext = (int64_t)hw.h_ctr[0], st->n_windows = n_win, st->n_tier2 = (int64_t)hw.h_ctr[1], st->n_slices = n_slices;
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_dp = ms_dp, st->n_ext = (int64_t)h_ctr[0], st->n_windows = n_win, st->n_tier2 = (int64_t)h_ctr[1], st->n_slices = n_slices;
 	return ret;
 }
 
@@ -5246,7 +5181,6 @@ int rb3gpu_hapdiv(rb3gpu_t *h, int64_t n_win, const int64_t *win_off, const uint
 #define RB3_SW_BT_BYTES ((int64_t)4 << 30)    // backtrack matrices of a slice at most (less where the free memory says so; one query may need what it needs)
 
 struct SwHostWs {
-	std::vector<void*> dv;
 	// per slot of a slice (sw_slices): hit or not, its steps, both scanned, and the hit as the fill kernel found it
 	uint32_t *d_flag = nullptr, *d_cnt = nullptr;
 	int64_t *d_hoff = nullptr, *d_soff = nullptr;
@@ -5263,43 +5197,24 @@ struct SwHostWs {
 	unsigned long long *h_ctr = nullptr;
 	int64_t *h_tot = nullptr;
 	hipEvent_t e[4] = { nullptr, nullptr, nullptr, nullptr };
-	~SwHostWs()
-	{
-		for (void *p : dv) if (p) (void)hipFree(p);
-		if (d_hits) (void)hipFree(d_hits);
-		if (d_steps) (void)hipFree(d_steps);
-		void *hv[] = { h_hits, h_steps, h_nhit, h_ctr, h_tot };
-		for (void *p : hv) if (p) (void)hipHostFree(p);
-		for (auto x : e) if (x) (void)hipEventDestroy(x);
-	}
 };
 
-// a device buffer and its page-locked copy on the host, both of `bytes` bytes, in place of the ones there are
-static int sw_regrow(rb3gpu_t *h, void **d, void **hp, size_t bytes)
-{
-	if (*d) { HIPCHK(hipFree(*d)); *d = nullptr; }
-	if (*hp) { HIPCHK(hipHostFree(*hp)); *hp = nullptr; }
-	HIPCHK(hipMalloc(d, bytes));
-	HIPCHK(hipHostMalloc(hp, bytes, hipHostMallocDefault));
-	return 0;
-}
-
 // what sw_slices works with, for slices of up to n_slot_cap slots: the caller's kernels are given these
-static int sw_slice_bufs(rb3gpu_t *h, SwHostWs &hw, int64_t n_slot_cap)
+static int sw_slice_bufs(rb3gpu_t *h, Scratch &sc, SwHostWs &hw, int64_t n_slot_cap)
 {
 	hw.n_slot_cap = n_slot_cap;
-	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_flag, (size_t)(n_slot_cap + 1) * 4));
-	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_cnt, (size_t)(n_slot_cap + 1) * 4));
-	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_hoff, (size_t)(n_slot_cap + 1) * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_soff, (size_t)(n_slot_cap + 1) * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_raw, (size_t)n_slot_cap * sizeof(SwRaw)));
-	HIPCHK(dv_alloc(hw.dv, (void**)&hw.d_ctr, 64));
+	HIPCHK(sc.dev(&hw.d_flag, (size_t)(n_slot_cap + 1) * 4 + 64));
+	HIPCHK(sc.dev(&hw.d_cnt, (size_t)(n_slot_cap + 1) * 4 + 64));
+	HIPCHK(sc.dev(&hw.d_hoff, (size_t)(n_slot_cap + 1) * 8 + 64));
+	HIPCHK(sc.dev(&hw.d_soff, (size_t)(n_slot_cap + 1) * 8 + 64));
+	HIPCHK(sc.dev(&hw.d_raw, (size_t)n_slot_cap * sizeof(SwRaw) + 64));
+	HIPCHK(sc.dev(&hw.d_ctr, 64 + 64));
 	const int r = rb3kount_scan(nullptr, &hw.tmp_bytes, nullptr, nullptr, n_slot_cap + 1, h->st);
 	if (r < 0) return scan_err(r);
-	HIPCHK(dv_alloc(hw.dv, &hw.d_tmp, hw.tmp_bytes + 256));
-	HIPCHK(hipHostMalloc((void**)&hw.h_ctr, 64, hipHostMallocDefault));
-	HIPCHK(hipHostMalloc((void**)&hw.h_tot, 64, hipHostMallocDefault));
-	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&hw.e[i]));
+	HIPCHK(sc.dev(&hw.d_tmp, hw.tmp_bytes + 256 + 64));
+	HIPCHK(sc.pinned(&hw.h_ctr, 64));
+	HIPCHK(sc.pinned(&hw.h_tot, 64));
+	for (int i = 0; i < 4; ++i) HIPCHK(sc.event(&hw.e[i]));
 	HIPCHK(hipMemsetAsync(hw.d_ctr, 0, 64, h->st));
 	return 0;
 }
@@ -5314,7 +5229,7 @@ struct SwFetch { const void *d; void *h; }; // an int per query of the slice tha
  * Returns what failed, or 0 and in *cb_ret what cb returned last; the statistics are written then */
 extern "C++" {
 template<class Fill, class After, class Emit>
-static int sw_slices(rb3gpu_t *h, SwHostWs &hw, const std::vector<int64_t> &cuts, int64_t per_q, const std::vector<SwFetch> &fetch, int64_t max_pos, double t0, Fill fill, After after,
+static int sw_slices(rb3gpu_t *h, Scratch &sc, SwHostWs &hw, const std::vector<int64_t> &cuts, int64_t per_q, const std::vector<SwFetch> &fetch, int64_t max_pos, double t0, Fill fill, After after,
 		Emit emit, rb3gpu_sw_cb cb, void *ud, int *cb_ret, rb3gpu_sw_stats_t *st, rb3gpu_locate_stats_t *lst)
 {
 	static_assert(sizeof(SwRaw) == 40, "the locate step reads (lo, hi) with a stride of five words");
@@ -5323,7 +5238,7 @@ static int sw_slices(rb3gpu_t *h, SwHostWs &hw, const std::vector<int64_t> &cuts
 	const int64_t loc_cap = std::max<int64_t>(1, max_pos);
 	LocWs lws;
 	if (with_pos) {
-		const int r = loc_init(h, lws, std::min<int64_t>(n_slot_cap, RB3_LOC_SLICE_IV), false);
+		const int r = loc_init(h, sc, lws, std::min<int64_t>(n_slot_cap, RB3_LOC_SLICE_IV), false);
 		if (r < 0) return r;
 	}
 	double ms_dp = 0, ms_bt = 0;
@@ -5359,13 +5274,13 @@ static int sw_slices(rb3gpu_t *h, SwHostWs &hw, const std::vector<int64_t> &cuts
 			if (nh > hw.hit_cap) {
 				const int64_t c = std::max(nh, std::min(n_slot_cap, 2 * hw.hit_cap));
 				hw.hit_cap = 0;
-				if (const int e = sw_regrow(h, (void**)&hw.d_hits, (void**)&hw.h_hits, (size_t)c * sizeof(SwRaw))) return e;
+				HIPCHK(sc.regrow(&hw.d_hits, &hw.h_hits, (size_t)c * sizeof(SwRaw)));
 				hw.hit_cap = c;
 			}
 			if (ns > hw.step_cap) {
 				const int64_t c = std::max(ns, 2 * hw.step_cap);
 				hw.step_cap = 0;
-				if (const int e = sw_regrow(h, (void**)&hw.d_steps, (void**)&hw.h_steps, (size_t)c + 64)) return e;
+				HIPCHK(sc.regrow(&hw.d_steps, &hw.h_steps, (size_t)c + 64));
 				hw.step_cap = c;
 			}
 			HIPCHK(hipEventRecord(hw.e[2], h->st));
@@ -5391,7 +5306,7 @@ static int sw_slices(rb3gpu_t *h, SwHostWs &hw, const std::vector<int64_t> &cuts
 					for (int64_t i = 0; i < lim; ++i) lws.h_size[i] = hits[(size_t)(r0 + i)].hi - hits[(size_t)(r0 + i)].lo;
 					const int64_t nn = loc_slice_end(lws, lws.h_size.data(), 0, lim, loc_cap);
 					lws.h_size.resize((size_t)nn);
-					const int lr = loc_slice(h, lws, nn, (const int64_t*)(hw.d_hits + r0), (int)(sizeof(SwRaw) / 8), 0, loc_cap);
+					const int lr = loc_slice(h, sc, lws, nn, (const int64_t*)(hw.d_hits + r0), (int)(sizeof(SwRaw) / 8), 0, loc_cap);
 					if (lr < 0) return lr;
 					const int64_t base = (int64_t)pairs.size(), np = lws.h_off[(size_t)nn];
 					if (np > 0) pairs.insert(pairs.end(), (const rb3gpu_pos_t*)lws.h_pairs, (const rb3gpu_pos_t*)lws.h_pairs + np);
@@ -5467,18 +5382,19 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 	const size_t fixed = (size_t)total + (size_t)n_query * 16 + (size_t)max_cells * 12 + (size_t)slice * N * 64 + ((size_t)64 << 20);
 	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
 	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
+	Scratch sc;
 	SwHostWs hw;
 	uint8_t *d_sym = nullptr;
 	int64_t *d_off = nullptr, *d_btoff = nullptr;
 	int32_t *d_nhit = nullptr;
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_sym, (size_t)total));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_off, (size_t)(n_query + 1) * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_btoff, (size_t)n_query * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_nhit, (size_t)slice * 4));
-	HIPCHK(dv_alloc(hw.dv, (void**)&ws.bt, (size_t)max_cells * 12));
-	if (const int e = hd_ws_alloc(h, hw.dv, ws, nb, N)) return e;
-	if (const int e = sw_slice_bufs(h, hw, slice * N)) return e;
-	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 4, hipHostMallocDefault));
+	HIPCHK(sc.dev(&d_sym, (size_t)total + 64));
+	HIPCHK(sc.dev(&d_off, (size_t)(n_query + 1) * 8 + 64));
+	HIPCHK(sc.dev(&d_btoff, (size_t)n_query * 8 + 64));
+	HIPCHK(sc.dev(&d_nhit, (size_t)slice * 4 + 64));
+	HIPCHK(sc.dev(&ws.bt, (size_t)max_cells * 12 + 64));
+	if (const int e = hd_ws_alloc(h, sc, ws, nb, N)) return e;
+	if (const int e = sw_slice_bufs(h, sc, hw, slice * N)) return e;
+	HIPCHK(sc.pinned(&hw.h_nhit, (size_t)slice * 4));
 	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_off, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_btoff, bt_off.data(), (size_t)n_query * 8, hipMemcpyHostToDevice, h->st));
@@ -5497,7 +5413,7 @@ int rb3gpu_sw_e2e(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 				q0, (int)N, (const uint32_t*)ws.bt, n_slot, (const uint32_t*)hw.d_flag, (const SwRaw*)hw.d_raw, (const int64_t*)hw.d_hoff, (const int64_t*)hw.d_soff, hw.d_hits, hw.d_steps, hw.d_ctr);
 	};
 	int ret = 0;
-	if (const int e = sw_slices(h, hw, cuts, N, {{d_nhit, hw.h_nhit}}, opt->max_pos, t0, fill, [](int64_t, int64_t) { return 0; }, emit, cb, ud, &ret, st, lst)) return e;
+	if (const int e = sw_slices(h, sc, hw, cuts, N, {{d_nhit, hw.h_nhit}}, opt->max_pos, t0, fill, [](int64_t, int64_t) { return 0; }, emit, cb, ud, &ret, st, lst)) return e;
 	return ret;
 }
 
@@ -5561,22 +5477,23 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 	const size_t fixed = (size_t)n_nodes * 9 + (size_t)n_edges * 4 + (size_t)n_query * 16 + (size_t)max_cells * cell_bytes + (size_t)max_nodes * 4 + (size_t)slice * 128 + ((size_t)64 << 20);
 	if (fr < fixed + per_block || (fr - fixed) / 2 < per_block) return RB3GPU_ENOMEM;
 	const int64_t nb = std::min<int64_t>(std::min<int64_t>(slice, RB3_HD_BLOCKS), (int64_t)((fr - fixed) / 2 / per_block));
+	Scratch sc;
 	SwHostWs hw;
 	uint8_t *d_nsym = nullptr;
 	int64_t *d_noff = nullptr, *d_poff = nullptr, *d_coff = nullptr;
 	int32_t *d_pre = nullptr, *d_node = nullptr, *h_node = nullptr;
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_nsym, (size_t)n_nodes));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_noff, (size_t)(n_query + 1) * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_poff, (size_t)(n_nodes + 1) * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_pre, (size_t)n_edges * 4));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_coff, (size_t)n_query * 8));
-	HIPCHK(dv_alloc(hw.dv, (void**)&d_node, (size_t)slice * 4));
-	HIPCHK(dv_alloc(hw.dv, (void**)&ws.cells, (size_t)max_cells * sizeof(HdCell)));
-	HIPCHK(dv_alloc(hw.dv, (void**)&ws.w.bt, (size_t)max_cells * 12));
-	HIPCHK(dv_alloc(hw.dv, (void**)&ws.ncnt, (size_t)max_nodes * 4));
-	if (const int e = hd_ws_alloc(h, hw.dv, ws.w, nb, N)) return e;
-	if (const int e = sw_slice_bufs(h, hw, slice)) return e;
-	HIPCHK(hipHostMalloc((void**)&hw.h_nhit, (size_t)slice * 8, hipHostMallocDefault)); // (the flags of the slice, then the nodes of its hits)
+	HIPCHK(sc.dev(&d_nsym, (size_t)n_nodes + 64));
+	HIPCHK(sc.dev(&d_noff, (size_t)(n_query + 1) * 8 + 64));
+	HIPCHK(sc.dev(&d_poff, (size_t)(n_nodes + 1) * 8 + 64));
+	HIPCHK(sc.dev(&d_pre, (size_t)n_edges * 4 + 64));
+	HIPCHK(sc.dev(&d_coff, (size_t)n_query * 8 + 64));
+	HIPCHK(sc.dev(&d_node, (size_t)slice * 4 + 64));
+	HIPCHK(sc.dev(&ws.cells, (size_t)max_cells * sizeof(HdCell) + 64));
+	HIPCHK(sc.dev(&ws.w.bt, (size_t)max_cells * 12 + 64));
+	HIPCHK(sc.dev(&ws.ncnt, (size_t)max_nodes * 4 + 64));
+	if (const int e = hd_ws_alloc(h, sc, ws.w, nb, N)) return e;
+	if (const int e = sw_slice_bufs(h, sc, hw, slice)) return e;
+	HIPCHK(sc.pinned(&hw.h_nhit, (size_t)slice * 8)); // (the flags of the slice, then the nodes of its hits)
 	h_node = hw.h_nhit + slice;
 	HIPCHK(hipMemcpyAsync(d_nsym, node_sym, (size_t)n_nodes, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_noff, node_off, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
@@ -5604,7 +5521,7 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 				q0, (int)N, (const uint32_t*)ws.w.bt, nq, (const uint32_t*)hw.d_flag, (const SwRaw*)hw.d_raw, (const int32_t*)d_node, (const int64_t*)hw.d_hoff, (const int64_t*)hw.d_soff, hw.d_hits, hw.d_steps, hw.d_ctr);
 	};
 	int ret = 0;
-	if (const int e = sw_slices(h, hw, cuts, 1, {{hw.d_flag, hw.h_nhit}, {d_node, h_node}}, opt->max_pos, // (one slot per query: its flag is its number of hits)
+	if (const int e = sw_slices(h, sc, hw, cuts, 1, {{hw.d_flag, hw.h_nhit}, {d_node, h_node}}, opt->max_pos, // (one slot per query: its flag is its number of hits)
 			 t0, fill, after, emit, cb, ud, &ret, st ? &st->sw : nullptr, lst)) return e;
 	if (st) st->n_nodes = n_nodes, st->n_edges = n_edges;
 	return ret;
@@ -5616,21 +5533,6 @@ int rb3gpu_sw_local(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const 
 #define RB3_GET_SLICE ((int64_t)1 << 26)      // symbols of an emit slice (a byte of device and of page-locked host memory each)
 #define RB3_SEED_CHUNK ((int64_t)2048)        // window starts per walker
 #define RB3_SEED_SLICE ((int64_t)1 << 20)     // walkers per launch
-
-struct WalkWs {
-	std::vector<void*> dv;
-	void *h_out = nullptr;
-	unsigned long long *h_ctr = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	~WalkWs()
-	{
-		for (void *p : dv) if (p) (void)hipFree(p);
-		if (h_out) (void)hipHostFree(h_out);
-		if (h_ctr) (void)hipHostFree(h_ctr);
-		if (e0) (void)hipEventDestroy(e0);
-		if (e1) (void)hipEventDestroy(e1);
-	}
-};
 
 int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const uint8_t *symbols, rb3gpu_suffix_rec_t *out, rb3gpu_suffix_stats_t *st)
 {
@@ -5649,19 +5551,19 @@ int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 		return 0;
 	}
 	const int64_t slice = std::min(n_query, h->tn.suffix_slice > 0 ? h->tn.suffix_slice : RB3_SUFFIX_SLICE);
-	WalkWs ws;
+	Scratch sc;
 	uint8_t *d_sym = nullptr;
 	int64_t *d_qoff = nullptr;
 	SuffixOut *d_out = nullptr;
-	unsigned long long *d_ctr = nullptr;
-	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
-	HIPCHK(dalloc(&d_sym, (size_t)total + 64));
-	HIPCHK(dalloc(&d_qoff, (size_t)(n_query + 1) * 8));
-	HIPCHK(dalloc(&d_out, (size_t)slice * sizeof(SuffixOut)));
-	HIPCHK(dalloc(&d_ctr, 64));
-	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 64, hipHostMallocDefault));
-	HIPCHK(hipEventCreate(&ws.e0));
-	HIPCHK(hipEventCreate(&ws.e1));
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	HIPCHK(sc.dev(&d_sym, (size_t)total + 64));
+	HIPCHK(sc.dev(&d_qoff, (size_t)(n_query + 1) * 8));
+	HIPCHK(sc.dev(&d_out, (size_t)slice * sizeof(SuffixOut)));
+	HIPCHK(sc.dev(&d_ctr, 64));
+	HIPCHK(sc.pinned(&h_ctr, 64));
+	HIPCHK(sc.event(&e0));
+	HIPCHK(sc.event(&e1));
 	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
@@ -5673,18 +5575,18 @@ int rb3gpu_suffix(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, const ui
 		const int64_t q1 = std::min(n_query, q0 + slice);
 		HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
 		const int64_t nb = std::min<int64_t>(((q1 - q0) * 8 + 255) / 256, 4096);
-		HIPCHK(hipEventRecord(ws.e0, h->st));
+		HIPCHK(hipEventRecord(e0, h->st));
 		hipLaunchKernelGGL(k_suffix_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_qoff, q0, q1, d_out, d_ctr);
-		HIPCHK(hipEventRecord(ws.e1, h->st));
+		HIPCHK(hipEventRecord(e1, h->st));
 		HIPCHK(hipMemcpyAsync(out + q0, d_out, (size_t)(q1 - q0) * sizeof(SuffixOut), hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
-		ms_walk += ev_ms(ws.e0, ws.e1);
+		ms_walk += ev_ms(e0, e1);
 		q0 = q1;
 	}
-	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
-	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_steps = (int64_t)ws.h_ctr[1], st->n_slices = n_slices;
+	if (st) st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_steps = (int64_t)h_ctr[1], st->n_slices = n_slices;
 	return 0;
 }
 
@@ -5713,28 +5615,27 @@ int rb3gpu_seed_present(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, co
 		return 0;
 	}
 	const int64_t slice = std::min(n_walkers, h->tn.seed_slice > 0 ? h->tn.seed_slice : RB3_SEED_SLICE);
-	WalkWs ws;
+	Scratch sc;
 	uint8_t *d_sym = nullptr, *d_present = nullptr;
 	int64_t *d_qoff = nullptr;
-	SeedWalker *d_wk = nullptr;
-	unsigned long long *d_ctr = nullptr;
-	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
-	HIPCHK(dalloc(&d_sym, (size_t)total + 64));
-	HIPCHK(dalloc(&d_qoff, (size_t)(n_query + 1) * 8));
-	HIPCHK(dalloc(&d_present, (size_t)n_query + 64));
-	HIPCHK(dalloc(&d_wk, (size_t)slice * sizeof(SeedWalker)));
-	HIPCHK(dalloc(&d_ctr, 64));
-	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 64, hipHostMallocDefault));
-	HIPCHK(hipHostMalloc(&ws.h_out, (size_t)slice * sizeof(SeedWalker), hipHostMallocDefault));
-	HIPCHK(hipEventCreate(&ws.e0));
-	HIPCHK(hipEventCreate(&ws.e1));
+	SeedWalker *d_wk = nullptr, *wk = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	HIPCHK(sc.dev(&d_sym, (size_t)total + 64));
+	HIPCHK(sc.dev(&d_qoff, (size_t)(n_query + 1) * 8));
+	HIPCHK(sc.dev(&d_present, (size_t)n_query + 64));
+	HIPCHK(sc.dev(&d_wk, (size_t)slice * sizeof(SeedWalker)));
+	HIPCHK(sc.dev(&d_ctr, 64));
+	HIPCHK(sc.pinned(&h_ctr, 64));
+	HIPCHK(sc.pinned(&wk, (size_t)slice * sizeof(SeedWalker)));
+	HIPCHK(sc.event(&e0));
+	HIPCHK(sc.event(&e1));
 	HIPCHK(hipMemcpyAsync(d_sym, symbols, (size_t)total, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemcpyAsync(d_qoff, offsets, (size_t)(n_query + 1) * 8, hipMemcpyHostToDevice, h->st));
 	HIPCHK(hipMemsetAsync(d_present, 0, (size_t)n_query + 64, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	const IdxView ix = view_of(h);
 	const Acc7 acc = acc7_of(h);
-	SeedWalker *wk = (SeedWalker*)ws.h_out;
 	double ms_walk = 0;
 	int64_t n_slices = 0, q = 0, a = 0; // the next walker starts at window a of query q
 	for (int64_t w0 = 0; w0 < n_walkers; ++n_slices) {
@@ -5750,21 +5651,21 @@ int rb3gpu_seed_present(rb3gpu_t *h, int64_t n_query, const int64_t *offsets, co
 		HIPCHK(hipMemcpyAsync(d_wk, wk, (size_t)nw * sizeof(SeedWalker), hipMemcpyHostToDevice, h->st));
 		HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
 		const int64_t nb = std::min<int64_t>((nw * 8 + 255) / 256, 4096);
-		HIPCHK(hipEventRecord(ws.e0, h->st));
+		HIPCHK(hipEventRecord(e0, h->st));
 		hipLaunchKernelGGL(k_seed_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, acc, (const uint8_t*)d_sym, (const int64_t*)d_qoff, (const SeedWalker*)d_wk, nw, (int32_t)min_len, d_present, d_ctr);
-		HIPCHK(hipEventRecord(ws.e1, h->st));
+		HIPCHK(hipEventRecord(e1, h->st));
 		HIPCHK(hipStreamSynchronize(h->st)); // (the walkers of the next slice are written where these were read from)
 		HIPCHK(hipGetLastError());
-		ms_walk += ev_ms(ws.e0, ws.e1);
+		ms_walk += ev_ms(e0, e1);
 		w0 += nw;
 	}
 	HIPCHK(hipMemcpyAsync(present, d_present, (size_t)n_query, hipMemcpyDeviceToHost, h->st));
-	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 16, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
 	if (st) {
 		int64_t np = 0;
 		for (int64_t i = 0; i < n_query; ++i) np += present[i] != 0;
-		st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_present = np, st->n_steps = (int64_t)ws.h_ctr[1], st->n_slices = n_slices;
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_present = np, st->n_steps = (int64_t)h_ctr[1], st->n_slices = n_slices;
 	}
 	return 0;
 }
@@ -5783,47 +5684,47 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 	const int64_t nv = (int64_t)vrow.size();
 	std::vector<int64_t> len((size_t)n, 0), end((size_t)n, -1), off;
 	const int64_t budget = h->tn.get_slice > 0 ? h->tn.get_slice : RB3_GET_SLICE;
-	WalkWs ws;
+	Scratch sc;
 	int64_t *d_rows = nullptr, *d_len = nullptr, *d_end = nullptr, *d_off = nullptr;
 	uint32_t *d_len32 = nullptr;
-	uint8_t *d_out = nullptr;
-	unsigned long long *d_ctr = nullptr;
+	uint8_t *d_out = nullptr, *h_out = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
 	void *d_tmp = nullptr;
 	size_t tmp_bytes = 0;
 	double ms_count = 0, ms_emit = 0;
 	int64_t n_sym = 0, n_slices = 0, out_cap = 0;
 	const IdxView ix = view_of(h);
-	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
 	if (nv > 0) { // count: the length of every walk and the row it ends at
-		HIPCHK(dalloc(&d_rows, (size_t)nv * 8));
-		HIPCHK(dalloc(&d_len, (size_t)nv * 8));
-		HIPCHK(dalloc(&d_end, (size_t)nv * 8));
-		HIPCHK(dalloc(&d_len32, (size_t)(nv + 1) * 4));
-		HIPCHK(dalloc(&d_off, (size_t)(nv + 1) * 8));
-		HIPCHK(dalloc(&d_ctr, 64));
-		HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 64, hipHostMallocDefault));
-		HIPCHK(hipEventCreate(&ws.e0));
-		HIPCHK(hipEventCreate(&ws.e1));
+		HIPCHK(sc.dev(&d_rows, (size_t)nv * 8));
+		HIPCHK(sc.dev(&d_len, (size_t)nv * 8));
+		HIPCHK(sc.dev(&d_end, (size_t)nv * 8));
+		HIPCHK(sc.dev(&d_len32, (size_t)(nv + 1) * 4));
+		HIPCHK(sc.dev(&d_off, (size_t)(nv + 1) * 8));
+		HIPCHK(sc.dev(&d_ctr, 64));
+		HIPCHK(sc.pinned(&h_ctr, 64));
+		HIPCHK(sc.event(&e0));
+		HIPCHK(sc.event(&e1));
 		{
 			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, nv + 1, h->st);
 			if (r < 0) return scan_err(r);
-			HIPCHK(dalloc(&d_tmp, tmp_bytes + 256));
+			HIPCHK(sc.dev(&d_tmp, tmp_bytes + 256));
 		}
 		HIPCHK(hipMemcpyAsync(d_rows, vrow.data(), (size_t)nv * 8, hipMemcpyHostToDevice, h->st));
 		HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 		HIPCHK(hipMemsetAsync(d_len32, 0, (size_t)(nv + 1) * 4, h->st));
 		const int64_t nb = std::min<int64_t>((nv * 8 + 255) / 256, 4096);
-		HIPCHK(hipEventRecord(ws.e0, h->st));
+		HIPCHK(hipEventRecord(e0, h->st));
 		hipLaunchKernelGGL(k_get_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, (int64_t)0, nv, d_len, d_end, d_len32, (const int64_t*)nullptr, (uint8_t*)nullptr, (int64_t)0, d_ctr);
-		HIPCHK(hipEventRecord(ws.e1, h->st));
+		HIPCHK(hipEventRecord(e1, h->st));
 		std::vector<int64_t> vlen((size_t)nv), vend((size_t)nv);
 		HIPCHK(hipMemcpyAsync(vlen.data(), d_len, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(vend.data(), d_end, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
-		ms_count = ev_ms(ws.e0, ws.e1);
-		if (ws.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a walk that did not end: not an index
+		ms_count = ev_ms(e0, e1);
+		if (h_ctr[2] != 0) return RB3GPU_EINTERNAL; // a walk that did not end: not an index
 		for (int64_t v = 0; v < nv; ++v) {
 			if (vlen[(size_t)v] < 0 || vlen[(size_t)v] >= h->n || vend[(size_t)v] < 0 || vend[(size_t)v] >= h->n) return RB3GPU_EINTERNAL;
 			if (vlen[(size_t)v] > 0xFFFFFFFFLL) return RB3GPU_EUNSUP; // (the scan of a slice adds 32-bit lengths)
@@ -5841,37 +5742,34 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 		for (int64_t i = i0; i < i1; ++i) off[(size_t)(i - i0 + 1)] = off[(size_t)(i - i0)] + len[(size_t)i];
 		if (tot > 0) {
 			if (tot > out_cap) { // (grows to the largest slice: the budget, or the one row that exceeds it)
-				if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
-				if (d_out) { for (void *&p : ws.dv) if (p == d_out) p = nullptr; HIPCHK(hipFree(d_out)); d_out = nullptr; }
 				out_cap = 0;
 				const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 20));
-				HIPCHK(dalloc(&d_out, (size_t)oc + 64));
-				HIPCHK(hipHostMalloc(&ws.h_out, (size_t)oc + 64, hipHostMallocDefault));
+				HIPCHK(sc.regrow(&d_out, &h_out, (size_t)oc + 64));
 				out_cap = oc;
 			}
 			size_t tb = tmp_bytes + 256;
 			const int r = rb3kount_scan(d_tmp, &tb, d_len32 + v0, d_off, v1 - v0 + 1, h->st); // (d_len32[nv] = 0: the entry behind the last row)
 			if (r < 0) return scan_err(r);
 			HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
-			HIPCHK(hipMemcpyAsync(ws.h_ctr + 4, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(h_ctr + 4, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
 			const int64_t nb = std::min<int64_t>(((v1 - v0) * 8 + 255) / 256, 4096);
-			HIPCHK(hipEventRecord(ws.e0, h->st));
+			HIPCHK(hipEventRecord(e0, h->st));
 			hipLaunchKernelGGL(k_get_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, v0, v1, d_len, d_end, d_len32, (const int64_t*)d_off, d_out, tot, d_ctr);
-			HIPCHK(hipEventRecord(ws.e1, h->st));
-			HIPCHK(hipMemcpyAsync(ws.h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
-			HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipEventRecord(e1, h->st));
+			HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
 			HIPCHK(hipStreamSynchronize(h->st));
 			HIPCHK(hipGetLastError());
-			ms_emit += ev_ms(ws.e0, ws.e1);
-			if ((int64_t)ws.h_ctr[4] != tot || ws.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // the scan on the device and the sum on the host are of the same lengths
+			ms_emit += ev_ms(e0, e1);
+			if ((int64_t)h_ctr[4] != tot || h_ctr[2] != 0) return RB3GPU_EINTERNAL; // the scan on the device and the sum on the host are of the same lengths
 		}
 		n_sym += tot;
-		ret = cb(ud, i0, i1 - i0, end.data() + i0, off.data(), (const uint8_t*)ws.h_out);
+		ret = cb(ud, i0, i1 - i0, end.data() + i0, off.data(), h_out);
 		i0 = i1, v0 = v1;
 	}
 	if (st) {
 		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = ms_count, st->ms_emit = ms_emit, st->n_rows = n, st->n_symbols = n_sym, st->n_slices = n_slices;
-		st->n_steps = ws.h_ctr ? (int64_t)ws.h_ctr[1] : 0;
+		st->n_steps = h_ctr ? (int64_t)h_ctr[1] : 0;
 	}
 	return ret;
 }
@@ -5879,11 +5777,6 @@ int rb3gpu_retrieve(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve
 /* `get` in pieces (rb3gpu_walk.h): the whole index walked once in pieces of about 2^S steps, all at the same time; the pieces joined by pointer
  * jumping and sorted by (string, distance from its start) once per call; then every slice of rows written by all of its pieces side by side */
 #define RB3_GET_PIECE 8                       // log2 of the splitter spacing (not measured: DESIGN.md 7k)
-
-struct PieceEv {
-	hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-	~PieceEv() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_retrieve_cb cb, void *ud, rb3gpu_pieces_stats_t *st)
 {
@@ -5908,8 +5801,10 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 	const int64_t nv = (int64_t)vrow.size();
 	std::vector<int64_t> len((size_t)n, 0), end((size_t)n, -1), off;
 	const int64_t budget = h->tn.get_slice > 0 ? h->tn.get_slice : RB3_GET_SLICE;
-	WalkWs ws;
-	PieceEv ev;
+	Scratch sc;
+	hipEvent_t ev[6] = {};
+	uint8_t *h_out = nullptr;
+	unsigned long long *h_ctr = nullptr;
 	double ms_pieces = 0, ms_join = 0, ms_sort = 0, ms_emit = 0;
 	int64_t n_sym = 0, n_slices = 0, out_cap = 0, n_steps = 0, max_piece = 0;
 	if (nv > 0) {
@@ -5923,31 +5818,30 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 		int kbits = 1;
 		while (((int64_t)1 << kbits) < m) ++kbits;
 		const IdxView ix = view_of(h);
-		auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
 		// the tables: two link words twice and two piece ids per piece (the keys of the sort take the place of the link table the join leaves free), 8 bytes per string
-		HIPCHK(dalloc(&d_lnk[0], (size_t)nsp * 16));
-		HIPCHK(dalloc(&d_lnk[1], (size_t)nsp * 16));
-		HIPCHK(dalloc(&d_val[0], (size_t)nsp * 4));
-		HIPCHK(dalloc(&d_val[1], (size_t)nsp * 4));
-		HIPCHK(dalloc(&d_endrow, (size_t)m * 8));
-		HIPCHK(dalloc(&d_rq, (size_t)nv * 16));
-		HIPCHK(dalloc(&d_rows, (size_t)nv * 8));
-		HIPCHK(dalloc(&d_len, (size_t)nv * 8));
-		HIPCHK(dalloc(&d_end, (size_t)nv * 8));
-		HIPCHK(dalloc(&d_len32, (size_t)(nv + 1) * 4));
-		HIPCHK(dalloc(&d_cnt32, (size_t)(nv + 1) * 4));
-		HIPCHK(dalloc(&d_first, (size_t)nv * 4));
-		HIPCHK(dalloc(&d_off, (size_t)(nv + 1) * 8));
-		HIPCHK(dalloc(&d_ioff, (size_t)(nv + 1) * 8));
-		HIPCHK(dalloc(&d_ctr, 64));
-		HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 128, hipHostMallocDefault));
-		for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+		HIPCHK(sc.dev(&d_lnk[0], (size_t)nsp * 16));
+		HIPCHK(sc.dev(&d_lnk[1], (size_t)nsp * 16));
+		HIPCHK(sc.dev(&d_val[0], (size_t)nsp * 4));
+		HIPCHK(sc.dev(&d_val[1], (size_t)nsp * 4));
+		HIPCHK(sc.dev(&d_endrow, (size_t)m * 8));
+		HIPCHK(sc.dev(&d_rq, (size_t)nv * 16));
+		HIPCHK(sc.dev(&d_rows, (size_t)nv * 8));
+		HIPCHK(sc.dev(&d_len, (size_t)nv * 8));
+		HIPCHK(sc.dev(&d_end, (size_t)nv * 8));
+		HIPCHK(sc.dev(&d_len32, (size_t)(nv + 1) * 4));
+		HIPCHK(sc.dev(&d_cnt32, (size_t)(nv + 1) * 4));
+		HIPCHK(sc.dev(&d_first, (size_t)nv * 4));
+		HIPCHK(sc.dev(&d_off, (size_t)(nv + 1) * 8));
+		HIPCHK(sc.dev(&d_ioff, (size_t)(nv + 1) * 8));
+		HIPCHK(sc.dev(&d_ctr, 64));
+		HIPCHK(sc.pinned(&h_ctr, 128));
+		for (hipEvent_t &x : ev) HIPCHK(sc.event(&x));
 		{
 			int r = rb3kount_scan(nullptr, &scan_bytes, nullptr, nullptr, nv + 1, h->st);
 			if (r < 0) return scan_err(r);
 			r = rb3kount_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, nsp, 32 + kbits, h->st);
 			if (r < 0) return scan_err(r);
-			HIPCHK(dalloc(&d_tmp, std::max(scan_bytes, sort_bytes) + 256));
+			HIPCHK(sc.dev(&d_tmp, std::max(scan_bytes, sort_bytes) + 256));
 		}
 		HIPCHK(hipMemcpyAsync(d_rows, vrow.data(), (size_t)nv * 8, hipMemcpyHostToDevice, h->st));
 		HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
@@ -5958,12 +5852,12 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 		pv.S = S, pv.nsp = nsp, pv.lnk = d_lnk[0], pv.rq = d_rq, pv.endrow = d_endrow, pv.rows = d_rows, pv.ioff = d_ioff, pv.off = d_off;
 		pv.first = d_first, pv.len32 = d_len32, pv.sorted = d_val[1];
 		// 1. the pieces, and the rows asked for down to the first splitter
-		HIPCHK(hipEventRecord(ev.e[0], h->st));
+		HIPCHK(hipEventRecord(ev[0], h->st));
 		{
 			const int64_t nb = std::min<int64_t>(((nsp + nv) * 8 + 255) / 256, 4096);
 			hipLaunchKernelGGL(k_piece_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, pv, (int64_t)0, nv, (uint8_t*)nullptr, (int64_t)0, d_ctr);
 		}
-		HIPCHK(hipEventRecord(ev.e[1], h->st));
+		HIPCHK(hipEventRecord(ev[1], h->st));
 		// 2. the join: after it every piece holds (RB3_SSA_END | its string, D)
 		int cur = 0, rounds = 1;
 		while (((int64_t)1 << (rounds - 1)) < nsp) ++rounds; // ceil(log2 nsp) + 1
@@ -5971,7 +5865,7 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 			hipLaunchKernelGGL(k_ssa_jump, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, (const uint64_t*)d_lnk[cur], (uint64_t*)d_lnk[cur ^ 1]);
 		uint64_t *d_key[2] = { (uint64_t*)d_lnk[cur ^ 1], (uint64_t*)d_lnk[cur ^ 1] + nsp };
 		hipLaunchKernelGGL(k_piece_key, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, m, (const ulonglong2*)d_lnk[cur], d_key[0], d_val[0], d_ctr + 4);
-		HIPCHK(hipEventRecord(ev.e[2], h->st));
+		HIPCHK(hipEventRecord(ev[2], h->st));
 		// 3. the order of the pieces, its inverse, and every row's lengths and range
 		{
 			size_t tb = sort_bytes;
@@ -5981,23 +5875,23 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 		hipLaunchKernelGGL(k_piece_inverse, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, (const uint32_t*)d_val[1], d_val[0]);
 		hipLaunchKernelGGL(k_piece_resolve, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, h->st, nv, nsp, m, (const ulonglong2*)d_lnk[cur], (const ulonglong2*)d_rq, (const int64_t*)d_endrow,
 				(const uint64_t*)d_key[1], (const uint32_t*)d_val[0], d_len, d_end, d_len32, d_cnt32, d_first, d_ctr + 4);
-		HIPCHK(hipEventRecord(ev.e[3], h->st));
+		HIPCHK(hipEventRecord(ev[3], h->st));
 		pv.lnk = d_lnk[cur];
 		std::vector<int64_t> vlen((size_t)nv), vend((size_t)nv);
 		std::vector<uint32_t> vcnt((size_t)nv);
 		HIPCHK(hipMemcpyAsync(vlen.data(), d_len, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(vend.data(), d_end, (size_t)nv * 8, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipMemcpyAsync(vcnt.data(), d_cnt32, (size_t)nv * 4, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 64, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 64, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
-		ms_pieces = ev_ms(ev.e[0], ev.e[1]), ms_join = ev_ms(ev.e[1], ev.e[2]), ms_sort = ev_ms(ev.e[2], ev.e[3]);
-		n_steps = (int64_t)ws.h_ctr[1], max_piece = (int64_t)ws.h_ctr[3];
-		if (ws.h_ctr[2] != 0 || ws.h_ctr[4] != 0) { // a piece that met no splitter, a chain that ends in no string: not an index
-			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] get: %llu pieces too long, %llu broken links\n", ws.h_ctr[2], ws.h_ctr[4]);
+		ms_pieces = ev_ms(ev[0], ev[1]), ms_join = ev_ms(ev[1], ev[2]), ms_sort = ev_ms(ev[2], ev[3]);
+		n_steps = (int64_t)h_ctr[1], max_piece = (int64_t)h_ctr[3];
+		if (h_ctr[2] != 0 || h_ctr[4] != 0) { // a piece that met no splitter, a chain that ends in no string: not an index
+			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] get: %llu pieces too long, %llu broken links\n", h_ctr[2], h_ctr[4]);
 			return RB3GPU_EINTERNAL;
 		}
-		if (ws.h_ctr[5] != 0) return RB3GPU_EUNSUP; // a string of 2^32 symbols or more
+		if (h_ctr[5] != 0) return RB3GPU_EUNSUP; // a string of 2^32 symbols or more
 		for (int64_t v = 0; v < nv; ++v) {
 			if (vlen[(size_t)v] < 0 || vlen[(size_t)v] >= h->n || vend[(size_t)v] < 0 || vend[(size_t)v] >= h->n || vcnt[(size_t)v] == 0) return RB3GPU_EINTERNAL;
 			len[(size_t)vat[(size_t)v]] = vlen[(size_t)v], end[(size_t)vat[(size_t)v]] = vend[(size_t)v];
@@ -6013,12 +5907,9 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 			for (int64_t i = i0; i < i1; ++i) off[(size_t)(i - i0 + 1)] = off[(size_t)(i - i0)] + len[(size_t)i];
 			if (tot > 0) {
 				if (tot > out_cap) { // (grows to the largest slice: the budget, or the one row that exceeds it)
-					if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
-					if (d_out) { for (void *&p : ws.dv) if (p == d_out) p = nullptr; HIPCHK(hipFree(d_out)); d_out = nullptr; }
 					out_cap = 0;
 					const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 20));
-					HIPCHK(dalloc(&d_out, (size_t)oc + 64));
-					HIPCHK(hipHostMalloc(&ws.h_out, (size_t)oc + 64, hipHostMallocDefault));
+					HIPCHK(sc.regrow(&d_out, &h_out, (size_t)oc + 64));
 					out_cap = oc;
 				}
 				size_t tb = scan_bytes + 256;
@@ -6028,22 +5919,22 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 				r = rb3kount_scan(d_tmp, &tb, d_cnt32 + v0, d_ioff, v1 - v0 + 1, h->st);
 				if (r < 0) return scan_err(r);
 				HIPCHK(hipMemsetAsync(d_ctr, 0, 24, h->st));
-				HIPCHK(hipMemcpyAsync(ws.h_ctr + 8, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
-				HIPCHK(hipMemcpyAsync(ws.h_ctr + 9, d_ioff + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipMemcpyAsync(h_ctr + 8, d_off + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipMemcpyAsync(h_ctr + 9, d_ioff + (v1 - v0), 8, hipMemcpyDeviceToHost, h->st));
 				const int64_t nb = std::min<int64_t>((items * 8 + 255) / 256, 4096);
-				HIPCHK(hipEventRecord(ev.e[4], h->st));
+				HIPCHK(hipEventRecord(ev[4], h->st));
 				hipLaunchKernelGGL(k_piece_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, pv, v0, v1 - v0, d_out, tot, d_ctr);
-				HIPCHK(hipEventRecord(ev.e[5], h->st));
-				HIPCHK(hipMemcpyAsync(ws.h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
-				HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipEventRecord(ev[5], h->st));
+				HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+				HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 24, hipMemcpyDeviceToHost, h->st));
 				HIPCHK(hipStreamSynchronize(h->st));
 				HIPCHK(hipGetLastError());
-				ms_emit += ev_ms(ev.e[4], ev.e[5]);
-				n_steps += (int64_t)ws.h_ctr[1];
-				if ((int64_t)ws.h_ctr[8] != tot || (int64_t)ws.h_ctr[9] != items || ws.h_ctr[2] != 0) return RB3GPU_EINTERNAL; // the scans on the device and the sums on the host are of the same numbers
+				ms_emit += ev_ms(ev[4], ev[5]);
+				n_steps += (int64_t)h_ctr[1];
+				if ((int64_t)h_ctr[8] != tot || (int64_t)h_ctr[9] != items || h_ctr[2] != 0) return RB3GPU_EINTERNAL; // the scans on the device and the sums on the host are of the same numbers
 			}
 			n_sym += tot;
-			ret = cb(ud, i0, i1 - i0, end.data() + i0, off.data(), (const uint8_t*)ws.h_out);
+			ret = cb(ud, i0, i1 - i0, end.data() + i0, off.data(), h_out);
 			i0 = i1, v0 = v1;
 		}
 		if (st) {
@@ -6072,17 +5963,16 @@ static int fetch_table(rb3gpu_t *h, double *ms)
 	int obits = 1, r;
 	while (obits < 63 && ((int64_t)1 << obits) < h->n) ++obits; // (an offset is below the number of rows)
 	if (obits + h->ssa_ms > 64) return RB3GPU_EUNSUP;
-	WalkWs ws;
+	Scratch sc;
 	uint64_t *d_key[2] = { nullptr, nullptr };
 	uint32_t *d_val = nullptr, *d_tab = nullptr;
 	void *d_tmp = nullptr;
 	size_t sort_bytes = 0;
-	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
-	HIPCHK(dalloc(&d_key[0], (size_t)ns * 8));
-	HIPCHK(dalloc(&d_key[1], (size_t)ns * 8));
-	HIPCHK(dalloc(&d_val, (size_t)ns * 4));
+	HIPCHK(sc.dev(&d_key[0], (size_t)ns * 8));
+	HIPCHK(sc.dev(&d_key[1], (size_t)ns * 8));
+	HIPCHK(sc.dev(&d_val, (size_t)ns * 4));
 	if ((r = rb3kount_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, ns, obits + h->ssa_ms, h->st)) < 0) return scan_err(r);
-	HIPCHK(dalloc(&d_tmp, sort_bytes + 256));
+	HIPCHK(sc.dev(&d_tmp, sort_bytes + 256));
 	if ((r = dev_malloc(h, (void**)&d_tab, (size_t)ns * 4)) < 0) return r;
 	HIPCHK(hipEventRecord(h->ev[0], h->st));
 	hipLaunchKernelGGL(k_fetch_key, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->st, ns, h->ssa_ms, obits, (const uint64_t*)(h->ssa_dev + h->ssa_m), d_key[0], d_val);
@@ -6115,32 +6005,31 @@ int rb3gpu_fetch(rb3gpu_t *h, int64_t n, const rb3gpu_region_t *reg, int64_t *ba
 	if (const int e = fetch_table(h, &ms_table)) return e;
 	const int64_t m = h->acc[1], budget = h->tn.fetch_slice > 0 ? h->tn.fetch_slice : RB3_FETCH_SLICE;
 	const IdxView ix = view_of(h);
-	WalkWs ws;
-	PieceEv ev;
+	Scratch sc;
+	hipEvent_t ev[6] = {};
 	FetchRegion *d_reg = nullptr;
 	int64_t *d_ak = nullptr, *d_ao = nullptr, *d_mlist = nullptr, *d_ioff = nullptr, *d_off = nullptr;
 	uint32_t *d_first = nullptr, *d_cnt32 = nullptr;
-	uint8_t *d_out = nullptr;
-	unsigned long long *d_ctr = nullptr;
+	uint8_t *d_out = nullptr, *h_out = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
 	void *d_tmp = nullptr;
 	size_t scan_bytes = 0;
 	static_assert(sizeof(FetchRegion) == sizeof(rb3gpu_region_t), "the regions go to the device as they come");
-	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
-	HIPCHK(dalloc(&d_reg, (size_t)n * sizeof(FetchRegion)));
-	HIPCHK(dalloc(&d_ak, (size_t)n * 8));
-	HIPCHK(dalloc(&d_ao, (size_t)n * 8));
-	HIPCHK(dalloc(&d_mlist, (size_t)n * 8));
-	HIPCHK(dalloc(&d_ioff, (size_t)(n + 1) * 8));
-	HIPCHK(dalloc(&d_off, (size_t)(n + 1) * 8));
-	HIPCHK(dalloc(&d_first, (size_t)n * 4));
-	HIPCHK(dalloc(&d_cnt32, (size_t)(n + 1) * 4));
-	HIPCHK(dalloc(&d_ctr, 64));
-	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 128, hipHostMallocDefault));
-	for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+	HIPCHK(sc.dev(&d_reg, (size_t)n * sizeof(FetchRegion)));
+	HIPCHK(sc.dev(&d_ak, (size_t)n * 8));
+	HIPCHK(sc.dev(&d_ao, (size_t)n * 8));
+	HIPCHK(sc.dev(&d_mlist, (size_t)n * 8));
+	HIPCHK(sc.dev(&d_ioff, (size_t)(n + 1) * 8));
+	HIPCHK(sc.dev(&d_off, (size_t)(n + 1) * 8));
+	HIPCHK(sc.dev(&d_first, (size_t)n * 4));
+	HIPCHK(sc.dev(&d_cnt32, (size_t)(n + 1) * 4));
+	HIPCHK(sc.dev(&d_ctr, 64));
+	HIPCHK(sc.pinned(&h_ctr, 128));
+	for (hipEvent_t &x : ev) HIPCHK(sc.event(&x));
 	{
 		const int r = rb3kount_scan(nullptr, &scan_bytes, nullptr, nullptr, n + 1, h->st);
 		if (r < 0) return scan_err(r);
-		HIPCHK(dalloc(&d_tmp, scan_bytes + 256));
+		HIPCHK(sc.dev(&d_tmp, scan_bytes + 256));
 	}
 	FetchView fv;
 	fv.ss = h->ssa_ss, fv.ms = h->ssa_ms, fv.n_ssa = h->ssa_n, fv.ssa = h->ssa_dev + h->ssa_m, fv.tab = h->ssa_tab, fv.reg = d_reg, fv.ak = d_ak, fv.ao = d_ao;
@@ -6150,28 +6039,28 @@ int rb3gpu_fetch(rb3gpu_t *h, int64_t n, const rb3gpu_region_t *reg, int64_t *ba
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 64, h->st));
 	HIPCHK(hipMemsetAsync(d_ctr + 5, 0xff, 8, h->st));
 	HIPCHK(hipMemsetAsync(d_cnt32 + n, 0, 4, h->st)); // (the entry behind the last region, for the scan)
-	HIPCHK(hipEventRecord(ev.e[0], h->st));
+	HIPCHK(hipEventRecord(ev[0], h->st));
 	hipLaunchKernelGGL(k_fetch_plan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, fv, n, m, d_ctr);
 	{
 		const int64_t nb = std::min<int64_t>((n * 8 + 255) / 256, 4096);
 		hipLaunchKernelGGL(k_fetch_len, dim3((unsigned)nb), dim3(256), 0, h->st, ix, fv, d_ctr);
 	}
-	HIPCHK(hipEventRecord(ev.e[1], h->st));
+	HIPCHK(hipEventRecord(ev[1], h->st));
 	std::vector<uint32_t> vcnt((size_t)n);
 	HIPCHK(hipMemcpyAsync(vcnt.data(), d_cnt32, (size_t)n * 4, hipMemcpyDeviceToHost, h->st));
-	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 64, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 64, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
 	HIPCHK(hipGetLastError());
-	const double ms_plan = ev_ms(ev.e[0], ev.e[1]);
-	const int64_t n_measured = (int64_t)ws.h_ctr[4];
-	int64_t n_steps = (int64_t)ws.h_ctr[1], n_walkers = 0, n_sym = 0, n_slices = 0, max_walk = 0, out_cap = 0;
+	const double ms_plan = ev_ms(ev[0], ev[1]);
+	const int64_t n_measured = (int64_t)h_ctr[4];
+	int64_t n_steps = (int64_t)h_ctr[1], n_walkers = 0, n_sym = 0, n_slices = 0, max_walk = 0, out_cap = 0;
 	double ms_walk = 0;
-	if (ws.h_ctr[2] != 0) { // a sample of another string on the way from a sentinel's row: not the sampled suffix array of this index
-		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] fetch: %llu strings measured through samples that are not theirs\n", ws.h_ctr[2]);
+	if (h_ctr[2] != 0) { // a sample of another string on the way from a sentinel's row: not the sampled suffix array of this index
+		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] fetch: %llu strings measured through samples that are not theirs\n", h_ctr[2]);
 		return RB3GPU_EINTERNAL;
 	}
-	if (ws.h_ctr[5] != ~0ull) { // an invalid region: the first one
-		if (bad) *bad = (int64_t)ws.h_ctr[5];
+	if (h_ctr[5] != ~0ull) { // an invalid region: the first one
+		if (bad) *bad = (int64_t)h_ctr[5];
 		return RB3GPU_EINVAL;
 	}
 	// 2. slices of consecutive regions whose lengths sum to at most the budget, a longer region alone
@@ -6183,12 +6072,9 @@ int rb3gpu_fetch(rb3gpu_t *h, int64_t n, const rb3gpu_region_t *reg, int64_t *ba
 		off.assign((size_t)(i1 - i0 + 1), 0);
 		for (int64_t i = i0; i < i1; ++i) off[(size_t)(i - i0 + 1)] = off[(size_t)(i - i0)] + (reg[i].end - reg[i].beg);
 		if (tot > out_cap) { // (grows to the largest slice: the budget, or the one region that exceeds it)
-			if (ws.h_out) { HIPCHK(hipHostFree(ws.h_out)); ws.h_out = nullptr; }
-			if (d_out) { for (void *&p : ws.dv) if (p == d_out) p = nullptr; HIPCHK(hipFree(d_out)); d_out = nullptr; }
 			out_cap = 0;
 			const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 20));
-			HIPCHK(dalloc(&d_out, (size_t)oc + 64));
-			HIPCHK(hipHostMalloc(&ws.h_out, (size_t)oc + 64, hipHostMallocDefault));
+			HIPCHK(sc.regrow(&d_out, &h_out, (size_t)oc + 64));
 			out_cap = oc;
 		}
 		size_t tb = scan_bytes + 256;
@@ -6196,23 +6082,23 @@ int rb3gpu_fetch(rb3gpu_t *h, int64_t n, const rb3gpu_region_t *reg, int64_t *ba
 		if (r < 0) return scan_err(r);
 		HIPCHK(hipMemcpyAsync(d_off, off.data(), (size_t)(i1 - i0 + 1) * 8, hipMemcpyHostToDevice, h->st));
 		HIPCHK(hipMemsetAsync(d_ctr, 0, 32, h->st));
-		HIPCHK(hipMemcpyAsync(ws.h_ctr + 9, d_ioff + (i1 - i0), 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr + 9, d_ioff + (i1 - i0), 8, hipMemcpyDeviceToHost, h->st));
 		const int64_t nb = std::min<int64_t>((items * 8 + 255) / 256, 4096);
-		HIPCHK(hipEventRecord(ev.e[4], h->st));
+		HIPCHK(hipEventRecord(ev[4], h->st));
 		hipLaunchKernelGGL(k_fetch_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, fv, i0, i1 - i0, d_out, tot, d_ctr);
-		HIPCHK(hipEventRecord(ev.e[5], h->st));
-		HIPCHK(hipMemcpyAsync(ws.h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 32, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipEventRecord(ev[5], h->st));
+		HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 32, hipMemcpyDeviceToHost, h->st));
 		HIPCHK(hipStreamSynchronize(h->st));
 		HIPCHK(hipGetLastError());
-		ms_walk += ev_ms(ev.e[4], ev.e[5]);
-		n_steps += (int64_t)ws.h_ctr[1], n_walkers += items, n_sym += tot, max_walk = std::max(max_walk, (int64_t)ws.h_ctr[3]);
-		if ((int64_t)ws.h_ctr[9] != items) return RB3GPU_EINTERNAL; // the scan on the device and the sum on the host are of the same numbers
-		if (ws.h_ctr[2] != 0) { // a walker met a sample that is not (its string, its offset), or the start of its string above beg
-			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] fetch: %llu walkers met rows the sampled suffix array does not describe\n", ws.h_ctr[2]);
+		ms_walk += ev_ms(ev[4], ev[5]);
+		n_steps += (int64_t)h_ctr[1], n_walkers += items, n_sym += tot, max_walk = std::max(max_walk, (int64_t)h_ctr[3]);
+		if ((int64_t)h_ctr[9] != items) return RB3GPU_EINTERNAL; // the scan on the device and the sum on the host are of the same numbers
+		if (h_ctr[2] != 0) { // a walker met a sample that is not (its string, its offset), or the start of its string above beg
+			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] fetch: %llu walkers met rows the sampled suffix array does not describe\n", h_ctr[2]);
 			return RB3GPU_EINTERNAL;
 		}
-		ret = cb(ud, i0, i1 - i0, off.data(), (const uint8_t*)ws.h_out);
+		ret = cb(ud, i0, i1 - i0, off.data(), h_out);
 		i0 = i1;
 	}
 	if (st) {
@@ -6272,32 +6158,31 @@ int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gp
 	if (const int e = drv_enter(h, &t0)) return e;
 	const int64_t ngo = (n_old + RB3_GRP - 1) >> RB3_GRP_BITS; // groups of the bitmap: all of them whole
 	const IdxView ix = view_of(h);
-	WalkWs ws;
-	PieceEv ev;
+	Scratch sc;
+	hipEvent_t ev[6] = {};
 	uint32_t *d_bm = nullptr, *d_cnt = nullptr;
 	int64_t *d_pre = nullptr, *d_rows = nullptr;
-	unsigned long long *d_ctr = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
 	void *d_tmp = nullptr;
 	size_t scan_bytes = 0;
-	auto dalloc = [&](void *pp, size_t bytes) { void *p = nullptr; const hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) ws.dv.push_back(p), *(void**)pp = p; return e; };
-	HIPCHK(dalloc(&d_bm, (size_t)ngo * RB3_RM_WORDS * 4));
-	HIPCHK(dalloc(&d_cnt, (size_t)(ngo + 1) * 4));
-	HIPCHK(dalloc(&d_pre, (size_t)(ngo + 1) * 8));
-	HIPCHK(dalloc(&d_rows, (size_t)nd * 8));
-	HIPCHK(dalloc(&d_ctr, 256)); // [0, 8): the pieces' walk, [8, 16): the marking walk, [16, 24): the flags, [24, 32): the letters
-	HIPCHK(hipHostMalloc((void**)&ws.h_ctr, 256, hipHostMallocDefault));
-	for (hipEvent_t &x : ev.e) HIPCHK(hipEventCreate(&x));
+	HIPCHK(sc.dev(&d_bm, (size_t)ngo * RB3_RM_WORDS * 4));
+	HIPCHK(sc.dev(&d_cnt, (size_t)(ngo + 1) * 4));
+	HIPCHK(sc.dev(&d_pre, (size_t)(ngo + 1) * 8));
+	HIPCHK(sc.dev(&d_rows, (size_t)nd * 8));
+	HIPCHK(sc.dev(&d_ctr, 256)); // [0, 8): the pieces' walk, [8, 16): the marking walk, [16, 24): the flags, [24, 32): the letters
+	HIPCHK(sc.pinned(&h_ctr, 256));
+	for (hipEvent_t &x : ev) HIPCHK(sc.event(&x));
 	{
 		const int r = rb3kount_scan(nullptr, &scan_bytes, nullptr, nullptr, ngo + 1, h->st);
 		if (r < 0) return scan_err(r);
-		HIPCHK(dalloc(&d_tmp, scan_bytes + 256));
+		HIPCHK(sc.dev(&d_tmp, scan_bytes + 256));
 	}
 	HIPCHK(hipMemsetAsync(d_bm, 0, (size_t)ngo * RB3_RM_WORDS * 4, h->st));
 	HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(ngo + 1) * 4, h->st)); // (entry ngo stays 0: the scan's entry behind the last group is the total)
 	HIPCHK(hipMemsetAsync(d_ctr, 0, 256, h->st));
 	HIPCHK(hipMemcpyAsync(d_rows, vr.data(), (size_t)nd * 8, hipMemcpyHostToDevice, h->st));
 	// 1. mark
-	HIPCHK(hipEventRecord(ev.e[0], h->st));
+	HIPCHK(hipEventRecord(ev[0], h->st));
 	if (!pieces) {
 		const int64_t nb = std::min<int64_t>((nd * 8 + 255) / 256, 4096);
 		hipLaunchKernelGGL(k_mark_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, nd, d_bm, d_ctr + 8);
@@ -6305,26 +6190,26 @@ int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gp
 		ulonglong2 *d_lnk[2] = { nullptr, nullptr };
 		int64_t *d_endrow = nullptr;
 		uint8_t *d_flag = nullptr;
-		HIPCHK(dalloc(&d_lnk[0], (size_t)nsp * 16));
-		HIPCHK(dalloc(&d_lnk[1], (size_t)nsp * 16));
-		HIPCHK(dalloc(&d_endrow, (size_t)m * 8));
-		HIPCHK(dalloc(&d_flag, (size_t)m));
+		HIPCHK(sc.dev(&d_lnk[0], (size_t)nsp * 16));
+		HIPCHK(sc.dev(&d_lnk[1], (size_t)nsp * 16));
+		HIPCHK(sc.dev(&d_endrow, (size_t)m * 8));
+		HIPCHK(sc.dev(&d_flag, (size_t)m));
 		HIPCHK(hipMemsetAsync(d_flag, 0, (size_t)m, h->st));
 		PieceView pv;
 		memset(&pv, 0, sizeof(pv));
 		pv.S = S, pv.nsp = nsp, pv.lnk = d_lnk[0], pv.endrow = d_endrow;
 		const int64_t nb = std::min<int64_t>((nsp * 8 + 255) / 256, 4096);
 		hipLaunchKernelGGL(k_piece_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, pv, (int64_t)0, (int64_t)0, (uint8_t*)nullptr, (int64_t)0, d_ctr); // (no rows: a string's row is a splitter's)
-		HIPCHK(hipEventRecord(ev.e[2], h->st));
+		HIPCHK(hipEventRecord(ev[2], h->st));
 		int cur = 0, rounds = 1;
 		while (((int64_t)1 << (rounds - 1)) < nsp) ++rounds; // ceil(log2 nsp) + 1
 		for (int r = 0; r < rounds; ++r, cur ^= 1)
 			hipLaunchKernelGGL(k_ssa_jump, dim3((unsigned)((nsp + 255) / 256)), dim3(256), 0, h->st, nsp, (const uint64_t*)d_lnk[cur], (uint64_t*)d_lnk[cur ^ 1]);
 		hipLaunchKernelGGL(k_mark_flag, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->st, nd, (const int64_t*)d_rows, m, (const ulonglong2*)d_lnk[cur], d_flag, d_ctr + 16);
-		HIPCHK(hipEventRecord(ev.e[3], h->st));
+		HIPCHK(hipEventRecord(ev[3], h->st));
 		hipLaunchKernelGGL(k_mark_pieces, dim3((unsigned)nb), dim3(256), 0, h->st, ix, S, nsp, (const ulonglong2*)d_lnk[cur], (const uint8_t*)d_flag, d_bm, d_ctr + 8);
 	}
-	HIPCHK(hipEventRecord(ev.e[1], h->st));
+	HIPCHK(hipEventRecord(ev[1], h->st));
 	// 2. the rank of the compaction, and the check: nothing has been destroyed so far
 	hipLaunchKernelGGL(k_mark_count, dim3((unsigned)ngo), dim3(256), 0, h->st, ix, (const uint32_t*)d_bm, d_cnt, d_ctr + 24);
 	{
@@ -6334,15 +6219,15 @@ int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gp
 	}
 	std::vector<int64_t> pre((size_t)ngo + 1);
 	HIPCHK(hipMemcpyAsync(pre.data(), d_pre, (size_t)(ngo + 1) * 8, hipMemcpyDeviceToHost, h->st));
-	HIPCHK(hipMemcpyAsync(ws.h_ctr, d_ctr, 256, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 256, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
 	HIPCHK(hipGetLastError());
-	const unsigned long long *cp = ws.h_ctr, *cm = ws.h_ctr + 8, *cf = ws.h_ctr + 16, *cl = ws.h_ctr + 24;
-	const double ms_mark = ev_ms(ev.e[0], ev.e[1]);
+	const unsigned long long *cp = h_ctr, *cm = h_ctr + 8, *cf = h_ctr + 16, *cl = h_ctr + 24;
+	const double ms_mark = ev_ms(ev[0], ev[1]);
 	if (h->opt.verbose >= 3) {
 		if (pieces)
 			fprintf(stderr, "[M::%s::%.3f] marked %lld rows of %lld strings in pieces: counting walk %.3f ms (%llu steps), join %.3f ms, marking walk %.3f ms (%llu steps)\n", __func__, now_s() - h->t0, (long long)pre[(size_t)ngo],
-					(long long)nd, ev_ms(ev.e[0], ev.e[2]), cp[1], ev_ms(ev.e[2], ev.e[3]), ev_ms(ev.e[3], ev.e[1]), cm[1]);
+					(long long)nd, ev_ms(ev[0], ev[2]), cp[1], ev_ms(ev[2], ev[3]), ev_ms(ev[3], ev[1]), cm[1]);
 		else fprintf(stderr, "[M::%s::%.3f] marked %lld rows of %lld strings: marking walk %.3f ms (%llu steps)\n", __func__, now_s() - h->t0, (long long)pre[(size_t)ngo], (long long)nd, ms_mark, cm[1]);
 	}
 	if (pieces && cf[1] != 0) return RB3GPU_EUNSUP; // a string of 2^32 symbols or more
