@@ -62,7 +62,8 @@ typedef struct {
 	double  ms_sort;             /* rb3gpu_bwt_from_text: upload + suffix sorting + BWT */
 	int64_t n_sort_rounds;       /* prefix-doubling rounds of those calls */
 	int64_t n_reb_groups;        /* groups (8192 symbols) of the merges whose rebuild went through the run-space kernel ... */
-	int64_t n_reb_groups_window; /* ... and how many of them it handed on to the per-window kernels (single-sync merges) */
+	int64_t n_reb_groups_window; /* ... and how many of them it handed on to the symbol path (the plane or per-window kernels); counted by the
+	                                single-sync merges and by rb3gpu_sh_finish */
 	int64_t n_lf_checked;        /* batch rows whose LF relation was verified against the index after the rank phase (approximate) */
 	int64_t n_long_settles;      /* merges whose tentative records needed the pointer-jumping settle pass (paths over > 64 walkers) */
 	double  ms_alloc;            /* host time inside hipMalloc / hipFree for the handle's buffers (they grow with the index; replaced ones are freed in bulk) */
@@ -76,6 +77,8 @@ typedef struct {
 	                                verified after the rank phase: all of them, on every merge with text-order words */
 	int64_t n_peer_rounds;       /* lock-step rounds of the interval-sharded merge that ran as PEER ROUNDS (one kernel per rank, states written straight
 	                                into the owner's receive buffer; rb3gpu_comm_t.stream_barrier): 0 where the host drove the rounds */
+	int64_t n_reb_groups_tier2;  /* groups of n_reb_groups that the small tier of the run-space kernel handed to the medium one (0 for a rebuild that
+	                                starts with the medium tier); n_reb_groups_window of them went on to the symbol path */
 } rb3gpu_stats_t;
 
 void rb3gpu_opt_init(rb3gpu_opt_t *opt);
@@ -711,7 +714,7 @@ int rb3gpu_stream_sync(void *stream);
 
 /* Diagnostic switches of a handle (no reference analogue; none is needed in normal use).  Each key is also read ONCE from
  * the environment variable RB3GPU_<KEY> when the handle is created; the merge path itself never calls getenv().
- *   "tent" 0/1, "staged" 0/1, "group_rebuild" 0/1, "window_rebuild" 0/1, "reb_force" 0/1, "octs" 1..8, "blkmul", "blkcap", "ssa_split" 4..20,
+ *   "tent" 0/1, "staged" 0/1, "group_rebuild" 0/1, "window_rebuild" 0/1, "reb_force" 0/1/-1 (the run-space rebuild always / never), "octs" 1..8, "blkmul", "blkcap", "ssa_split" 4..20,
  *   "lf_check" n (verify the LF relation of every n-th batch row against the index after each merge; default 4096, 0 = off)
  *   "tent_q" 1/2/4/8 (width of the drop-out masks in units of 256 bits; 0 = follows what the walkers report), "trec" 0/1/-1 (records of a
  *   text-order walk in text order: never / always / where the index does not fit the caches), "copy_walkers" 0/1, "b2_split" S (splitter

@@ -141,7 +141,7 @@ struct Tune {
 	int reb_t1_rows = 96;    // the small tier of the run-space rebuild runs first where a group receives at most this many batch rows on average
 	int plane_rebuild = 1;   // symbols are rebuilt in plane space, a lane per 32 symbols (k_plane_group); 0: a wave per window (k_pass1w / k_decide / k_pass2w, rounds 1-3)
 	int resolve_v1 = 0;      // settle the tentative stretches with k_resolve (one hop per stretch) instead of k_cum / k_resolve_w / k_sfin
-	int reb_force = 0;       // the run-space rebuild whatever the row density and the old index look like (tests: the hand-over paths)
+	int reb_force = 0;       // 1: the run-space rebuild whatever the row density and the old index look like (tests: the hand-over paths); -1: never (tests: a run-coded old range in k_plane_group<false>)
 	int octs = 8;            // octets per wave of k_chain
 	int lpw = 8;             // (lanes per walker of k_chain: an octet.  The key is still accepted; the quad variant of rounds 2-5 is gone)
 	int blkmul = 1;          // launch width multiplier of k_chain
@@ -673,7 +673,7 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "reb_t1_rows")) t.reb_t1_rows = (int)v;
 	else if (!strcmp(key, "part")) t.part = (int)v;
 	else if (!strcmp(key, "scan_place")) t.scan_place = v != 0;
-	else if (!strcmp(key, "reb_force")) t.reb_force = v != 0;
+	else if (!strcmp(key, "reb_force")) t.reb_force = v < 0 ? -1 : v != 0;
 	else if (!strcmp(key, "resolve_v1")) t.resolve_v1 = v != 0;
 	else if (!strcmp(key, "octs")) t.octs = v < 1 ? 1 : v > 8 ? 8 : (int)v;
 	else if (!strcmp(key, "lpw")) t.lpw = 8;
@@ -978,8 +978,8 @@ static int scan_records(rb3gpu_t *h, const uint32_t *in, int64_t nrec, uint64_t 
 static bool runspace_applies(const rb3gpu_t *h, int64_t n2, int64_t ntot)
 {
 	const int64_t nwin_old = (h->n >> RB3_WIN_BITS) + 1;
-	if (h->tn.window_rebuild || h->nslots == nwin_old) return false; // (a fully bit-plane index has no run slot to start from)
-	if (h->tn.reb_force) return true;
+	if (h->tn.window_rebuild || h->tn.reb_force < 0 || h->nslots == nwin_old) return false; // (a fully bit-plane index has no run slot to start from)
+	if (h->tn.reb_force > 0) return true;
 	if (h->reb_pp_all && h->tn.plane_rebuild) return false; // (most groups still hold a bit-plane slot: every one of them would be handed on)
 	return h->nslots * 2 < nwin_old && (double)n2 * RB3_GRP <= 4096.0 * (double)ntot; // (run-coded index; not where half of every group is new)
 }
@@ -2343,6 +2343,7 @@ static int merge_core(rb3gpu_t *h, int64_t len, const uint8_t *d_b2, int commit,
 		}
 		if (ran_runspace) { // the run-space rebuild ran: how many groups it handed to the window kernels
 			h->stt.n_reb_groups += ngrp, h->stt.n_reb_groups_window += (int64_t)(hm[MISC_RG_LISTS] >> 32);
+			h->stt.n_reb_groups_tier2 += (int64_t)(hm[MISC_RG_LISTS] & 0xFFFFFFFFull);
 			h->reb_last[0] = (int64_t)(hm[MISC_RG_LISTS] & 0xFFFFFFFFull), h->reb_last[1] = (int64_t)(hm[MISC_RG_LISTS] >> 32); // (the next rebuild sizes its grids by them)
 		} else h->reb_last[0] = h->reb_last[1] = -1;
 		// Which rebuild the next merge starts with: the run-space tiers hand on every group whose old range holds a bit-plane slot
@@ -3936,9 +3937,14 @@ int rb3gpu_sh_finish(rb3gpu_t *h, int64_t jlo, int64_t n_rows, const uint8_t *d_
 		return RB3GPU_EINTERNAL;
 	}
 	int64_t ngrp = 0, nslots = 0, acc[7];
+	const bool ran_runspace = runspace_applies(h, n_rows, ntot) && use_winpar(h, (ntot >> RB3_WIN_BITS) + 1); // (as build_index decides)
 	if ((r = build_index<false>(h, n_rows, d_bwt + jlo, (const int64_t*)dpos, ntot, false, &ngrp, &nslots, acc)) < 0) return r;
 	HIPCHK(hipEventRecord(h->ev[3], h->st));
+	unsigned long long hl = 0; // the lengths of the two hand-over lists of the run-space rebuild
+	if (ran_runspace) HIPCHK(hipMemcpyAsync(&hl, misc + MISC_RG_LISTS, 8, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
+	if (ran_runspace)
+		h->stt.n_reb_groups += ngrp, h->stt.n_reb_groups_window += (int64_t)(hl >> 32), h->stt.n_reb_groups_tier2 += (int64_t)(hl & 0xFFFFFFFFull);
 	h->stt.ms_build += ev_ms(h->ev[2], h->ev[3]);
 	h->stt.n_symbols_merged += n_rows;
 	h->stt.bytes_rebuild += 9 * n_rows + h->stt.bytes_index + ngrp * (int64_t)sizeof(rb3_grp_t) + nslots * (int64_t)sizeof(rb3_slot_t);
