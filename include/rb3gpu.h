@@ -681,6 +681,27 @@ int rb3gpu_retrieve_pieces(rb3gpu_t *h, int64_t n, const int64_t *rows, rb3gpu_r
 typedef struct { double ms_total, ms_mark, ms_build; int64_t n_strings, n_rows, n_steps, n_pieces, max_piece_steps, removed[6]; } rb3gpu_remove_stats_t;
 int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gpu_remove_stats_t *st);
 
+/* which strings of the index are redundant (no counterpart in the reference): exact copies of another string, and strings that lie wholly inside a
+ * longer one.  ALL acc[1] strings are judged.  From row r the LF walk of rb3gpu_retrieve spells string r from its last symbol to its first, and the symbols read
+ * drive two backward searches of rb3gpu_suffix: `any` from all the rows and `suf` from the sentinels' rows.  Where the walk reads the sentinel, rec[r] (may be NULL;
+ * acc[1] records) is occ = |any|, the places string r occurs at anywhere in the index, itself included; cls = the sentinels in front of suf, the same for all copies
+ * of a string and for no other string; copies = the sentinels inside suf, the strings that ARE string r.  A walk whose `any` has come down to one row ends there --
+ * the string is unique -- with (1, 1, -1): a unique read costs about log4(acc[6]) steps, not its length (rb3gpu_tune "dedup_early" 0: every walk goes down to its
+ * sentinel; the kinds are the same).  A unit is a row; with pair != 0 unit u is rows 2u and 2u + 1 of an index of both strands in input order, judged on row 2u,
+ * and every row enters the class table as unit r >> 1: a copy of a reverse complement is a copy, a palindrome keeps itself, and a sequence inside another one's
+ * reverse complement is inside a string of the index.  kind[u] (acc[1] >> pair bytes): 'C' contained, occ > copies (never with dup_only != 0); else 'D' duplicate,
+ * copies > 1 and u is not the smallest unit of its class; else 'K'.  keeper[u]: the smallest unit of u's class, u itself where copies == 1.  Symbols are compared
+ * as indexed (an N equals an N); a string of no symbols occurs at every row.  An octet of lanes per string; a step is the two dependent trips of a rank (directory word, slot) with five requests in flight in each;
+ * rb3gpu_tune "dedup_slice" strings per launch (default 4 M).  One string is one dependent chain: a long string that is NOT unique near its end runs at the latency
+ * of a rank.  The call holds 28 bytes per string and 9 per unit on the device; nothing is kept on the handle and the index is not changed.  RB3GPU_ESTATE without an
+ * index; RB3GPU_EINVAL for pair on an odd acc[1] and for a unit whose two rows disagree in occ or copies (not an index of both strands in input order);
+ * RB3GPU_EUNSUP for acc[1] >= 2^31 and for a string of 2^31 symbols or more; RB3GPU_EINTERNAL for a walk that does not end and for a walk whose own last row is not
+ * among the copies it counted.  st (may be NULL): ms_total wall time, ms_walk the walks alone (HIP events), n_strings, n_steps, n_early walks ended early, n_dup and
+ * n_contained units, n_classes classes of more than one string, n_slices */
+typedef struct { int64_t occ, copies, cls; } rb3gpu_dedup_rec_t;
+typedef struct { double ms_total, ms_walk; int64_t n_strings, n_steps, n_early, n_dup, n_contained, n_classes, n_slices; } rb3gpu_dedup_stats_t;
+int rb3gpu_dedup(rb3gpu_t *h, int pair, int dup_only, uint8_t *kind, int64_t *keeper, rb3gpu_dedup_rec_t *rec, rb3gpu_dedup_stats_t *st);
+
 /* regions of the indexed strings, read through the sampled suffix array the handle holds (rb3gpu_ssa_set / rb3gpu_ssa_keep; no counterpart in the reference;
  * DESIGN.md 7m): random access into the indexed text.  A region is (row r, beg, end): the symbols [beg, end) of string r, the string rb3gpu_retrieve spells for
  * row r < acc[1]; 0-based, end exclusive; valid iff 0 <= r < acc[1] and 0 <= beg < end <= the length of the string.  Sample x of the sampled suffix array says that
@@ -724,6 +745,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "hapdiv_slice" N (windows per launch of rb3gpu_hapdiv; 0 = 64 K), "hapdiv_table" N (slots of a window's candidate table in LDS; 0 = 256, at most 256);
  *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e and rb3gpu_sw_local; 0 = 16 K), "sw_table" N (as "hapdiv_table", for both);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
+ *   "dedup_slice" N (strings per launch of rb3gpu_dedup; 0 = 4 M), "dedup_early" 0/1 (its walks end once the string is known to be unique; default 1);
  *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8); "fetch_slice" N (symbols of a slice of regions of rb3gpu_fetch; 0 = 64 M);
  *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);

@@ -2065,6 +2065,103 @@ static int main_remove(int argc, char *argv[])
 	return ret;
 }
 
+/* dedup [--pair] [--dup-only] [--table] <idx> (no counterpart in the reference): the sequences that are exact copies of another one or lie wholly inside a
+ * longer one, through ONE call of rb3gpu_dedup.  The output is the list `remove -f` reads: the units to drop, one bare number per line, ascending -- rows, or with
+ * --pair sequences of an index of both strands in input order, where a copy of a reverse complement is a copy too.  --table: every unit with its kind (K kept,
+ * D duplicate, C contained), the keeper of its class, occ and copies of its (forward) row.  Nothing to drop is no output and exit 0.  --pair on a sorted index or on
+ * one strand, a further argument and a file that is no index are one line on stderr each, exit 1, nothing on stdout. */
+static const struct option dedup_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "pair", no_argument, 0, 503 },
+	{ "dup-only", no_argument, 0, 504 },
+	{ "table", no_argument, 0, 505 },
+	{ 0, 0, 0, 0 }
+};
+
+static int main_dedup(int argc, char *argv[])
+{
+	int c, ret = 0, device = 0, pair = 0, dup_only = 0, table = 0;
+	int64_t acc[7], nu = 0, u;
+	uint8_t *kind = 0;
+	int64_t *keeper = 0;
+	rb3gpu_dedup_rec_t *rec = 0;
+	rb3gpu_dedup_stats_t st;
+	rb3gpu_t *h;
+	index_host_t ih;
+	rb3h_buf_t out;
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "", dedup_long_opts, 0)) >= 0) {
+		if (c == 301) device = atoi(optarg);
+		else if (c == 503) pair = 1;
+		else if (c == 504) dup_only = 1;
+		else if (c == 505) table = 1;
+		else if (c == '?') return 1;
+	}
+	if (argc - optind < 1) {
+		fprintf(stderr, "Usage: ropebwt3-amd dedup [options] <idx.fmd|fmr|bre>\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  --pair         a unit is sequence i of an index of both strands in input order: rows 2i and 2i+1\n");
+		fprintf(stderr, "  --dup-only     exact copies only: a sequence inside a longer one stays\n");
+		fprintf(stderr, "  --table        every unit: number, kind (K kept, D duplicate, C contained), keeper, occurrences, copies\n");
+		fprintf(stderr, "  --gpu INT      HIP device ordinal [0]\n");
+		fprintf(stderr, "Output: the units to drop, one per line: what `remove [--pair] -f -` reads\n");
+		return 1;
+	}
+	if (argc - optind > 1) { fprintf(stderr, "ERROR: dedup: takes one index and nothing else ('%s')\n", argv[optind + 1]); return 1; }
+	if (pair && index_order(argv[optind]) != RB3GPU_SO_IO) {
+		fprintf(stderr, "ERROR: dedup: --pair numbers the sequences in input order; the strings of this index are sorted (build -s / -r): run it without --pair\n");
+		return 1;
+	}
+	memset(&ih, 0, sizeof(ih));
+	memset(&out, 0, sizeof(out));
+	c = rb3h_verbose;
+	rb3h_verbose = 0; /* (the command refuses with ONE line: the loading says nothing until the index is accepted) */
+	if (index_host_read(argv[optind], &ih) < 0) {
+		rb3h_verbose = c;
+		fprintf(stderr, "ERROR: dedup: '%s' is not an index\n", argv[optind]);
+		return 1;
+	}
+	rb3h_verbose = c > 2 ? 2 : c;
+	h = open_index(device, argv[optind], &ih);
+	rb3h_verbose = c;
+	if (h == 0) return 1;
+	rb3gpu_tune(h, "verbose", rb3h_verbose);
+	rb3gpu_get_acc(h, acc);
+	if (pair && !both_strands(acc)) ret = 1;
+	if (ret == 0) {
+		nu = pair ? acc[1] / 2 : acc[1];
+		kind = (uint8_t*)malloc((size_t)nu + 1);
+		keeper = (int64_t*)malloc((size_t)(nu + 1) * 8);
+		if (table) rec = (rb3gpu_dedup_rec_t*)malloc((size_t)(acc[1] + 1) * sizeof(*rec));
+		if (kind == 0 || keeper == 0 || (table && rec == 0)) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+	}
+	if (ret == 0) {
+		c = rb3gpu_dedup(h, pair, dup_only, kind, keeper, rec, &st);
+		if (c == RB3GPU_EINVAL && pair) { fprintf(stderr, "ERROR: dedup: --pair: rows 2i and 2i+1 of this index are not the two strands of a sequence\n"); ret = 1; }
+		else if (c != 0) { fprintf(stderr, "ERROR: the GPU engine failed to compare the sequences: %s\n", rb3gpu_strerror(c)); ret = 1; }
+	}
+	for (u = 0; u < nu && ret == 0; ++u) {
+		if (!table && kind[u] == 'K') continue;
+		if (out.l + 128 > out.m) {
+			const int64_t m = (out.l + 128) * 2;
+			uint8_t *t = (uint8_t*)realloc(out.s, (size_t)m);
+			if (t == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; break; }
+			out.s = t, out.m = m;
+		}
+		if (table) out.l += sprintf((char*)out.s + out.l, "%ld\t%c\t%ld\t%ld\t%ld\n", (long)u, kind[u], (long)keeper[u], (long)rec[pair ? 2 * u : u].occ, (long)rec[pair ? 2 * u : u].copies);
+		else out.l += sprintf((char*)out.s + out.l, "%ld\n", (long)u);
+		if (out_flush(&out, 0) < 0) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	}
+	if (ret == 0 && (out_flush(&out, 1) < 0 || fflush(stdout) != 0)) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (ret == 0 && rb3h_verbose >= 3)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld strings: %lld duplicates, %lld contained, %lld classes of copies; %lld steps in %lld slice(s), %lld walks ended early; %.3f ms in the engine, walk %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_strings, (long long)st.n_dup, (long long)st.n_contained, (long long)st.n_classes, (long long)st.n_steps,
+				(long long)st.n_slices, (long long)st.n_early, st.ms_total, st.ms_walk);
+	free(out.s); free(kind); free(keeper); free(rec);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* fetch [-f FILE] [--row] [-s INT] <idx> [region ...] (no counterpart in the reference): regions of the indexed sequences through the sampled suffix array,
  * ONE call of rb3gpu_fetch.  A region is the word name:beg-end[:+|:-] (rb3h_region_parse: 0-based, end-exclusive, the name cut at the last colons); -f adds BED lines.
  * Named regions need <idx>.ssa and <idx>.len.gz and an index of both strands in input order: sequence i forward is row 2i, region as given; strand - is row 2i + 1,
@@ -2897,6 +2994,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    suffix     find the longest matching suffix of queries (on an MI355X)\n");
 	fprintf(fp, "    get        retrieve the i-th sequence from a BWT (on an MI355X)\n");
 	fprintf(fp, "    remove     take sequences out of a BWT (on an MI355X)\n");
+	fprintf(fp, "    dedup      list sequences that are copies of, or lie inside, another one (on an MI355X)\n");
 	fprintf(fp, "    fetch      retrieve regions of sequences through the sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
@@ -2920,6 +3018,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "suffix") == 0) ret = main_suffix(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "get") == 0) ret = main_get(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "remove") == 0) ret = main_remove(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "dedup") == 0) ret = main_dedup(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "fetch") == 0) ret = main_fetch(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);

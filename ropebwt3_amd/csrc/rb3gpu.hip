@@ -28,6 +28,7 @@
 #include "rb3gpu_mem.h"
 #include "rb3gpu_walk.h"
 #include "rb3gpu_remove.h"
+#include "rb3gpu_dedup.h"
 #include "rb3gpu_fetch.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
@@ -174,6 +175,8 @@ struct Tune {
 	int64_t sw_slice = 0;    // rb3gpu_sw_e2e: queries per launch and per piece handed to the callback (0: 16 K; fewer where the backtrack matrices of a slice would not fit)
 	int64_t sw_table = 0;    // rb3gpu_sw_e2e: slots of a query's candidate table in LDS (0: 256, at most 256), as hapdiv_table
 	int64_t suffix_slice = 0;// rb3gpu_suffix: queries per launch (0: 4 M)
+	int64_t dedup_slice = 0; // rb3gpu_dedup: strings per launch (0: 4 M)
+	int dedup_early = 1;     // rb3gpu_dedup: a walk ends once its string is known to be unique (0: every walk goes down to its sentinel)
 	int64_t seed_chunk = 0;  // rb3gpu_seed_present: window starts per walker where the caller names none (0: 2048)
 	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
@@ -708,6 +711,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "sw_slice")) t.sw_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "sw_table")) t.sw_table = v < 0 ? 0 : v > HD_LDS_SLOTS ? HD_LDS_SLOTS : v;
 	else if (!strcmp(key, "suffix_slice")) t.suffix_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "dedup_slice")) t.dedup_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "dedup_early")) t.dedup_early = v != 0;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_piece")) t.get_piece = v < 1 ? 0 : v > 20 ? 20 : (int)v;
 	else if (!strcmp(key, "fetch_slice")) t.fetch_slice = v < 0 ? 0 : v;
@@ -752,7 +757,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -6280,6 +6285,82 @@ int rb3gpu_remove(rb3gpu_t *h, int64_t n, const int64_t *rows, int pieces, rb3gp
 		st->ms_total = (now_s() - t0) * 1e3, st->ms_mark = ms_mark, st->ms_build = h->stt.ms_build - ms_build0;
 		st->n_strings = nd, st->n_rows = n_rows, st->n_steps = (int64_t)(cp[1] + cm[1]), st->n_pieces = pieces ? nsp : 0, st->max_piece_steps = (int64_t)cp[3];
 		for (int a = 0; a < 6; ++a) st->removed[a] = (int64_t)cl[a];
+	}
+	return 0;
+}
+
+/* ---- dedup: copies and contained strings (rb3gpu_dedup.h) ---------------------------------------- */
+
+#define RB3_DEDUP_SLICE ((int64_t)1 << 22)    // strings per launch
+
+int rb3gpu_dedup(rb3gpu_t *h, int pair, int dup_only, uint8_t *kind, int64_t *keeper, rb3gpu_dedup_rec_t *rec, rb3gpu_dedup_stats_t *st)
+{
+	static_assert(sizeof(DedupRec) == sizeof(rb3gpu_dedup_rec_t), "one record layout on both sides");
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || !kind || !keeper) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1];
+	if (m <= 0) return RB3GPU_ESTATE; // (no index has no string)
+	if (pair && (m & 1)) return RB3GPU_EINVAL;
+	if (m >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP; // (a unit is 32 bits of the keeper table)
+	pair = pair != 0, dup_only = dup_only != 0;
+	const int64_t nu = m >> pair;
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	const int64_t slice = std::min(m, h->tn.dedup_slice > 0 ? h->tn.dedup_slice : RB3_DEDUP_SLICE);
+	Scratch sc;
+	DedupRec *d_rec = nullptr;
+	uint32_t *d_keep = nullptr;
+	uint8_t *d_kind = nullptr;
+	int64_t *d_keeper = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	HIPCHK(sc.dev(&d_rec, (size_t)m * sizeof(DedupRec)));
+	HIPCHK(sc.dev(&d_keep, (size_t)m * 4));
+	HIPCHK(sc.dev(&d_kind, (size_t)nu + 64));
+	HIPCHK(sc.dev(&d_keeper, (size_t)nu * 8));
+	HIPCHK(sc.dev(&d_ctr, 128)); // [0, 8): the walk, [8, 16): keeper and kind
+	HIPCHK(sc.pinned(&h_ctr, 128));
+	HIPCHK(sc.event(&e0));
+	HIPCHK(sc.event(&e1));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 128, h->st));
+	HIPCHK(hipMemsetAsync(d_keep, 0xFF, (size_t)m * 4, h->st)); // RB3_DEDUP_NONE
+	const IdxView ix = view_of(h);
+	double ms_walk = 0;
+	int64_t n_slices = 0;
+	for (int64_t r0 = 0; r0 < m; ++n_slices) { // the records stay on the device: a class may have its strings in any slices
+		const int64_t r1 = std::min(m, r0 + slice);
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
+		const int64_t nb = std::min<int64_t>(((r1 - r0) * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(e0, h->st));
+		hipLaunchKernelGGL(k_dedup_walk, dim3((unsigned)nb), dim3(256), 0, h->st, ix, r0, r1, h->tn.dedup_early, d_rec, d_ctr);
+		HIPCHK(hipEventRecord(e1, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_walk += ev_ms(e0, e1);
+		r0 = r1;
+	}
+	const unsigned nbm = (unsigned)((m + 255) / 256);
+	hipLaunchKernelGGL(k_dedup_keeper, dim3(nbm), dim3(256), 0, h->st, m, pair, (const DedupRec*)d_rec, d_keep, d_ctr + 8);
+	hipLaunchKernelGGL(k_dedup_kind, dim3(nbm), dim3(256), 0, h->st, m, nu, pair, dup_only, (const DedupRec*)d_rec, (const uint32_t*)d_keep, d_kind, d_keeper, d_ctr + 9);
+	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 128, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipGetLastError());
+	const unsigned long long *cw = h_ctr, *ck = h_ctr + 8;
+	if (cw[5] != 0) return RB3GPU_EUNSUP; // a string of 2^31 symbols or more
+	if (cw[2] != 0 || cw[3] != 0 || ck[0] != 0) {
+		if (h->opt.verbose >= 1)
+			fprintf(stderr, "[E::rb3gpu] dedup: %llu walks did not end, %llu ended outside the copies they counted, %llu classes outside the table\n", cw[2], cw[3], ck[0]);
+		return RB3GPU_EINTERNAL;
+	}
+	if (ck[4] != 0) return RB3GPU_EINVAL; // rows 2u and 2u + 1 that are not each other's strands: the caller's line, not the engine's
+	HIPCHK(hipMemcpyAsync(kind, d_kind, (size_t)nu, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(keeper, d_keeper, (size_t)nu * 8, hipMemcpyDeviceToHost, h->st));
+	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec, (size_t)m * sizeof(DedupRec), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	if (st) {
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_walk = ms_walk, st->n_strings = m, st->n_steps = (int64_t)cw[1], st->n_early = (int64_t)cw[4];
+		st->n_dup = (int64_t)ck[1], st->n_contained = (int64_t)ck[2], st->n_classes = (int64_t)ck[3], st->n_slices = n_slices;
 	}
 	return 0;
 }

@@ -170,6 +170,17 @@ class RemoveStats(ctypes.Structure):
         return {k: (list(getattr(self, k)) if k == "removed" else getattr(self, k)) for k, _ in self._fields_}
 
 
+DEDUP_REC = np.dtype([("occ", "<i8"), ("copies", "<i8"), ("cls", "<i8")])  # rb3gpu_dedup_rec_t
+
+
+class DedupStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_strings", ctypes.c_int64), ("n_steps", ctypes.c_int64), ("n_early", ctypes.c_int64),
+                ("n_dup", ctypes.c_int64), ("n_contained", ctypes.c_int64), ("n_classes", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FetchStats(ctypes.Structure):
     _fields_ = [("ms_total", ctypes.c_double), ("ms_table", ctypes.c_double), ("ms_plan", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_regions", ctypes.c_int64),
                 ("n_symbols", ctypes.c_int64), ("n_walkers", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_steps", ctypes.c_int64), ("max_walk_steps", ctypes.c_int64),
@@ -308,6 +319,7 @@ SYMBOLS = {
     "rb3gpu_retrieve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(RetrieveStats)]),
     "rb3gpu_retrieve_pieces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(PiecesStats)]),
     "rb3gpu_remove": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RemoveStats)]),
+    "rb3gpu_dedup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DedupStats)]),
     "rb3gpu_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), FETCH_F, ctypes.c_void_p, ctypes.POINTER(FetchStats)]),
 }
 
@@ -1018,6 +1030,22 @@ class Rb3Gpu:
         self._chk(self._lib.rb3gpu_remove(self._h, rows.size, rows.ctypes.data if rows.size else None, 1 if pieces else 0, ctypes.byref(st)), "rb3gpu_remove")
         if stats is not None:
             stats.update(st.as_dict())
+
+    def dedup(self, pair=False, dup_only=False, records=False, stats=None):
+        """rb3gpu_dedup: which strings of the index are copies of another one ('D') or lie inside a longer one ('C'; never with dup_only), and which stay ('K'):
+        (kind, keeper) -- a uint8 array of the letters and an int64 array of the smallest unit of each unit's class, one entry per unit.  A unit is a row; with
+        pair=True sequence u, rows 2u and 2u + 1 of an index of both strands in input order.  records=True: (kind, keeper, rec), rec a structured array
+        (DEDUP_REC) of occ, copies and cls per ROW -- (1, 1, -1) where the walk ended early.  stats: a dict that receives rb3gpu_dedup_stats_t"""
+        m = int(self.get_acc()[1])
+        nu = m >> 1 if pair else m
+        kind, keeper = np.zeros(max(nu, 1), dtype=np.uint8), np.zeros(max(nu, 1), dtype=np.int64)
+        rec = np.zeros(max(m, 1), dtype=DEDUP_REC) if records else None
+        st = DedupStats()
+        self._chk(self._lib.rb3gpu_dedup(self._h, 1 if pair else 0, 1 if dup_only else 0, kind.ctypes.data, keeper.ctypes.data, rec.ctypes.data if records else None,
+                                         ctypes.byref(st)), "rb3gpu_dedup")
+        if stats is not None:
+            stats.update(st.as_dict())
+        return (kind[:nu], keeper[:nu], rec[:m]) if records else (kind[:nu], keeper[:nu])
 
     def fetch(self, rows, begs, ends, stats=False):
         """rb3gpu_fetch: the symbols [begs[i], ends[i]) of string rows[i] (0-based, end exclusive; string r is what retrieve([r]) spells), read through the
