@@ -702,6 +702,33 @@ typedef struct { int64_t occ, copies, cls; } rb3gpu_dedup_rec_t;
 typedef struct { double ms_total, ms_walk; int64_t n_strings, n_steps, n_early, n_dup, n_contained, n_classes, n_slices; } rb3gpu_dedup_stats_t;
 int rb3gpu_dedup(rb3gpu_t *h, int pair, int dup_only, uint8_t *kind, int64_t *keeper, rb3gpu_dedup_rec_t *rec, rb3gpu_dedup_stats_t *st);
 
+/* which strings of the index overlap, end to start, and by how much (no counterpart in the reference): the record (a, b, len, len_b) says that the last
+ * len symbols of string a are the first len symbols of string b, min_len <= len < the length of a, len <= len_b = the length of b.  ALL acc[1] strings are walked.
+ * From row a the LF walk of rb3gpu_retrieve spells string a from its last symbol to its first, and the symbols read drive the backward search of rb3gpu_suffix from
+ * all the rows: after d symbols the interval holds every row whose suffix starts with the last d symbols of a, and the sentinels among its BWT symbols are the
+ * strings that START with them -- occ0(hi) - occ0(lo) of them, the group of depth d, named by the sentinel ranks in between.  The pass that reads a's own sentinel is
+ * the whole string and no overlap.  A group of more than max_hits partners is left out as a whole (0: none is).  A walk whose interval has come down to one row ends
+ * there: that row is its own suffix, and only the whole string is left (rb3gpu_tune "ovl_early" 0: every walk goes down to its sentinel; the records are the same).
+ * Nothing is filtered: a == b is a self-overlap, and len == len_b a partner that is wholly the overlap (what rb3gpu_dedup calls contained); on an index of both
+ * strands the four orientations are there, each overlap from both of its sides.  Symbols are compared as indexed (an N equals an N).  Three stages: COUNT, an octet
+ * of lanes per string, three rank loads in flight per pass, rb3gpu_tune "ovl_strings" strings per launch (default 4 M), gives the records of every string and the
+ * largest depth that has any; then, unless there is no record (and len is NULL), the lengths and end rows of all strings by the counting walk of rb3gpu_retrieve and
+ * the table from sentinel rank to string; then EMIT walks the strings that have records again, to that depth only.  The records reach cb in slices (host memory
+ * valid during the call only) of consecutive strings whose records sum to at most rb3gpu_tune "ovl_slice" (default 16 M records; a string with more is a slice of
+ * its own), ordered by a ascending, then len descending, then sentinel rank ascending -- the index's own order of the partners.  len (may be NULL; acc[1] entries)
+ * receives the length of every string before the first callback.  A nonzero return from cb stops the call and is returned; without a record cb is never called.
+ * The call holds 48 bytes per string and the records of a slice on the device; nothing is kept on the handle and the index is not changed.  RB3GPU_ESTATE without an
+ * index; RB3GPU_EINVAL for min_len < 1, max_hits < 0 and a NULL callback; RB3GPU_EUNSUP for acc[1] >= 2^31, a string of 2^31 symbols or more and a string with 2^31
+ * records or more; RB3GPU_EINTERNAL for a walk that does not end, a rank table that is not written exactly once per entry and a stored count that differs from the
+ * counted one.  st (may be NULL): ms_total wall time; ms_count, ms_who, ms_emit the stages (HIP events); n_steps_count and n_steps_emit passes of the two walks;
+ * n_early walks ended early; n_hits records; n_groups kept groups; n_capped_groups and n_capped_hits the groups over max_hits and their partners; n_emitters strings
+ * with records; n_slices callbacks */
+typedef struct { int32_t a, b, len, len_b; } rb3gpu_overlap_rec_t;
+typedef struct { double ms_total, ms_count, ms_who, ms_emit;
+                 int64_t n_strings, n_steps_count, n_steps_emit, n_early, n_hits, n_groups, n_capped_groups, n_capped_hits, n_emitters, n_slices; } rb3gpu_overlap_stats_t;
+typedef int (*rb3gpu_overlap_cb)(void *ud, int64_t n, const rb3gpu_overlap_rec_t *recs);
+int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_overlap_stats_t *st);
+
 /* regions of the indexed strings, read through the sampled suffix array the handle holds (rb3gpu_ssa_set / rb3gpu_ssa_keep; no counterpart in the reference;
  * DESIGN.md 7m): random access into the indexed text.  A region is (row r, beg, end): the symbols [beg, end) of string r, the string rb3gpu_retrieve spells for
  * row r < acc[1]; 0-based, end exclusive; valid iff 0 <= r < acc[1] and 0 <= beg < end <= the length of the string.  Sample x of the sampled suffix array says that
@@ -746,6 +773,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "sw_slice" N (queries per launch of rb3gpu_sw_e2e and rb3gpu_sw_local; 0 = 16 K), "sw_table" N (as "hapdiv_table", for both);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
  *   "dedup_slice" N (strings per launch of rb3gpu_dedup; 0 = 4 M), "dedup_early" 0/1 (its walks end once the string is known to be unique; default 1);
+ *   "ovl_strings" N (strings per launch of the counting walk of rb3gpu_overlap; 0 = 4 M), "ovl_slice" N (records of an emit slice; 0 = 16 M), "ovl_early" 0/1 (default 1);
  *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8); "fetch_slice" N (symbols of a slice of regions of rb3gpu_fetch; 0 = 64 M);
  *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);

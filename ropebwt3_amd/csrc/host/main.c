@@ -2162,6 +2162,108 @@ static int main_dedup(int argc, char *argv[])
 	return ret;
 }
 
+/* overlap [-l INT] [-c INT] [--pair] <idx> (no counterpart in the reference): the suffix-prefix overlaps of the indexed sequences, through ONE call of
+ * rb3gpu_overlap.  One line per record: a, b, len, len_a, len_b -- the last len symbols of row a are the first len of row b; by a, then longest first, then in the
+ * index's order of the partners.  --pair: i, strand_i, j, strand_j, len, len_i, len_j with sequence i = row >> 1 of an index of both strands in input order, + for an
+ * even row and - for an odd one; both views of an overlap are printed.  -l below 1, -c below 0, --pair on a sorted index or on one strand, a further argument and a
+ * file that is no index are one line on stderr each, exit 1, nothing on stdout. */
+static const struct option overlap_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "pair", no_argument, 0, 503 },
+	{ 0, 0, 0, 0 }
+};
+
+typedef struct { const int64_t *len; rb3h_buf_t out; int pair, err; } overlap_out_t;
+
+static int overlap_sink(void *ud, int64_t n, const rb3gpu_overlap_rec_t *recs)
+{
+	overlap_out_t *o = (overlap_out_t*)ud;
+	int64_t i;
+	for (i = 0; i < n && !o->err; ++i) {
+		const rb3gpu_overlap_rec_t *r = &recs[i];
+		if (o->out.l + 160 > o->out.m) {
+			const int64_t m = (o->out.l + 160) * 2;
+			uint8_t *t = (uint8_t*)realloc(o->out.s, (size_t)m);
+			if (t == 0) { o->err = 1; break; }
+			o->out.s = t, o->out.m = m;
+		}
+		if (o->pair) o->out.l += sprintf((char*)o->out.s + o->out.l, "%d\t%c\t%d\t%c\t%d\t%ld\t%d\n", r->a >> 1, "+-"[r->a & 1], r->b >> 1, "+-"[r->b & 1], r->len, (long)o->len[r->a], r->len_b);
+		else o->out.l += sprintf((char*)o->out.s + o->out.l, "%d\t%d\t%d\t%ld\t%d\n", r->a, r->b, r->len, (long)o->len[r->a], r->len_b);
+		if (out_flush(&o->out, 0) < 0) o->err = 2;
+	}
+	return o->err;
+}
+
+static int main_overlap(int argc, char *argv[])
+{
+	int c, ret = 0, device = 0, pair = 0;
+	int64_t acc[7], min_len = 31, max_hits = 0, *len = 0;
+	rb3gpu_overlap_stats_t st;
+	rb3gpu_t *h;
+	index_host_t ih;
+	overlap_out_t o;
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "l:c:", overlap_long_opts, 0)) >= 0) {
+		if (c == 301) device = atoi(optarg);
+		else if (c == 503) pair = 1;
+		else if (c == 'l') min_len = atol(optarg);
+		else if (c == 'c') max_hits = atol(optarg);
+		else if (c == '?') return 1;
+	}
+	if (argc - optind < 1) {
+		fprintf(stderr, "Usage: ropebwt3-amd overlap [options] <idx.fmd|fmr|bre>\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -l INT         min overlap length [%ld]\n", (long)min_len);
+		fprintf(stderr, "  -c INT         leave out an overlap shared with more than INT partners (0: none) [%ld]\n", (long)max_hits);
+		fprintf(stderr, "  --pair         name sequence i of an index of both strands in input order and its strand: rows 2i (+) and 2i+1 (-)\n");
+		fprintf(stderr, "  --gpu INT      HIP device ordinal [0]\n");
+		fprintf(stderr, "Output: a, b, len, len_a, len_b per overlap: the last len symbols of a are the first len of b (--pair: i, strand, j, strand, len, len_i, len_j)\n");
+		return 1;
+	}
+	if (min_len < 1) { fprintf(stderr, "ERROR: overlap: -l takes a length of at least 1\n"); return 1; }
+	if (max_hits < 0) { fprintf(stderr, "ERROR: overlap: -c takes a number of partners, 0 for no limit\n"); return 1; }
+	if (argc - optind > 1) { fprintf(stderr, "ERROR: overlap: takes one index and nothing else ('%s')\n", argv[optind + 1]); return 1; }
+	if (pair && index_order(argv[optind]) != RB3GPU_SO_IO) {
+		fprintf(stderr, "ERROR: overlap: --pair numbers the sequences in input order; the strings of this index are sorted (build -s / -r): run it without --pair\n");
+		return 1;
+	}
+	memset(&ih, 0, sizeof(ih));
+	memset(&o, 0, sizeof(o));
+	c = rb3h_verbose;
+	rb3h_verbose = 0; /* (the command refuses with ONE line: the loading says nothing until the index is accepted) */
+	if (index_host_read(argv[optind], &ih) < 0) {
+		rb3h_verbose = c;
+		fprintf(stderr, "ERROR: overlap: '%s' is not an index\n", argv[optind]);
+		return 1;
+	}
+	rb3h_verbose = c > 2 ? 2 : c;
+	h = open_index(device, argv[optind], &ih);
+	rb3h_verbose = c;
+	if (h == 0) return 1;
+	rb3gpu_tune(h, "verbose", rb3h_verbose);
+	rb3gpu_get_acc(h, acc);
+	if (pair && !both_strands(acc)) ret = 1;
+	if (ret == 0) {
+		len = (int64_t*)malloc((size_t)(acc[1] + 1) * 8);
+		if (len == 0) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+	}
+	if (ret == 0) {
+		o.len = len, o.pair = pair;
+		c = rb3gpu_overlap(h, min_len, max_hits, len, overlap_sink, &o, &st);
+		if (o.err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+		else if (o.err == 2) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+		else if (c != 0) { fprintf(stderr, "ERROR: the GPU engine failed to find the overlaps: %s\n", rb3gpu_strerror(c)); ret = 1; }
+	}
+	if (ret == 0 && (out_flush(&o.out, 1) < 0 || fflush(stdout) != 0)) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (ret == 0 && rb3h_verbose >= 3)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld strings: %lld overlaps in %lld groups of %lld strings, %lld groups of %lld partners over -c; %lld + %lld steps, %lld walks ended early, %lld slice(s); %.3f ms in the engine: count %.3f, who %.3f, emit %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_strings, (long long)st.n_hits, (long long)st.n_groups, (long long)st.n_emitters, (long long)st.n_capped_groups,
+				(long long)st.n_capped_hits, (long long)st.n_steps_count, (long long)st.n_steps_emit, (long long)st.n_early, (long long)st.n_slices, st.ms_total, st.ms_count, st.ms_who, st.ms_emit);
+	free(o.out.s); free(len);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* fetch [-f FILE] [--row] [-s INT] <idx> [region ...] (no counterpart in the reference): regions of the indexed sequences through the sampled suffix array,
  * ONE call of rb3gpu_fetch.  A region is the word name:beg-end[:+|:-] (rb3h_region_parse: 0-based, end-exclusive, the name cut at the last colons); -f adds BED lines.
  * Named regions need <idx>.ssa and <idx>.len.gz and an index of both strands in input order: sequence i forward is row 2i, region as given; strand - is row 2i + 1,
@@ -2995,6 +3097,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    get        retrieve the i-th sequence from a BWT (on an MI355X)\n");
 	fprintf(fp, "    remove     take sequences out of a BWT (on an MI355X)\n");
 	fprintf(fp, "    dedup      list sequences that are copies of, or lie inside, another one (on an MI355X)\n");
+	fprintf(fp, "    overlap    list the suffix-prefix overlaps of the sequences (on an MI355X)\n");
 	fprintf(fp, "    fetch      retrieve regions of sequences through the sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
@@ -3019,6 +3122,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "get") == 0) ret = main_get(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "remove") == 0) ret = main_remove(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "dedup") == 0) ret = main_dedup(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "overlap") == 0) ret = main_overlap(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "fetch") == 0) ret = main_fetch(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);

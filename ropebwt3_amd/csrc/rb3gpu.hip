@@ -29,6 +29,7 @@
 #include "rb3gpu_walk.h"
 #include "rb3gpu_remove.h"
 #include "rb3gpu_dedup.h"
+#include "rb3gpu_overlap.h"
 #include "rb3gpu_fetch.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
@@ -177,6 +178,9 @@ struct Tune {
 	int64_t suffix_slice = 0;// rb3gpu_suffix: queries per launch (0: 4 M)
 	int64_t dedup_slice = 0; // rb3gpu_dedup: strings per launch (0: 4 M)
 	int dedup_early = 1;     // rb3gpu_dedup: a walk ends once its string is known to be unique (0: every walk goes down to its sentinel)
+	int64_t ovl_strings = 0; // rb3gpu_overlap: strings per launch of the counting walk (0: 4 M)
+	int64_t ovl_slice = 0;   // rb3gpu_overlap: records of an emit slice (0: 16 M; a string with more is a slice of its own)
+	int ovl_early = 1;       // rb3gpu_overlap: a walk ends once its interval is one row (0: every walk goes down to its sentinel)
 	int64_t seed_chunk = 0;  // rb3gpu_seed_present: window starts per walker where the caller names none (0: 2048)
 	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
@@ -713,6 +717,9 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "suffix_slice")) t.suffix_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "dedup_slice")) t.dedup_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "dedup_early")) t.dedup_early = v != 0;
+	else if (!strcmp(key, "ovl_strings")) t.ovl_strings = v < 0 ? 0 : v;
+	else if (!strcmp(key, "ovl_slice")) t.ovl_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "ovl_early")) t.ovl_early = v != 0;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_piece")) t.get_piece = v < 1 ? 0 : v > 20 ? 20 : (int)v;
 	else if (!strcmp(key, "fetch_slice")) t.fetch_slice = v < 0 ? 0 : v;
@@ -757,7 +764,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "ovl_strings", "ovl_slice", "ovl_early", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -6363,6 +6370,166 @@ int rb3gpu_dedup(rb3gpu_t *h, int pair, int dup_only, uint8_t *kind, int64_t *ke
 		st->n_dup = (int64_t)ck[1], st->n_contained = (int64_t)ck[2], st->n_classes = (int64_t)ck[3], st->n_slices = n_slices;
 	}
 	return 0;
+}
+
+/* ---- overlap: suffix-prefix overlaps of the strings (rb3gpu_overlap.h) --------------------------- */
+
+#define RB3_OVL_STRINGS ((int64_t)1 << 22)    // strings per launch of the counting walk
+#define RB3_OVL_SLICE   ((int64_t)1 << 24)    // records of an emit slice
+
+int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_overlap_stats_t *st)
+{
+	static_assert(sizeof(OvlRec) == sizeof(rb3gpu_overlap_rec_t) && sizeof(OvlRec) == 16, "one record layout on both sides");
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || !cb || min_len < 1 || max_hits < 0) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1];
+	if (m <= 0) return RB3GPU_ESTATE; // (no index has no string)
+	if (m >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP; // (a string is 32 bits of a record)
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	const int32_t min32 = (int32_t)std::min<int64_t>(min_len, 0x7fffffff); // (no string has that many symbols)
+	const int64_t per = std::min(m, h->tn.ovl_strings > 0 ? h->tn.ovl_strings : RB3_OVL_STRINGS);
+	const int64_t budget = h->tn.ovl_slice > 0 ? h->tn.ovl_slice : RB3_OVL_SLICE;
+	Scratch sc;
+	uint32_t *d_cnt = nullptr, *d_who = nullptr, *d_len32 = nullptr, *d_em = nullptr;
+	int32_t *d_last = nullptr;
+	int64_t *d_off = nullptr, *d_rows = nullptr, *d_len = nullptr, *d_end = nullptr;
+	OvlRec *d_out = nullptr, *h_out = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	void *d_tmp = nullptr;
+	size_t tmp_bytes = 0;
+	HIPCHK(sc.dev(&d_cnt, (size_t)(m + 1) * 4));
+	HIPCHK(sc.dev(&d_last, (size_t)m * 4));
+	HIPCHK(sc.dev(&d_ctr, 512)); // [0, 16): the counting walk, [16, 24): the lengths and the rank table, [32, 48): the emitting walk, [48]: the end of the scan
+	HIPCHK(sc.pinned(&h_ctr, 512));
+	memset(h_ctr, 0, 512);
+	HIPCHK(sc.event(&e0));
+	HIPCHK(sc.event(&e1));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, 512, h->st));
+	HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_last, 0xFF, (size_t)m * 4, h->st));
+	const IdxView ix = view_of(h);
+	double ms_count = 0, ms_who = 0, ms_emit = 0;
+	int64_t n_slices = 0, n_emitters = 0;
+	// 1. count: the records of every string and the largest depth that has any
+	for (int64_t r0 = 0; r0 < m;) {
+		const int64_t r1 = std::min(m, r0 + per);
+		HIPCHK(hipMemsetAsync(d_ctr, 0, 8, h->st));
+		const int64_t nb = std::min<int64_t>(((r1 - r0) * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(e0, h->st));
+		hipLaunchKernelGGL(k_ovl_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, r0, r1, min32, max_hits, h->tn.ovl_early, (const uint32_t*)nullptr, d_cnt, d_last,
+				(const int64_t*)nullptr, (int64_t)0, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (OvlRec*)nullptr, (int64_t)0, d_ctr);
+		HIPCHK(hipEventRecord(e1, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_count += ev_ms(e0, e1);
+		r0 = r1;
+	}
+	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 128, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	const unsigned long long *cw = h_ctr, *cg = h_ctr + 16, *ce = h_ctr + 32;
+	if (cw[3] != 0 || cw[9] != 0) return RB3GPU_EUNSUP; // a string of 2^31 symbols, or of 2^31 records, or more
+	if (cw[2] != 0) {
+		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] overlap: %llu walks did not end\n", cw[2]);
+		return RB3GPU_EINTERNAL;
+	}
+	const int64_t n_hits = (int64_t)cw[8];
+	// 2. the length and the end row of every string (the counting walk of `get` over the rows 0 .. m - 1), and the string of every sentinel rank
+	if (n_hits > 0 || len != nullptr) {
+		HIPCHK(sc.dev(&d_rows, (size_t)m * 8));
+		HIPCHK(sc.dev(&d_len, (size_t)m * 8));
+		HIPCHK(sc.dev(&d_end, (size_t)m * 8));
+		HIPCHK(sc.dev(&d_len32, (size_t)m * 4));
+		const unsigned nbm = (unsigned)((m + 255) / 256);
+		const int64_t nb = std::min<int64_t>((m * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(e0, h->st));
+		hipLaunchKernelGGL(k_ovl_iota, dim3(nbm), dim3(256), 0, h->st, m, d_rows);
+		hipLaunchKernelGGL(k_get_walk<false>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const int64_t*)d_rows, (int64_t)0, m, d_len, d_end, d_len32, (const int64_t*)nullptr, (uint8_t*)nullptr, (int64_t)0, d_ctr + 16);
+		if (n_hits > 0) {
+			HIPCHK(sc.dev(&d_who, (size_t)m * 4));
+			HIPCHK(hipMemsetAsync(d_who, 0xFF, (size_t)m * 4, h->st)); // RB3_OVL_NONE
+			hipLaunchKernelGGL(k_ovl_who, dim3((unsigned)((m * 8 + 255) / 256)), dim3(256), 0, h->st, ix, (const int64_t*)d_end, d_who, d_ctr + 19);
+		}
+		HIPCHK(hipEventRecord(e1, h->st));
+		std::vector<int64_t> vlen;
+		int64_t *hl = len;
+		if (hl == nullptr) vlen.resize((size_t)m), hl = vlen.data();
+		HIPCHK(hipMemcpyAsync(hl, d_len, (size_t)m * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr + 16, d_ctr + 16, 64, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_who = ev_ms(e0, e1);
+		if (cg[2] != 0 || cg[3] != 0) {
+			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] overlap: %llu walks did not end, %llu entries of the rank table not written exactly once\n", cg[2], cg[3]);
+			return RB3GPU_EINTERNAL;
+		}
+		for (int64_t r = 0; r < m; ++r) {
+			if (hl[r] < 0 || hl[r] >= h->n) return RB3GPU_EINTERNAL;
+			if (hl[r] >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP;
+		}
+	}
+	// 3. emit: where every string's records start, the strings that have any, and slices of them whose records sum to at most the budget, one with more alone
+	int ret = 0;
+	if (n_hits > 0) {
+		HIPCHK(sc.dev(&d_off, (size_t)(m + 1) * 8));
+		{
+			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, m + 1, h->st);
+			if (r < 0) return scan_err(r);
+			HIPCHK(sc.dev(&d_tmp, tmp_bytes + 256));
+			size_t tb = tmp_bytes + 256;
+			const int r2 = rb3kount_scan(d_tmp, &tb, d_cnt, d_off, m + 1, h->st); // (d_cnt[m] = 0: the entry behind the last string)
+			if (r2 < 0) return scan_err(r2);
+		}
+		std::vector<uint32_t> cnt((size_t)m), em;
+		std::vector<int64_t> eoff(1, 0); // eoff[i]: the records in front of emitter i
+		HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)m * 4, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr + 48, d_off + m, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		for (int64_t r = 0; r < m; ++r)
+			if (cnt[(size_t)r] > 0u) em.push_back((uint32_t)r), eoff.push_back(eoff.back() + (int64_t)cnt[(size_t)r]);
+		n_emitters = (int64_t)em.size();
+		if (eoff.back() != n_hits || (int64_t)h_ctr[48] != n_hits) return RB3GPU_EINTERNAL; // the scan on the device, the sum on the host and the walks' count are of the same records
+		HIPCHK(sc.dev(&d_em, (size_t)n_emitters * 4));
+		HIPCHK(hipMemcpyAsync(d_em, em.data(), (size_t)n_emitters * 4, hipMemcpyHostToDevice, h->st));
+		int64_t out_cap = 0;
+		for (int64_t i0 = 0; i0 < n_emitters && ret == 0; ++n_slices) {
+			int64_t i1 = i0 + 1;
+			while (i1 < n_emitters && eoff[(size_t)i1 + 1] - eoff[(size_t)i0] <= budget) ++i1;
+			const int64_t tot = eoff[(size_t)i1] - eoff[(size_t)i0];
+			if (tot > out_cap) { // (grows to the largest slice: the budget, or the one string that exceeds it)
+				out_cap = 0;
+				const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 16));
+				HIPCHK(sc.regrow(&d_out, &h_out, (size_t)oc * sizeof(OvlRec)));
+				out_cap = oc;
+			}
+			HIPCHK(hipMemsetAsync(d_ctr + 32, 0, 8, h->st));
+			HIPCHK(hipMemsetAsync(d_ctr + 40, 0, 8, h->st)); // the records stored by this slice
+			const int64_t nb = std::min<int64_t>(((i1 - i0) * 8 + 255) / 256, 4096);
+			HIPCHK(hipEventRecord(e0, h->st));
+			hipLaunchKernelGGL(k_ovl_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, i0, i1, min32, max_hits, 0, (const uint32_t*)d_em, d_cnt, d_last,
+					(const int64_t*)d_off, eoff[(size_t)i0], (const uint32_t*)d_who, (const uint32_t*)d_len32, d_out, tot, d_ctr + 32);
+			HIPCHK(hipEventRecord(e1, h->st));
+			HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)tot * sizeof(OvlRec), hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(h_ctr + 32, d_ctr + 32, 88, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_emit += ev_ms(e0, e1);
+			if (ce[2] != 0 || ce[3] != 0 || ce[10] != 0 || (int64_t)ce[8] != tot) {
+				if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] overlap: a slice stored %llu records where %lld were counted (%llu strings differ)\n", ce[8], (long long)tot, ce[10]);
+				return RB3GPU_EINTERNAL;
+			}
+			ret = cb(ud, tot, (const rb3gpu_overlap_rec_t*)h_out);
+			i0 = i1;
+		}
+	}
+	if (st) {
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = ms_count, st->ms_who = ms_who, st->ms_emit = ms_emit;
+		st->n_strings = m, st->n_steps_count = (int64_t)cw[1], st->n_steps_emit = (int64_t)ce[1], st->n_early = (int64_t)cw[4], st->n_hits = n_hits, st->n_groups = (int64_t)cw[5];
+		st->n_capped_groups = (int64_t)cw[6], st->n_capped_hits = (int64_t)cw[7], st->n_emitters = n_emitters, st->n_slices = n_slices;
+	}
+	return ret;
 }
 
 } // extern "C"

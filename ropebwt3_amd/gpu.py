@@ -181,6 +181,19 @@ class DedupStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+OVERLAP_REC = np.dtype([("a", "<i4"), ("b", "<i4"), ("len", "<i4"), ("len_b", "<i4")])  # rb3gpu_overlap_rec_t
+OVERLAP_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
+
+
+class OverlapStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_count", ctypes.c_double), ("ms_who", ctypes.c_double), ("ms_emit", ctypes.c_double), ("n_strings", ctypes.c_int64),
+                ("n_steps_count", ctypes.c_int64), ("n_steps_emit", ctypes.c_int64), ("n_early", ctypes.c_int64), ("n_hits", ctypes.c_int64), ("n_groups", ctypes.c_int64),
+                ("n_capped_groups", ctypes.c_int64), ("n_capped_hits", ctypes.c_int64), ("n_emitters", ctypes.c_int64), ("n_slices", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FetchStats(ctypes.Structure):
     _fields_ = [("ms_total", ctypes.c_double), ("ms_table", ctypes.c_double), ("ms_plan", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_regions", ctypes.c_int64),
                 ("n_symbols", ctypes.c_int64), ("n_walkers", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_steps", ctypes.c_int64), ("max_walk_steps", ctypes.c_int64),
@@ -320,6 +333,7 @@ SYMBOLS = {
     "rb3gpu_retrieve_pieces": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, RETRIEVE_F, ctypes.c_void_p, ctypes.POINTER(PiecesStats)]),
     "rb3gpu_remove": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RemoveStats)]),
     "rb3gpu_dedup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DedupStats)]),
+    "rb3gpu_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, OVERLAP_F, ctypes.c_void_p, ctypes.POINTER(OverlapStats)]),
     "rb3gpu_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), FETCH_F, ctypes.c_void_p, ctypes.POINTER(FetchStats)]),
 }
 
@@ -1046,6 +1060,25 @@ class Rb3Gpu:
         if stats is not None:
             stats.update(st.as_dict())
         return (kind[:nu], keeper[:nu], rec[:m]) if records else (kind[:nu], keeper[:nu])
+
+    def overlap(self, min_len, max_hits=0, stats=None, lengths=False):
+        """rb3gpu_overlap: the suffix-prefix overlaps of all the strings of the index: one structured array (OVERLAP_REC) of the records (a, b, len, len_b) -- the last
+        len symbols of string a are the first len of string b, min_len <= len < the length of a, len_b the length of b -- ordered by a, then longest first, then in
+        the index's order of the partners.  max_hits > 0 leaves out every group of more than max_hits partners of one (a, len).  lengths=True: (records, the length of
+        every string, int64).  stats: a dict that receives rb3gpu_overlap_stats_t"""
+        got = []
+
+        def cb(_ud, n, recs):
+            got.append(np.frombuffer(ctypes.string_at(recs, int(n) * OVERLAP_REC.itemsize), dtype=OVERLAP_REC))
+            return 0
+        m = int(self.get_acc()[1])
+        ln = np.zeros(max(m, 1), dtype=np.int64) if lengths else None
+        st = OverlapStats()
+        self._chk(self._lib.rb3gpu_overlap(self._h, int(min_len), int(max_hits), ln.ctypes.data if lengths else None, OVERLAP_F(cb), None, ctypes.byref(st)), "rb3gpu_overlap")
+        if stats is not None:
+            stats.update(st.as_dict())
+        rec = np.concatenate(got) if got else np.zeros(0, dtype=OVERLAP_REC)
+        return (rec, ln[:m]) if lengths else rec
 
     def fetch(self, rows, begs, ends, stats=False):
         """rb3gpu_fetch: the symbols [begs[i], ends[i]) of string rows[i] (0-based, end exclusive; string r is what retrieve([r]) spells), read through the
