@@ -729,6 +729,25 @@ typedef struct { double ms_total, ms_count, ms_who, ms_emit;
 typedef int (*rb3gpu_overlap_cb)(void *ud, int64_t n, const rb3gpu_overlap_rec_t *recs);
 int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_overlap_stats_t *st);
 
+/* the irreducible overlaps: the records of rb3gpu_overlap for the same index, min_len and max_hits -- the set R -- without those that two longer ones imply (the
+ * transitive reduction of Myers' string graph; no counterpart in the reference).  (a, b, o) is reducible iff some (a, c, o_c) of R has o_c > o and
+ * len(c) > o_c and (c, b, len(c) - o_c + o) is in R: c overlaps a by more, reaches beyond the end of a, and what it adds there is a prefix of what b adds.  Nothing else
+ * is filtered: c == a and c == b count, a witness counts whether it is itself reducible or not (the answer does not depend on any order), copies of a witness are all
+ * kept and copies of a reducible partner all reduced.  The kept records are a subsequence of rb3gpu_overlap's in its order; the deepest group of every string is kept
+ * whole, so the strings with kept records are the strings with records; with max_hits the rule is applied to the capped set.  The record type, the callback, the
+ * slices (consecutive strings whose KEPT records sum to at most "ovl_slice") and len are rb3gpu_overlap's.  Stages: COUNT, the lengths, the rank table and the scan
+ * as there; EMIT of ALL the records into one resident array, "ovl_strings" strings per launch; REDUCE, an octet of lanes per record, the lanes over the records of
+ * the same string with a deeper overlap, each with one binary search in the list of its witness, rb3gpu_tune "ovl_reduce_strings" strings per launch (default 4 M);
+ * COMPACT, a scan of the keep flags and an order-preserving scatter per slice.  The call holds 28 bytes per record (the record, its flag, its scanned position) and
+ * 4 bytes per string more than rb3gpu_overlap on the device, and nothing on the handle.  More records than rb3gpu_tune "ovl_resident" (0, the default: no limit but
+ * the allocation) is RB3GPU_EUNSUP, an allocation that fails RB3GPU_ENOMEM, both before the first callback: use a larger min_len, a max_hits, or rb3gpu_overlap.
+ * Other codes as rb3gpu_overlap, and RB3GPU_EINTERNAL also for a string with records and none kept and for kept + reduced != n_hits.  st (may be NULL): ms_reduce
+ * and ms_compact the two new stages (HIP events; ms_emit includes the inverse rank table); n_kept the records delivered; resident_bytes what REDUCE and COMPACT held
+ * on the device; the rest as in rb3gpu_overlap_stats_t */
+typedef struct { double ms_total, ms_count, ms_who, ms_emit, ms_reduce, ms_compact;
+                 int64_t n_strings, n_hits, n_kept, n_groups, n_capped_groups, n_capped_hits, n_emitters, n_slices, resident_bytes; } rb3gpu_reduce_stats_t;
+int rb3gpu_overlap_reduced(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_reduce_stats_t *st);
+
 /* regions of the indexed strings, read through the sampled suffix array the handle holds (rb3gpu_ssa_set / rb3gpu_ssa_keep; no counterpart in the reference;
  * DESIGN.md 7m): random access into the indexed text.  A region is (row r, beg, end): the symbols [beg, end) of string r, the string rb3gpu_retrieve spells for
  * row r < acc[1]; 0-based, end exclusive; valid iff 0 <= r < acc[1] and 0 <= beg < end <= the length of the string.  Sample x of the sampled suffix array says that
@@ -774,6 +793,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "suffix_slice" N (queries per launch of rb3gpu_suffix; 0 = 4 M), "get_slice" N (symbols of an emit slice of rb3gpu_retrieve; 0 = 64 M);
  *   "dedup_slice" N (strings per launch of rb3gpu_dedup; 0 = 4 M), "dedup_early" 0/1 (its walks end once the string is known to be unique; default 1);
  *   "ovl_strings" N (strings per launch of the counting walk of rb3gpu_overlap; 0 = 4 M), "ovl_slice" N (records of an emit slice; 0 = 16 M), "ovl_early" 0/1 (default 1);
+ *   "ovl_resident" N (records rb3gpu_overlap_reduced may hold on the device; 0 = as many as can be allocated), "ovl_reduce_strings" N (strings per launch of its reduction; 0 = 4 M);
  *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8); "fetch_slice" N (symbols of a slice of regions of rb3gpu_fetch; 0 = 64 M);
  *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);

@@ -2162,14 +2162,16 @@ static int main_dedup(int argc, char *argv[])
 	return ret;
 }
 
-/* overlap [-l INT] [-c INT] [--pair] <idx> (no counterpart in the reference): the suffix-prefix overlaps of the indexed sequences, through ONE call of
- * rb3gpu_overlap.  One line per record: a, b, len, len_a, len_b -- the last len symbols of row a are the first len of row b; by a, then longest first, then in the
- * index's order of the partners.  --pair: i, strand_i, j, strand_j, len, len_i, len_j with sequence i = row >> 1 of an index of both strands in input order, + for an
+/* overlap [-l INT] [-c INT] [--pair] [--reduce] <idx> (no counterpart in the reference): the suffix-prefix overlaps of the indexed sequences, through
+ * ONE call of rb3gpu_overlap -- with --reduce of rb3gpu_overlap_reduced: the same lines for the irreducible overlaps only; more overlaps than it may hold on the device and
+ * more than the device's memory takes are one line on stderr each, exit 1, nothing on stdout.  One line per record: a, b, len, len_a, len_b -- the last len symbols of
+ * row a are the first len of row b; by a, then longest first, then in the index's order of the partners.  --pair: i, strand_i, j, strand_j, len, len_i, len_j with sequence i = row >> 1 of an index of both strands in input order, + for an
  * even row and - for an odd one; both views of an overlap are printed.  -l below 1, -c below 0, --pair on a sorted index or on one strand, a further argument and a
  * file that is no index are one line on stderr each, exit 1, nothing on stdout. */
 static const struct option overlap_long_opts[] = {
 	{ "gpu", required_argument, 0, 301 },
 	{ "pair", no_argument, 0, 503 },
+	{ "reduce", no_argument, 0, 504 },
 	{ 0, 0, 0, 0 }
 };
 
@@ -2196,9 +2198,10 @@ static int overlap_sink(void *ud, int64_t n, const rb3gpu_overlap_rec_t *recs)
 
 static int main_overlap(int argc, char *argv[])
 {
-	int c, ret = 0, device = 0, pair = 0;
+	int c, ret = 0, device = 0, pair = 0, reduce = 0;
 	int64_t acc[7], min_len = 31, max_hits = 0, *len = 0;
 	rb3gpu_overlap_stats_t st;
+	rb3gpu_reduce_stats_t rs;
 	rb3gpu_t *h;
 	index_host_t ih;
 	overlap_out_t o;
@@ -2206,6 +2209,7 @@ static int main_overlap(int argc, char *argv[])
 	while ((c = getopt_long(argc, argv, "l:c:", overlap_long_opts, 0)) >= 0) {
 		if (c == 301) device = atoi(optarg);
 		else if (c == 503) pair = 1;
+		else if (c == 504) reduce = 1;
 		else if (c == 'l') min_len = atol(optarg);
 		else if (c == 'c') max_hits = atol(optarg);
 		else if (c == '?') return 1;
@@ -2216,6 +2220,7 @@ static int main_overlap(int argc, char *argv[])
 		fprintf(stderr, "  -l INT         min overlap length [%ld]\n", (long)min_len);
 		fprintf(stderr, "  -c INT         leave out an overlap shared with more than INT partners (0: none) [%ld]\n", (long)max_hits);
 		fprintf(stderr, "  --pair         name sequence i of an index of both strands in input order and its strand: rows 2i (+) and 2i+1 (-)\n");
+		fprintf(stderr, "  --reduce       only the irreducible overlaps: leave out a -> b where a longer a -> c and c -> b put b at the same place (after -c)\n");
 		fprintf(stderr, "  --gpu INT      HIP device ordinal [0]\n");
 		fprintf(stderr, "Output: a, b, len, len_a, len_b per overlap: the last len symbols of a are the first len of b (--pair: i, strand, j, strand, len, len_i, len_j)\n");
 		return 1;
@@ -2249,13 +2254,20 @@ static int main_overlap(int argc, char *argv[])
 	}
 	if (ret == 0) {
 		o.len = len, o.pair = pair;
-		c = rb3gpu_overlap(h, min_len, max_hits, len, overlap_sink, &o, &st);
+		if (reduce) c = rb3gpu_overlap_reduced(h, min_len, max_hits, len, overlap_sink, &o, &rs);
+		else c = rb3gpu_overlap(h, min_len, max_hits, len, overlap_sink, &o, &st);
 		if (o.err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
 		else if (o.err == 2) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+		else if (reduce && c == RB3GPU_EUNSUP) { fprintf(stderr, "ERROR: overlap: --reduce holds all the overlaps on the device, and there are more than RB3GPU_OVL_RESIDENT allows: raise -l, set -c, or run it without --reduce\n"); ret = 1; }
+		else if (reduce && c == RB3GPU_ENOMEM) { fprintf(stderr, "ERROR: overlap: --reduce holds all the overlaps on the device, and there are more than its memory takes: raise -l, set -c, or run it without --reduce\n"); ret = 1; }
 		else if (c != 0) { fprintf(stderr, "ERROR: the GPU engine failed to find the overlaps: %s\n", rb3gpu_strerror(c)); ret = 1; }
 	}
 	if (ret == 0 && (out_flush(&o.out, 1) < 0 || fflush(stdout) != 0)) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
-	if (ret == 0 && rb3h_verbose >= 3)
+	if (ret == 0 && rb3h_verbose >= 3 && reduce)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld strings: %lld overlaps in %lld groups of %lld strings, %lld kept by --reduce, %lld groups of %lld partners over -c; %lld slice(s), %lld bytes resident; %.3f ms in the engine: count %.3f, who %.3f, emit %.3f, reduce %.3f, compact %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)rs.n_strings, (long long)rs.n_hits, (long long)rs.n_groups, (long long)rs.n_emitters, (long long)rs.n_kept, (long long)rs.n_capped_groups,
+				(long long)rs.n_capped_hits, (long long)rs.n_slices, (long long)rs.resident_bytes, rs.ms_total, rs.ms_count, rs.ms_who, rs.ms_emit, rs.ms_reduce, rs.ms_compact);
+	else if (ret == 0 && rb3h_verbose >= 3)
 		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld strings: %lld overlaps in %lld groups of %lld strings, %lld groups of %lld partners over -c; %lld + %lld steps, %lld walks ended early, %lld slice(s); %.3f ms in the engine: count %.3f, who %.3f, emit %.3f ms\n",
 				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_strings, (long long)st.n_hits, (long long)st.n_groups, (long long)st.n_emitters, (long long)st.n_capped_groups,
 				(long long)st.n_capped_hits, (long long)st.n_steps_count, (long long)st.n_steps_emit, (long long)st.n_early, (long long)st.n_slices, st.ms_total, st.ms_count, st.ms_who, st.ms_emit);

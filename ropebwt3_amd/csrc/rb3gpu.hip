@@ -30,6 +30,7 @@
 #include "rb3gpu_remove.h"
 #include "rb3gpu_dedup.h"
 #include "rb3gpu_overlap.h"
+#include "rb3gpu_reduce.h"
 #include "rb3gpu_fetch.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
@@ -181,6 +182,8 @@ struct Tune {
 	int64_t ovl_strings = 0; // rb3gpu_overlap: strings per launch of the counting walk (0: 4 M)
 	int64_t ovl_slice = 0;   // rb3gpu_overlap: records of an emit slice (0: 16 M; a string with more is a slice of its own)
 	int ovl_early = 1;       // rb3gpu_overlap: a walk ends once its interval is one row (0: every walk goes down to its sentinel)
+	int64_t ovl_resident = 0;       // rb3gpu_overlap_reduced: the records it may hold on the device (0: as many as can be allocated)
+	int64_t ovl_reduce_strings = 0; // rb3gpu_overlap_reduced: strings per launch of the reduction (0: 4 M)
 	int64_t seed_chunk = 0;  // rb3gpu_seed_present: window starts per walker where the caller names none (0: 2048)
 	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
@@ -720,6 +723,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "ovl_strings")) t.ovl_strings = v < 0 ? 0 : v;
 	else if (!strcmp(key, "ovl_slice")) t.ovl_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "ovl_early")) t.ovl_early = v != 0;
+	else if (!strcmp(key, "ovl_resident")) t.ovl_resident = v < 0 ? 0 : v;
+	else if (!strcmp(key, "ovl_reduce_strings")) t.ovl_reduce_strings = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_piece")) t.get_piece = v < 1 ? 0 : v > 20 ? 20 : (int)v;
 	else if (!strcmp(key, "fetch_slice")) t.fetch_slice = v < 0 ? 0 : v;
@@ -764,7 +769,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "ovl_strings", "ovl_slice", "ovl_early", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "ovl_strings", "ovl_slice", "ovl_early", "ovl_resident", "ovl_reduce_strings", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -6377,32 +6382,36 @@ int rb3gpu_dedup(rb3gpu_t *h, int pair, int dup_only, uint8_t *kind, int64_t *ke
 #define RB3_OVL_STRINGS ((int64_t)1 << 22)    // strings per launch of the counting walk
 #define RB3_OVL_SLICE   ((int64_t)1 << 24)    // records of an emit slice
 
-int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_overlap_stats_t *st)
-{
-	static_assert(sizeof(OvlRec) == sizeof(rb3gpu_overlap_rec_t) && sizeof(OvlRec) == 16, "one record layout on both sides");
-	if (st) memset(st, 0, sizeof(*st));
-	if (!h || !cb || min_len < 1 || max_hits < 0) return RB3GPU_EINVAL;
-	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
-	const int64_t m = h->acc[1];
-	if (m <= 0) return RB3GPU_ESTATE; // (no index has no string)
-	if (m >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP; // (a string is 32 bits of a record)
-	double t0;
-	if (const int e = drv_enter(h, &t0)) return e;
-	const int32_t min32 = (int32_t)std::min<int64_t>(min_len, 0x7fffffff); // (no string has that many symbols)
-	const int64_t per = std::min(m, h->tn.ovl_strings > 0 ? h->tn.ovl_strings : RB3_OVL_STRINGS);
-	const int64_t budget = h->tn.ovl_slice > 0 ? h->tn.ovl_slice : RB3_OVL_SLICE;
-	Scratch sc;
+/* what COUNT, the lengths, the rank table and the scan leave to EMIT, shared by rb3gpu_overlap and rb3gpu_overlap_reduced: the device memory is the call's Scratch's */
+struct OvlPlan {
 	uint32_t *d_cnt = nullptr, *d_who = nullptr, *d_len32 = nullptr, *d_em = nullptr;
 	int32_t *d_last = nullptr;
-	int64_t *d_off = nullptr, *d_rows = nullptr, *d_len = nullptr, *d_end = nullptr;
-	OvlRec *d_out = nullptr, *h_out = nullptr;
-	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr;
+	int64_t *d_off = nullptr;
+	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr; // [0, 16): the counting walk, [16, 24): the lengths and the rank table, [32, 48): the emitting walk, [48]: the end of the scan
 	hipEvent_t e0 = nullptr, e1 = nullptr;
+	int32_t min32 = 0;
+	double ms_count = 0, ms_who = 0;
+	int64_t n_hits = 0, n_emitters = 0;
+	std::vector<uint32_t> em;  // the strings that have records
+	std::vector<int64_t> eoff; // eoff[i]: the records in front of emitter i
+};
+
+static int ovl_plan(rb3gpu_t *h, Scratch &sc, int64_t min_len, int64_t max_hits, int64_t *len, OvlPlan &P)
+{
+	const int64_t m = h->acc[1];
+	P.min32 = (int32_t)std::min<int64_t>(min_len, 0x7fffffff); // (no string has that many symbols)
+	const int32_t min32 = P.min32;
+	const int64_t per = std::min(m, h->tn.ovl_strings > 0 ? h->tn.ovl_strings : RB3_OVL_STRINGS);
+	uint32_t *&d_cnt = P.d_cnt, *&d_who = P.d_who, *&d_len32 = P.d_len32, *&d_em = P.d_em;
+	int32_t *&d_last = P.d_last;
+	int64_t *&d_off = P.d_off, *d_rows = nullptr, *d_len = nullptr, *d_end = nullptr;
+	unsigned long long *&d_ctr = P.d_ctr, *&h_ctr = P.h_ctr;
+	hipEvent_t &e0 = P.e0, &e1 = P.e1;
 	void *d_tmp = nullptr;
 	size_t tmp_bytes = 0;
 	HIPCHK(sc.dev(&d_cnt, (size_t)(m + 1) * 4));
 	HIPCHK(sc.dev(&d_last, (size_t)m * 4));
-	HIPCHK(sc.dev(&d_ctr, 512)); // [0, 16): the counting walk, [16, 24): the lengths and the rank table, [32, 48): the emitting walk, [48]: the end of the scan
+	HIPCHK(sc.dev(&d_ctr, 512));
 	HIPCHK(sc.pinned(&h_ctr, 512));
 	memset(h_ctr, 0, 512);
 	HIPCHK(sc.event(&e0));
@@ -6411,8 +6420,7 @@ int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len,
 	HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(m + 1) * 4, h->st));
 	HIPCHK(hipMemsetAsync(d_last, 0xFF, (size_t)m * 4, h->st));
 	const IdxView ix = view_of(h);
-	double ms_count = 0, ms_who = 0, ms_emit = 0;
-	int64_t n_slices = 0, n_emitters = 0;
+	double &ms_count = P.ms_count, &ms_who = P.ms_who;
 	// 1. count: the records of every string and the largest depth that has any
 	for (int64_t r0 = 0; r0 < m;) {
 		const int64_t r1 = std::min(m, r0 + per);
@@ -6429,13 +6437,13 @@ int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len,
 	}
 	HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 128, hipMemcpyDeviceToHost, h->st));
 	HIPCHK(hipStreamSynchronize(h->st));
-	const unsigned long long *cw = h_ctr, *cg = h_ctr + 16, *ce = h_ctr + 32;
+	const unsigned long long *cw = h_ctr, *cg = h_ctr + 16;
 	if (cw[3] != 0 || cw[9] != 0) return RB3GPU_EUNSUP; // a string of 2^31 symbols, or of 2^31 records, or more
 	if (cw[2] != 0) {
 		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] overlap: %llu walks did not end\n", cw[2]);
 		return RB3GPU_EINTERNAL;
 	}
-	const int64_t n_hits = (int64_t)cw[8];
+	const int64_t n_hits = P.n_hits = (int64_t)cw[8];
 	// 2. the length and the end row of every string (the counting walk of `get` over the rows 0 .. m - 1), and the string of every sentinel rank
 	if (n_hits > 0 || len != nullptr) {
 		HIPCHK(sc.dev(&d_rows, (size_t)m * 8));
@@ -6470,29 +6478,63 @@ int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len,
 			if (hl[r] >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP;
 		}
 	}
-	// 3. emit: where every string's records start, the strings that have any, and slices of them whose records sum to at most the budget, one with more alone
+	// 3. where every string's records start, and the strings that have any
+	if (n_hits == 0) return 0;
+	HIPCHK(sc.dev(&d_off, (size_t)(m + 1) * 8));
+	{
+		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, m + 1, h->st);
+		if (r < 0) return scan_err(r);
+		HIPCHK(sc.dev(&d_tmp, tmp_bytes + 256));
+		size_t tb = tmp_bytes + 256;
+		const int r2 = rb3kount_scan(d_tmp, &tb, d_cnt, d_off, m + 1, h->st); // (d_cnt[m] = 0: the entry behind the last string)
+		if (r2 < 0) return scan_err(r2);
+	}
+	std::vector<uint32_t> cnt((size_t)m), &em = P.em;
+	std::vector<int64_t> &eoff = P.eoff;
+	eoff.assign(1, 0);
+	HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)m * 4, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(h_ctr + 48, d_off + m, 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	for (int64_t r = 0; r < m; ++r)
+		if (cnt[(size_t)r] > 0u) em.push_back((uint32_t)r), eoff.push_back(eoff.back() + (int64_t)cnt[(size_t)r]);
+	const int64_t n_emitters = P.n_emitters = (int64_t)em.size();
+	if (eoff.back() != n_hits || (int64_t)h_ctr[48] != n_hits) return RB3GPU_EINTERNAL; // the scan on the device, the sum on the host and the walks' count are of the same records
+	HIPCHK(sc.dev(&d_em, (size_t)n_emitters * 4));
+	HIPCHK(hipMemcpyAsync(d_em, em.data(), (size_t)n_emitters * 4, hipMemcpyHostToDevice, h->st));
+	return 0;
+}
+
+int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_overlap_stats_t *st)
+{
+	static_assert(sizeof(OvlRec) == sizeof(rb3gpu_overlap_rec_t) && sizeof(OvlRec) == 16, "one record layout on both sides");
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || !cb || min_len < 1 || max_hits < 0) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1];
+	if (m <= 0) return RB3GPU_ESTATE; // (no index has no string)
+	if (m >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP; // (a string is 32 bits of a record)
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	const int64_t budget = h->tn.ovl_slice > 0 ? h->tn.ovl_slice : RB3_OVL_SLICE;
+	Scratch sc;
+	OvlPlan P;
+	if (const int e = ovl_plan(h, sc, min_len, max_hits, len, P)) return e;
+	const IdxView ix = view_of(h);
+	const int32_t min32 = P.min32;
+	const int64_t n_hits = P.n_hits, n_emitters = P.n_emitters;
+	const std::vector<int64_t> &eoff = P.eoff;
+	uint32_t *const d_cnt = P.d_cnt, *const d_who = P.d_who, *const d_len32 = P.d_len32, *const d_em = P.d_em;
+	int32_t *const d_last = P.d_last;
+	int64_t *const d_off = P.d_off;
+	unsigned long long *const d_ctr = P.d_ctr, *const h_ctr = P.h_ctr;
+	const unsigned long long *cw = h_ctr, *ce = h_ctr + 32;
+	const hipEvent_t e0 = P.e0, e1 = P.e1;
+	OvlRec *d_out = nullptr, *h_out = nullptr;
+	double ms_emit = 0;
+	int64_t n_slices = 0;
+	// emit: slices of the strings that have records whose records sum to at most the budget, one with more alone
 	int ret = 0;
 	if (n_hits > 0) {
-		HIPCHK(sc.dev(&d_off, (size_t)(m + 1) * 8));
-		{
-			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, m + 1, h->st);
-			if (r < 0) return scan_err(r);
-			HIPCHK(sc.dev(&d_tmp, tmp_bytes + 256));
-			size_t tb = tmp_bytes + 256;
-			const int r2 = rb3kount_scan(d_tmp, &tb, d_cnt, d_off, m + 1, h->st); // (d_cnt[m] = 0: the entry behind the last string)
-			if (r2 < 0) return scan_err(r2);
-		}
-		std::vector<uint32_t> cnt((size_t)m), em;
-		std::vector<int64_t> eoff(1, 0); // eoff[i]: the records in front of emitter i
-		HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)m * 4, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(h_ctr + 48, d_off + m, 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		for (int64_t r = 0; r < m; ++r)
-			if (cnt[(size_t)r] > 0u) em.push_back((uint32_t)r), eoff.push_back(eoff.back() + (int64_t)cnt[(size_t)r]);
-		n_emitters = (int64_t)em.size();
-		if (eoff.back() != n_hits || (int64_t)h_ctr[48] != n_hits) return RB3GPU_EINTERNAL; // the scan on the device, the sum on the host and the walks' count are of the same records
-		HIPCHK(sc.dev(&d_em, (size_t)n_emitters * 4));
-		HIPCHK(hipMemcpyAsync(d_em, em.data(), (size_t)n_emitters * 4, hipMemcpyHostToDevice, h->st));
 		int64_t out_cap = 0;
 		for (int64_t i0 = 0; i0 < n_emitters && ret == 0; ++n_slices) {
 			int64_t i1 = i0 + 1;
@@ -6525,9 +6567,150 @@ int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len,
 		}
 	}
 	if (st) {
-		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = ms_count, st->ms_who = ms_who, st->ms_emit = ms_emit;
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = P.ms_count, st->ms_who = P.ms_who, st->ms_emit = ms_emit;
 		st->n_strings = m, st->n_steps_count = (int64_t)cw[1], st->n_steps_emit = (int64_t)ce[1], st->n_early = (int64_t)cw[4], st->n_hits = n_hits, st->n_groups = (int64_t)cw[5];
 		st->n_capped_groups = (int64_t)cw[6], st->n_capped_hits = (int64_t)cw[7], st->n_emitters = n_emitters, st->n_slices = n_slices;
+	}
+	return ret;
+}
+
+/* ---- overlap --reduce: the irreducible overlaps (rb3gpu_reduce.h) --------------------------- */
+
+#define RB3_OVL_REDUCE_STRINGS ((int64_t)1 << 22)    // strings per launch of the reduction
+
+int rb3gpu_overlap_reduced(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_reduce_stats_t *st)
+{
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || !cb || min_len < 1 || max_hits < 0) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1];
+	if (m <= 0) return RB3GPU_ESTATE; // (no index has no string)
+	if (m >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP; // (a string is 32 bits of a record)
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	const int64_t budget = h->tn.ovl_slice > 0 ? h->tn.ovl_slice : RB3_OVL_SLICE;
+	Scratch sc;
+	OvlPlan P;
+	if (const int e = ovl_plan(h, sc, min_len, max_hits, len, P)) return e;
+	const IdxView ix = view_of(h);
+	const int64_t n = P.n_hits, ne = P.n_emitters;
+	const std::vector<uint32_t> &em = P.em;
+	const std::vector<int64_t> &eoff = P.eoff;
+	unsigned long long *const d_ctr = P.d_ctr, *const h_ctr = P.h_ctr; // [56, 59): the reduction, [59]: the inverse rank table, [60]: the scatter
+	const unsigned long long *cw = h_ctr, *ce = h_ctr + 32, *cr = h_ctr + 56;
+	double ms_emit = 0, ms_reduce = 0, ms_compact = 0;
+	int64_t n_kept = 0, n_slices = 0, resident = 0;
+	int ret = 0;
+	if (n > 0) {
+		if (h->tn.ovl_resident > 0 && n > h->tn.ovl_resident) return RB3GPU_EUNSUP; // (said by the caller, as the allocation below: the alternatives are its to name)
+		// 1. the resident array: every record at its scanned offset, written by launches of `per` strings each, and the sentinel rank of every string
+		OvlRec *d_rec = nullptr, *d_out = nullptr, *h_out = nullptr;
+		uint32_t *d_rank = nullptr, *d_keep = nullptr;
+		int64_t *d_pos = nullptr, *d_koff = nullptr;
+		void *d_tmp = nullptr;
+		size_t tmp_bytes = 0;
+		{
+			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, n + 1, h->st);
+			if (r < 0) return scan_err(r);
+		}
+		const size_t want[6] = { (size_t)n * sizeof(OvlRec), (size_t)m * 4, (size_t)(n + 1) * 4, (size_t)(n + 1) * 8, (size_t)(ne + 1) * 8, tmp_bytes + 256 };
+		void **const where[6] = { (void**)&d_rec, (void**)&d_rank, (void**)&d_keep, (void**)&d_pos, (void**)&d_koff, &d_tmp };
+		for (int i = 0; i < 6; ++i) {
+			if (sc.dev(where[i], want[i]) != hipSuccess) { // (too many records for this device: a larger min_len, a cap, or rb3gpu_overlap)
+				(void)hipGetLastError();
+				return RB3GPU_ENOMEM;
+			}
+			resident += (int64_t)want[i];
+		}
+		const auto first_emitter = [&](int64_t r) { return (int64_t)(std::lower_bound(em.begin(), em.end(), (uint32_t)r) - em.begin()); }; // the first one that is string r or behind it
+		const int64_t per = std::min(m, h->tn.ovl_strings > 0 ? h->tn.ovl_strings : RB3_OVL_STRINGS);
+		HIPCHK(hipMemsetAsync(d_rank, 0xFF, (size_t)m * 4, h->st));
+		HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)(n + 1) * 4, h->st)); // (keep[n] = 0: the entry behind the last record)
+		HIPCHK(hipEventRecord(P.e0, h->st));
+		hipLaunchKernelGGL(k_ovl_rank, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->st, m, (const uint32_t*)P.d_who, d_rank, d_ctr + 59);
+		HIPCHK(hipEventRecord(P.e1, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		ms_emit += ev_ms(P.e0, P.e1);
+		for (int64_t r0 = 0; r0 < m; r0 += per) {
+			const int64_t i0 = first_emitter(r0), i1 = first_emitter(std::min(m, r0 + per));
+			if (i0 == i1) continue;
+			HIPCHK(hipMemsetAsync(d_ctr + 32, 0, 8, h->st));
+			const int64_t nb = std::min<int64_t>(((i1 - i0) * 8 + 255) / 256, 4096);
+			HIPCHK(hipEventRecord(P.e0, h->st));
+			hipLaunchKernelGGL(k_ovl_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, i0, i1, P.min32, max_hits, 0, (const uint32_t*)P.d_em, P.d_cnt, P.d_last,
+					(const int64_t*)P.d_off, (int64_t)0, (const uint32_t*)P.d_who, (const uint32_t*)P.d_len32, d_rec, n, d_ctr + 32);
+			HIPCHK(hipEventRecord(P.e1, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_emit += ev_ms(P.e0, P.e1);
+		}
+		// 2. reduce: an octet per record, launches of the records of `rper` strings each
+		const int64_t rper = std::min(m, h->tn.ovl_reduce_strings > 0 ? h->tn.ovl_reduce_strings : RB3_OVL_REDUCE_STRINGS);
+		for (int64_t r0 = 0; r0 < m; r0 += rper) {
+			const int64_t j0 = eoff[(size_t)first_emitter(r0)], j1 = eoff[(size_t)first_emitter(std::min(m, r0 + rper))];
+			if (j0 == j1) continue;
+			const int64_t nb = std::min<int64_t>(((j1 - j0) * 8 + 255) / 256, (int64_t)1 << 16);
+			HIPCHK(hipEventRecord(P.e0, h->st));
+			hipLaunchKernelGGL(k_ovl_reduce, dim3((unsigned)nb), dim3(256), 0, h->st, (const OvlRec*)d_rec, (const int64_t*)P.d_off, (const uint32_t*)d_rank, m, n, j0, j1, d_keep, d_ctr + 56);
+			HIPCHK(hipEventRecord(P.e1, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_reduce += ev_ms(P.e0, P.e1);
+		}
+		// 3. compact: where every kept record goes, the kept records in front of every string that has records
+		HIPCHK(hipEventRecord(P.e0, h->st));
+		{
+			size_t tb = tmp_bytes + 256;
+			const int r = rb3kount_scan(d_tmp, &tb, d_keep, d_pos, n + 1, h->st);
+			if (r < 0) return scan_err(r);
+		}
+		hipLaunchKernelGGL(k_ovl_koff, dim3((unsigned)((ne + 256) / 256)), dim3(256), 0, h->st, ne, (const uint32_t*)P.d_em, m, n, (const int64_t*)P.d_off, (const int64_t*)d_pos, d_koff);
+		HIPCHK(hipEventRecord(P.e1, h->st));
+		std::vector<int64_t> koff((size_t)ne + 1);
+		HIPCHK(hipMemcpyAsync(koff.data(), d_koff, (size_t)(ne + 1) * 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipMemcpyAsync(h_ctr + 32, d_ctr + 32, 256, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_compact += ev_ms(P.e0, P.e1);
+		n_kept = koff[(size_t)ne];
+		bool sound = ce[2] == 0 && ce[3] == 0 && ce[10] == 0 && (int64_t)ce[8] == n && cr[2] == 0 && cr[3] == 0 && koff[0] == 0 && (int64_t)cr[1] == n_kept && (int64_t)(cr[0] + cr[1]) == n;
+		for (int64_t i = 0; i < ne && sound; ++i) sound = koff[(size_t)i + 1] > koff[(size_t)i]; // the deepest group of a string is never reducible
+		if (!sound) {
+			if (h->opt.verbose >= 1)
+				fprintf(stderr, "[E::rb3gpu] overlap: of %lld records %llu were stored (%llu strings differ), %llu reduced, %llu kept and %llu left alone; the scan has %lld kept\n",
+						(long long)n, ce[8], ce[10], cr[0], cr[1], cr[2], (long long)n_kept);
+			return RB3GPU_EINTERNAL;
+		}
+		// 4. slices of consecutive strings whose kept records sum to at most the budget, one with more alone
+		int64_t out_cap = 0;
+		for (int64_t i0 = 0; i0 < ne && ret == 0; ++n_slices) {
+			int64_t i1 = i0 + 1;
+			while (i1 < ne && koff[(size_t)i1 + 1] - koff[(size_t)i0] <= budget) ++i1;
+			const int64_t tot = koff[(size_t)i1] - koff[(size_t)i0], j0 = eoff[(size_t)i0], j1 = eoff[(size_t)i1];
+			if (tot > out_cap) { // (grows to the largest slice: the budget, or the one string that exceeds it)
+				out_cap = 0;
+				const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 16));
+				HIPCHK(sc.regrow(&d_out, &h_out, (size_t)oc * sizeof(OvlRec)));
+				out_cap = oc;
+			}
+			HIPCHK(hipEventRecord(P.e0, h->st));
+			hipLaunchKernelGGL(k_ovl_compact, dim3((unsigned)((j1 - j0 + 255) / 256)), dim3(256), 0, h->st, (const OvlRec*)d_rec, (const uint32_t*)d_keep, (const int64_t*)d_pos, j0, j1,
+					koff[(size_t)i0], d_out, tot, d_ctr + 60);
+			HIPCHK(hipEventRecord(P.e1, h->st));
+			HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)tot * sizeof(OvlRec), hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipMemcpyAsync(h_ctr + 60, d_ctr + 60, 8, hipMemcpyDeviceToHost, h->st));
+			HIPCHK(hipStreamSynchronize(h->st));
+			HIPCHK(hipGetLastError());
+			ms_compact += ev_ms(P.e0, P.e1);
+			if (cr[4] != 0) return RB3GPU_EINTERNAL;
+			ret = cb(ud, tot, (const rb3gpu_overlap_rec_t*)h_out);
+			i0 = i1;
+		}
+	}
+	if (st) {
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = P.ms_count, st->ms_who = P.ms_who, st->ms_emit = ms_emit, st->ms_reduce = ms_reduce, st->ms_compact = ms_compact;
+		st->n_strings = m, st->n_hits = n, st->n_kept = n_kept, st->n_groups = (int64_t)cw[5], st->n_capped_groups = (int64_t)cw[6], st->n_capped_hits = (int64_t)cw[7];
+		st->n_emitters = ne, st->n_slices = n_slices, st->resident_bytes = resident;
 	}
 	return ret;
 }

@@ -194,6 +194,16 @@ class OverlapStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ReduceStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_count", ctypes.c_double), ("ms_who", ctypes.c_double), ("ms_emit", ctypes.c_double), ("ms_reduce", ctypes.c_double),
+                ("ms_compact", ctypes.c_double), ("n_strings", ctypes.c_int64), ("n_hits", ctypes.c_int64), ("n_kept", ctypes.c_int64), ("n_groups", ctypes.c_int64),
+                ("n_capped_groups", ctypes.c_int64), ("n_capped_hits", ctypes.c_int64), ("n_emitters", ctypes.c_int64), ("n_slices", ctypes.c_int64),
+                ("resident_bytes", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FetchStats(ctypes.Structure):
     _fields_ = [("ms_total", ctypes.c_double), ("ms_table", ctypes.c_double), ("ms_plan", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_regions", ctypes.c_int64),
                 ("n_symbols", ctypes.c_int64), ("n_walkers", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_steps", ctypes.c_int64), ("max_walk_steps", ctypes.c_int64),
@@ -334,6 +344,7 @@ SYMBOLS = {
     "rb3gpu_remove": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RemoveStats)]),
     "rb3gpu_dedup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DedupStats)]),
     "rb3gpu_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, OVERLAP_F, ctypes.c_void_p, ctypes.POINTER(OverlapStats)]),
+    "rb3gpu_overlap_reduced": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, OVERLAP_F, ctypes.c_void_p, ctypes.POINTER(ReduceStats)]),
     "rb3gpu_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), FETCH_F, ctypes.c_void_p, ctypes.POINTER(FetchStats)]),
 }
 
@@ -1061,11 +1072,12 @@ class Rb3Gpu:
             stats.update(st.as_dict())
         return (kind[:nu], keeper[:nu], rec[:m]) if records else (kind[:nu], keeper[:nu])
 
-    def overlap(self, min_len, max_hits=0, stats=None, lengths=False):
+    def overlap(self, min_len, max_hits=0, stats=None, lengths=False, reduce=False):
         """rb3gpu_overlap: the suffix-prefix overlaps of all the strings of the index: one structured array (OVERLAP_REC) of the records (a, b, len, len_b) -- the last
         len symbols of string a are the first len of string b, min_len <= len < the length of a, len_b the length of b -- ordered by a, then longest first, then in
         the index's order of the partners.  max_hits > 0 leaves out every group of more than max_hits partners of one (a, len).  lengths=True: (records, the length of
-        every string, int64).  stats: a dict that receives rb3gpu_overlap_stats_t"""
+        every string, int64).  stats: a dict that receives rb3gpu_overlap_stats_t.  reduce=True: rb3gpu_overlap_reduced, only the irreducible records -- those that no
+        two longer ones imply -- in the same order; stats then receives rb3gpu_reduce_stats_t"""
         got = []
 
         def cb(_ud, n, recs):
@@ -1073,8 +1085,8 @@ class Rb3Gpu:
             return 0
         m = int(self.get_acc()[1])
         ln = np.zeros(max(m, 1), dtype=np.int64) if lengths else None
-        st = OverlapStats()
-        self._chk(self._lib.rb3gpu_overlap(self._h, int(min_len), int(max_hits), ln.ctypes.data if lengths else None, OVERLAP_F(cb), None, ctypes.byref(st)), "rb3gpu_overlap")
+        st, name = (ReduceStats(), "rb3gpu_overlap_reduced") if reduce else (OverlapStats(), "rb3gpu_overlap")
+        self._chk(getattr(self._lib, name)(self._h, int(min_len), int(max_hits), ln.ctypes.data if lengths else None, OVERLAP_F(cb), None, ctypes.byref(st)), name)
         if stats is not None:
             stats.update(st.as_dict())
         rec = np.concatenate(got) if got else np.zeros(0, dtype=OVERLAP_REC)
