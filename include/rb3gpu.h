@@ -802,6 +802,22 @@ int rb3gpu_stream_sync(void *stream);
  * -DRB3GPU_TEST_HOOKS, librb3gpu_hooks.so); the release library answers RB3GPU_EUNSUP.  Unknown key: RB3GPU_EINVAL. */
 int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value);
 
+/* Test seam of the merge's settle phase (test build only; the release library answers RB3GPU_EUNSUP).  The caller hands over a
+ * table of tentative stretches as the walkers of a merge would have left it, and the settle runs on it through the host functions a merge calls.
+ *   ids[n_ids] (ascending), records: the stretch ids in use and their 64-byte records (rb3_stretch_t, csrc/rb3gpu_kernels.h); every other id is zero;
+ *   masks: NULL, or for q > 1 the 8q mask words of every listed id (those of ids of the upper half are ignored);
+ *   n_a, n_b: the extents of the two halves of the table; chunk_ctr: NULL, or the 64 chunk counters the extent of the lower half is worked out from
+ *   instead of n_a (the path of a merge with narrow masks: the first settle kernel does it on its way);
+ *   q: 1, 2, 4, 8 (masks of 256 q bits); maxhops: walkers a dependency path is followed over before the second chance takes it;
+ *   engine: 0 = the merge's own (the settle kernels, then pointer jumping if a path was longer than maxhops), 1 = "resolve_v1" (q = 1 only);
+ *   phase: 0 = only the masks of the events, worked out from the handle's index; 1 = everything else, the masks taken as given; 2 = everything.
+ * Out: sfin_out[n_ids] (0: unsettled, else 1 + the unknown), masks_out (NULL, or 8q words per id: what the phase left behind -- per event after phase 0,
+ * cumulative after the others), bad_out[3] (the counters of the validation; [2] != 0: a path was longer than maxhops), *second_chance (it ran).
+ * RB3GPU_EINVAL for a table that names an id outside the extents or an interval outside the index: nothing malformed reaches the device.  The handle
+ * stays usable (its bookkeeping of the table's used part is kept). */
+int rb3gpu_test_settle(rb3gpu_t *h, int64_t n_ids, const int32_t *ids, const void *records, const uint32_t *masks, int64_t n_a, int64_t n_b, const uint32_t *chunk_ctr,
+		int q, int maxhops, int engine, int phase, int32_t *sfin_out, uint32_t *masks_out, uint64_t *bad_out, int *second_chance);
+
 int rb3gpu_stats(const rb3gpu_t *h, rb3gpu_stats_t *st);
 /* what the handle holds right now, buffer by buffer (diagnostics: which scratch makes up bytes_peak): i = 0, 1, ... until RB3GPU_EINVAL; *name is a static
  * string.  (No counterpart in the reference: its memory is the rope's, mrope.c:15-34.) */

@@ -597,13 +597,17 @@ static int tent_masks(rb3gpu_t *h, int q, uint32_t **mx)
 
 /* the settle kernels behind k_chain: the rows that dropped at every event, per walker the cumulative mask, the paths over first
  * stretches (up to maxhops hops), all other stretches */
-static void launch_settle(rb3gpu_t *h, const IdxView &iv, rb3_stretch_t *tab, uint32_t *mx, const uint32_t *sidctr, int32_t *sfin, unsigned long long *bad, int maxhops, int q, const uint32_t *mctr = nullptr)
+/* phase (the test seam rb3gpu_test_settle only; a merge runs everything): 0 = the masks of the events and nothing else, 1 = everything but them (the masks in
+ * the table are taken as they are) */
+static void launch_settle(rb3gpu_t *h, const IdxView &iv, rb3_stretch_t *tab, uint32_t *mx, const uint32_t *sidctr, int32_t *sfin, unsigned long long *bad, int maxhops, int q, const uint32_t *mctr = nullptr, int phase = 2)
 {
+	const bool ev = phase != 1, rest = phase != 0;
 	// mctr: the extent of the stretch ids in use has not been worked out yet (k_tent_extent); the first kernel of the narrow-mask settle does it on its way
-	const bool fused_extent = mctr != nullptr && !(q >= 2 && mx) && !h->tn.resolve_v1;
+	const bool fused_extent = mctr != nullptr && !(q >= 2 && mx) && !h->tn.resolve_v1 && ev;
 	if (mctr != nullptr && !fused_extent) hipLaunchKernelGGL(k_tent_extent, dim3(1), dim3(64), 0, h->st, mctr, (uint32_t*)sidctr);
 #define RB3_SETTLE_X(Q) do { \
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_events_x<Q>), dim3(2048), dim3(256), 0, h->st, iv, (const rb3_stretch_t*)tab, mx, sidctr); \
+		if (ev) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_events_x<Q>), dim3(2048), dim3(256), 0, h->st, iv, (const rb3_stretch_t*)tab, mx, sidctr); \
+		if (!rest) break; \
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cum_x<Q>), dim3(4096), dim3(64), 0, h->st, tab, mx, sidctr); \
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resolve_w_x<Q>), dim3(512), dim3(256), 0, h->st, tab, (const uint32_t*)mx, sidctr, sfin, bad, maxhops); \
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sfin_x<Q>), dim3(2048), dim3(256), 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)mx, sidctr, sfin); \
@@ -612,8 +616,9 @@ static void launch_settle(rb3gpu_t *h, const IdxView &iv, rb3_stretch_t *tab, ui
 	else if (q >= 4 && mx) RB3_SETTLE_X(4);
 	else if (q >= 2 && mx) RB3_SETTLE_X(2);
 	else {
-		hipLaunchKernelGGL(k_events, dim3((unsigned)h->tn.ev_blocks), dim3(256), 0, h->st, iv, tab, sidctr, fused_extent ? mctr : (const uint32_t*)nullptr, (uint32_t*)sidctr);
-		if (h->tn.resolve_v1) hipLaunchKernelGGL(k_resolve, dim3(2048), dim3(256), 0, h->st, tab, sidctr, sfin);
+		if (ev) hipLaunchKernelGGL(k_events, dim3((unsigned)h->tn.ev_blocks), dim3(256), 0, h->st, iv, tab, sidctr, fused_extent ? mctr : (const uint32_t*)nullptr, (uint32_t*)sidctr);
+		if (!rest) ;
+		else if (h->tn.resolve_v1) hipLaunchKernelGGL(k_resolve, dim3(2048), dim3(256), 0, h->st, tab, sidctr, sfin);
 		else {
 			hipLaunchKernelGGL(k_cum, dim3((unsigned)h->tn.cum_blocks), dim3(256), 0, h->st, tab, sidctr);
 			hipLaunchKernelGGL(k_resolve_w, dim3((unsigned)h->tn.resw_blocks), dim3(256), 0, h->st, tab, sidctr, sfin, bad, maxhops);
@@ -621,6 +626,44 @@ static void launch_settle(rb3gpu_t *h, const IdxView &iv, rb3_stretch_t *tab, ui
 		}
 	}
 #undef RB3_SETTLE_X
+}
+
+/* The settle's second chance: dependency paths longer than k_resolve_w follows (bad[2] != 0: a string that repeats indexed text), settled by pointer jumping
+ * over the walkers, then every other stretch once more.  settle_long_nodes: the nodes of the extents the merge read back (tent_used), and their scratch. */
+static int settle_long_nodes(rb3gpu_t *h, int tq, int64_t *nn)
+{
+	const int64_t na = h->sid_dirty[0], nb = h->sid_dirty[1], nblk = (na + RB3_TENT_BLOCK - 1) / RB3_TENT_BLOCK;
+	const size_t wj_bytes = tq > 1 ? 32 * (size_t)tq + 16 : sizeof(WjNode);
+	*nn = nblk + nb;
+	return *nn > 0 ? buf_ensure(h, h->xbuf, (size_t)*nn * 2 * wj_bytes) : 0;
+}
+
+static void launch_settle_long(rb3gpu_t *h, rb3_stretch_t *tab, uint32_t *mx, const uint32_t *sidctr, int32_t *sfin, int tq)
+{
+	const int64_t na = h->sid_dirty[0], nb = h->sid_dirty[1], nblk = (na + RB3_TENT_BLOCK - 1) / RB3_TENT_BLOCK, nn = nblk + nb;
+	const dim3 gj((unsigned)((nn + 255) / 256)), bj(256);
+#define RB3_WJ_X(Q) do { \
+		WjNodeX<Q> *nd[2] = { (WjNodeX<Q>*)h->xbuf.p, (WjNodeX<Q>*)h->xbuf.p + nn }; \
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wj_init_x<Q>), gj, bj, 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)mx, (const int32_t*)sfin, nblk, nb, nd[0]); \
+		int cur = 0; \
+		for (int64_t reach = 1; reach <= nn; reach <<= 1, cur ^= 1) \
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wj_round_x<Q>), gj, bj, 0, h->st, nn, (const WjNodeX<Q>*)nd[cur], nd[cur ^ 1]); \
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wj_apply_x<Q>), gj, bj, 0, h->st, nblk, nb, (const WjNodeX<Q>*)nd[cur], sfin); \
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sfin_x<Q>), dim3(2048), dim3(256), 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)mx, (const uint32_t*)sidctr, sfin); \
+	} while (0)
+	if (tq >= 8) RB3_WJ_X(8);
+	else if (tq >= 4) RB3_WJ_X(4);
+	else if (tq >= 2) RB3_WJ_X(2);
+	else {
+		WjNode *nd[2] = { (WjNode*)h->xbuf.p, (WjNode*)h->xbuf.p + nn };
+		hipLaunchKernelGGL(k_wj_init, gj, bj, 0, h->st, (const rb3_stretch_t*)tab, (const int32_t*)sfin, nblk, nb, nd[0]);
+		int cur = 0;
+		for (int64_t reach = 1; reach <= nn; reach <<= 1, cur ^= 1)
+			hipLaunchKernelGGL(k_wj_round, gj, bj, 0, h->st, nn, (const WjNode*)nd[cur], nd[cur ^ 1]);
+		hipLaunchKernelGGL(k_wj_apply, gj, bj, 0, h->st, nblk, nb, (const WjNode*)nd[cur], sfin);
+		hipLaunchKernelGGL(k_sfin, dim3(2048), dim3(256), 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)sidctr, sfin);
+	}
+#undef RB3_WJ_X
 }
 
 #define RB3_GRP_ALLOC (sizeof(rb3_grp_t) + 8) /* bytes per directory entry of an index buffer: the entry + its word of the compact copy */
@@ -2183,34 +2226,11 @@ static int merge_core(rb3gpu_t *h, int64_t len, const uint8_t *d_b2, int commit,
 			) {
 		// Second chance: dependency paths longer than k_resolve_w follows (a string that repeats indexed text).  Nothing was installed
 		// and the unsettled records are still in pos[]: settle them by pointer jumping over the walkers, then validate and rebuild again.
-		const int64_t na = h->sid_dirty[0], nb = h->sid_dirty[1], nblk = (na + RB3_TENT_BLOCK - 1) / RB3_TENT_BLOCK, nn = nblk + nb;
-		const size_t wj_bytes = tq > 1 ? 32 * (size_t)tq + 16 : sizeof(WjNode);
-		if (nn > 0 && (r = buf_ensure(h, h->xbuf, (size_t)nn * 2 * wj_bytes)) < 0) return r;
+		int64_t nn = 0;
+		if ((r = settle_long_nodes(h, tq, &nn)) < 0) return r;
 		if (nn > 0) {
 			HIPCHK(hipEventRecord(h->ev[4], h->st));
-			const dim3 gj((unsigned)((nn + 255) / 256)), bj(256);
-#define RB3_WJ_X(Q) do { \
-				WjNodeX<Q> *nd[2] = { (WjNodeX<Q>*)h->xbuf.p, (WjNodeX<Q>*)h->xbuf.p + nn }; \
-				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wj_init_x<Q>), gj, bj, 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)mx, (const int32_t*)sfin, nblk, nb, nd[0]); \
-				int cur = 0; \
-				for (int64_t reach = 1; reach <= nn; reach <<= 1, cur ^= 1) \
-					hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wj_round_x<Q>), gj, bj, 0, h->st, nn, (const WjNodeX<Q>*)nd[cur], nd[cur ^ 1]); \
-				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wj_apply_x<Q>), gj, bj, 0, h->st, nblk, nb, (const WjNodeX<Q>*)nd[cur], sfin); \
-				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sfin_x<Q>), dim3(2048), dim3(256), 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)mx, (const uint32_t*)sidctr, sfin); \
-			} while (0)
-			if (tq >= 8) RB3_WJ_X(8);
-			else if (tq >= 4) RB3_WJ_X(4);
-			else if (tq >= 2) RB3_WJ_X(2);
-			else {
-			WjNode *nd[2] = { (WjNode*)h->xbuf.p, (WjNode*)h->xbuf.p + nn };
-			hipLaunchKernelGGL(k_wj_init, gj, bj, 0, h->st, (const rb3_stretch_t*)tab, (const int32_t*)sfin, nblk, nb, nd[0]);
-			int cur = 0;
-			for (int64_t reach = 1; reach <= nn; reach <<= 1, cur ^= 1)
-				hipLaunchKernelGGL(k_wj_round, gj, bj, 0, h->st, nn, (const WjNode*)nd[cur], nd[cur ^ 1]);
-			hipLaunchKernelGGL(k_wj_apply, gj, bj, 0, h->st, nblk, nb, (const WjNode*)nd[cur], sfin);
-			hipLaunchKernelGGL(k_sfin, dim3(2048), dim3(256), 0, h->st, (const rb3_stretch_t*)tab, (const uint32_t*)sidctr, sfin);
-			}
-#undef RB3_WJ_X
+			launch_settle_long(h, tab, mx, (const uint32_t*)sidctr, sfin, tq);
 			HIPCHK(hipMemsetAsync(misc + 2, 0, 24, h->st));
 			if (rows_fused) {
 				HIPCHK(hipMemsetAsync(h->jg.p, 0, (size_t)(nwin + 1) * 8, h->st));
@@ -2387,6 +2407,98 @@ static int merge_core(rb3gpu_t *h, int64_t len, const uint8_t *d_b2, int commit,
 		fprintf(stderr, "[M::%s::%.3f] merged %lld symbols (%lld strings): lf %.3f ms, rank %.3f ms (%llu LF steps), rebuild %.3f ms\n", __func__,
 				now_s() - h->t0, (long long)len, (long long)acc2[1], ev_ms(h->ev[0], ev_rank0), ev_ms(ev_rank0, h->ev[2]), hm[1], ev_ms(h->ev[2], h->ev[3]));
 	return 0;
+}
+
+/* Test seam (include/rb3gpu.h): the settle of a merge on a stretch table the caller made, through the host functions merge_core calls. */
+int rb3gpu_test_settle(rb3gpu_t *h, int64_t n_ids, const int32_t *ids, const void *records, const uint32_t *masks, int64_t n_a, int64_t n_b, const uint32_t *chunk_ctr,
+		int q, int maxhops, int engine, int phase, int32_t *sfin_out, uint32_t *masks_out, uint64_t *bad_out, int *second_chance)
+{
+#ifndef RB3GPU_TEST_HOOKS
+	(void)h; (void)n_ids; (void)ids; (void)records; (void)masks; (void)n_a; (void)n_b; (void)chunk_ctr; (void)q; (void)maxhops; (void)engine; (void)phase;
+	(void)sfin_out; (void)masks_out; (void)bad_out; (void)second_chance;
+	return RB3GPU_EUNSUP; // test hooks are compiled out of the release library
+#else
+	if (!h || n_ids <= 0 || !ids || !records || !sfin_out || !bad_out || !second_chance) return RB3GPU_EINVAL;
+	if ((q != 1 && q != 2 && q != 4 && q != 8) || maxhops < 0 || maxhops > RB3_TENT_IDS || engine < 0 || engine > 1 || phase < 0 || phase > 2) return RB3GPU_EINVAL;
+	if (engine == 1 && q != 1) return RB3GPU_EINVAL; // k_resolve knows the masks inside the records only
+	if (h->mg_active) return RB3GPU_ESTATE;
+	if (phase != 1 && h->n <= 0) return RB3GPU_ESTATE; // k_events reads the index
+	uint32_t hctr[RB3_TENT_NCTR];
+	if (chunk_ctr) { // the extent of the lower half as the walkers leave it: the chunk counters (k_tent_extent)
+		uint32_t mxc = 0;
+		for (int c = 0; c < RB3_TENT_NCTR; ++c) hctr[c] = chunk_ctr[c], mxc = chunk_ctr[c] > mxc ? chunk_ctr[c] : mxc;
+		if (mxc > (uint32_t)(RB3_TENT_HALF / (RB3_TENT_NCTR * RB3_TENT_CHUNK))) return RB3GPU_EINVAL;
+		n_a = (int64_t)mxc * RB3_TENT_NCTR * RB3_TENT_CHUNK;
+	}
+	if (n_a < 0 || n_a > RB3_TENT_HALF || n_b < 0 || n_b >= RB3_TENT_POISON - RB3_TENT_HALF) return RB3GPU_EINVAL;
+	const int nw = 8 * q, dmax = 256 * q - 1;
+	const rb3_stretch_t *rec = (const rb3_stretch_t*)records;
+	auto listed = [&](int64_t id) { return (id >= 0 && id < n_a) || (id >= RB3_TENT_HALF && id < RB3_TENT_HALF + n_b); };
+	for (int64_t i = 0; i < n_ids; ++i) { // nothing reaches the device that could take a kernel outside the table or the index
+		const rb3_stretch_t &t = rec[i];
+		if (!listed(ids[i]) || (i > 0 && ids[i] <= ids[i - 1])) return RB3GPU_EINVAL;
+		const uint64_t type = t.w0 >> 62;
+		const int64_t prev = RB3_DEP_PREV(t.w0);
+		if (type != 0 && type != RB3_DEP_EVENT && type != RB3_DEP_LINK) return RB3GPU_EINVAL;
+		if (type != 0 && !listed(prev)) return RB3GPU_EINVAL;
+		if (type == RB3_DEP_EVENT) {
+			const int64_t lo = (int64_t)(t.w0 & (uint64_t)RB3_TENT_MASK), kk = (int64_t)(t.w1 & 0xFFFF);
+			if (ids[i] >= RB3_TENT_HALF || kk < 2 || kk > dmax || (phase != 1 && lo + kk > h->n)) return RB3GPU_EINVAL;
+			if (t.pad[0] == 0u || !listed((int64_t)t.pad[0] - 1) || (int64_t)t.pad[0] - 1 >= RB3_TENT_HALF) return RB3GPU_EINVAL;
+		} else if (t.pad[0] != 0u && (t.pad[0] & RB3_FIRSTFLAG)) return RB3GPU_EINVAL; // (k_cum's mark: never in a table as the walkers leave it)
+		else if (t.pad[0] != 0u && !listed((int64_t)t.pad[0] - 1)) return RB3GPU_EINVAL;
+		if (t.child < 0 || (t.child > 0 && !listed((int64_t)t.child - 1))) return RB3GPU_EINVAL;
+		if (t.del < 0 || t.del > dmax + 1 || t.pad[1] != 0u) return RB3GPU_EINVAL;
+	}
+	int r;
+	HIPCHK(hipSetDevice(h->dev));
+	rb3_stretch_t *tab = nullptr;
+	int32_t *sfin = nullptr;
+	uint32_t *mx = nullptr;
+	if ((r = tent_prepare(h, &tab, &sfin)) < 0) return r;
+	if ((r = tent_masks(h, q, &mx)) < 0) return r;
+	if ((r = buf_ensure(h, h->misc, MISC_WORDS * 8)) < 0) return r;
+	unsigned long long *misc = (unsigned long long*)h->misc.p;
+	uint32_t *sidctr = (uint32_t*)(misc + 5), *mctr = (uint32_t*)(misc + MISC_MCTR);
+	HIPCHK(hipMemsetAsync(misc, 0, MISC_WORDS * 8, h->st));
+	if (mx && n_a > 0) HIPCHK(hipMemsetAsync(mx, 0, (size_t)n_a * 4 * (size_t)nw, h->st));
+	for (int64_t i = 0, j; i < n_ids; i = j) { // runs of consecutive ids: one copy each
+		for (j = i + 1; j < n_ids && ids[j] == ids[j - 1] + 1; ++j) {}
+		HIPCHK(hipMemcpyAsync(tab + ids[i], rec + i, (size_t)(j - i) * sizeof(rb3_stretch_t), hipMemcpyHostToDevice, h->st));
+		if (mx && masks && ids[i] < RB3_TENT_HALF)
+			HIPCHK(hipMemcpyAsync(mx + (int64_t)ids[i] * nw, masks + i * nw, (size_t)(j - i) * 4 * (size_t)nw, hipMemcpyHostToDevice, h->st));
+	}
+	const uint32_t ext[2] = { chunk_ctr ? 0u : (uint32_t)n_a, (uint32_t)n_b };
+	HIPCHK(hipMemcpyAsync(sidctr, ext, 8, hipMemcpyHostToDevice, h->st));
+	if (chunk_ctr) HIPCHK(hipMemcpy2DAsync(mctr, 128, hctr, 4, 4, RB3_TENT_NCTR, hipMemcpyHostToDevice, h->st)); // (a counter per 128 bytes)
+	const int v1 = h->tn.resolve_v1;
+	h->tn.resolve_v1 = engine == 1;
+	launch_settle(h, view_of(h), tab, mx, (const uint32_t*)sidctr, sfin, misc + 2, maxhops, q, chunk_ctr ? (const uint32_t*)mctr : (const uint32_t*)nullptr, phase);
+	h->tn.resolve_v1 = v1;
+	unsigned long long hm[6];
+	HIPCHK(hipMemcpyAsync(hm, misc, sizeof(hm), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipGetLastError());
+	tent_used(h, hm[5]); // what the next tent_prepare has to clear
+	if (h->sid_dirty[0] != n_a || h->sid_dirty[1] != n_b) return RB3GPU_EINTERNAL;
+	*second_chance = 0;
+	if (engine == 0 && phase != 0 && hm[4] != 0) { // as merge_core: a path longer than maxhops
+		int64_t nn = 0;
+		if ((r = settle_long_nodes(h, q, &nn)) < 0) return r;
+		if (nn > 0) launch_settle_long(h, tab, mx, (const uint32_t*)sidctr, sfin, q), *second_chance = 1;
+	}
+	for (int64_t i = 0, j; i < n_ids; i = j) {
+		for (j = i + 1; j < n_ids && ids[j] == ids[j - 1] + 1; ++j) {}
+		HIPCHK(hipMemcpyAsync(sfin_out + i, sfin + ids[i], (size_t)(j - i) * 4, hipMemcpyDeviceToHost, h->st));
+		if (!masks_out) continue;
+		if (mx && ids[i] < RB3_TENT_HALF) HIPCHK(hipMemcpyAsync(masks_out + i * nw, mx + (int64_t)ids[i] * nw, (size_t)(j - i) * 4 * (size_t)nw, hipMemcpyDeviceToHost, h->st));
+		else if (!mx) HIPCHK(hipMemcpy2DAsync(masks_out + i * nw, 32, tab[ids[i]].mask, sizeof(rb3_stretch_t), 32, (size_t)(j - i), hipMemcpyDeviceToHost, h->st));
+		else memset(masks_out + i * nw, 0, (size_t)(j - i) * 4 * (size_t)nw); // (single ids have no wide mask)
+	}
+	HIPCHK(hipStreamSynchronize(h->st));
+	for (int k = 0; k < 3; ++k) bad_out[k] = hm[2 + k];
+	return 0;
+#endif
 }
 
 /* host -> HBM copy of a partial BWT through two pinned staging buffers: the CPU copies chunk i+1

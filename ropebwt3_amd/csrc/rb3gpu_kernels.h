@@ -1958,8 +1958,10 @@ __global__ void __launch_bounds__(256) k_resolve(rb3_stretch_t *tab, const uint3
  * first stretches only (d_0 of the next walker = d_last of this one + the link's offset) -- 3 to 24 hops where k_resolve
  * followed up to 1400 stretches one after the other --, and all other stretches are filled in parallel (k_sfin).
  * Record fields used: pad[0] of an event stretch = 1 + the walker's first stretch (written by the walker); of a first stretch,
- * after k_cum: RB3_FIRSTFLAG | 1 + the first stretch of the walker it links into; pad[1] = 1 + the walker's last stretch; mask[] of
- * a first stretch = the cumulative mask of the last one. */
+ * after k_cum: RB3_FIRSTFLAG | 1 + the first stretch of the walker it links into; pad[1] = 1 + the walker's last stretch -- the last one k_cum
+ * REACHED: a follower's link written into an event stretch replaces the event, the sequence ends in front of it, and the event stretches behind
+ * it keep the per-event masks of k_events, which k_sfin must not take for cumulative ones; pad[1] of an event stretch = 1 once k_cum has reached
+ * it and made its mask cumulative (k_sfin leaves the others unsettled); mask[] of a first stretch = the cumulative mask of the last one. */
 #define RB3_FIRSTFLAG 0x80000000u
 #define RB3_RESW_MAXHOPS 64
 
@@ -2041,6 +2043,7 @@ __global__ void __launch_bounds__(256) k_cum(rb3_stretch_t *tab, const uint32_t 
 				}
 				wave_sync();
 				tab[base + o].mask[j] = cumL[j]; // cumulative, first-interval coordinates
+				if (j == 0) tab[base + o].pad[1] = 1u; // ... and k_sfin may use it (an event stretch this loop never reaches keeps 0 and stays unsettled)
 				// A follower that knew more may have settled THIS stretch (del) without ever seeing a record of the first one -- it ran so
 				// closely behind the walker that those records were not visible yet, and recorded over them.  d_t, the unknown here, counts
 				// the survivors below the new suffix; the unknown d_0 of the first stretch is a position whose number of survivors (zeros of
@@ -2177,7 +2180,9 @@ __global__ void __launch_bounds__(256) k_wj_init(const rb3_stretch_t *tab, const
 				const int pl = RB3_DEP_PREV(w0); // the LAST stretch of the walker that ran into this one
 				const uint32_t hp = tab[pl].pad[0];
 				const int pf = (hp == 0u || (hp & RB3_FIRSTFLAG)) ? pl : (int)hp - 1;
-				if (pf >= 0 && pf < RB3_TENT_IDS && (pf >= RB3_TENT_HALF || (pf & (RB3_TENT_BLOCK - 1)) == 0)) {
+				// (an event stretch k_cum never reached -- pad[1] == 0: behind an event that a follower's link replaced -- still holds the mask of its own event, not
+				// the cumulative one: nothing follows from the walker's first unknown through it, and this node hangs on nothing)
+				if (pf >= 0 && pf < RB3_TENT_IDS && (pf >= RB3_TENT_HALF || (pf & (RB3_TENT_BLOCK - 1)) == 0) && (pf == pl || tab[pl].pad[1] != 0u)) {
 					n.ptr = wj_id(pf, nblk), n.c = (int32_t)tab[X].w1;
 					if (pf != pl || (tab[pf].pad[0] & RB3_FIRSTFLAG)) // the cumulative mask of its last stretch (k_cum keeps a copy in the first)
 						for (int q = 0; q < 8; ++q) n.M[q] = tab[pl].mask[q];
@@ -2241,13 +2246,17 @@ __global__ void __launch_bounds__(256) k_sfin(const rb3_stretch_t *tab, const ui
 	const int j = threadIdx.x & 7;
 	const int64_t na = sidctr[0] < (uint32_t)RB3_TENT_HALF ? sidctr[0] : RB3_TENT_HALF;
 	for (int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; s < na; s += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-		const uint32_t head = tab[s].pad[0];
+		const uint2 hp = *(const uint2*)tab[s].pad; // .x: 1 + the walker's first stretch, .y: k_cum reached this stretch
+		const uint32_t head = hp.x;
 		if (head == 0u || (head & RB3_FIRSTFLAG)) continue; // a first stretch: settled by a walker or by k_resolve_w
 		if (tab[s].w0 >> 62 != RB3_DEP_EVENT) continue;
 		{ // settled by a walker that ran into it: exact, whatever the first stretch says
 			const int dl = tab[s].del;
 			if (dl != 0) { if (j == 0 && dl >= 1 && dl <= RB3_TENT_KMAX + 1) sfin[s] = dl; continue; }
 		}
+		// k_cum never reached this stretch: a link written into an earlier event stretch of this walker replaced that event, k_cum stopped there, and
+		// the masks from there on are still those of their own events, in survivor coordinates -- unsettled, whatever the first stretch says
+		if (hp.y == 0u) continue;
 		int r0 = sfin[head - 1u];
 		if (r0 < 1) { // the walker's first unknown is not settled -- unless k_cum derived it from a later stretch, for the stretches from that one on
 			const int ch = tab[head - 1u].child, dl0 = tab[head - 1u].del;
@@ -2377,6 +2386,7 @@ __global__ void __launch_bounds__(64) k_cum_x(rb3_stretch_t *tab, uint32_t *mx, 
 					mx[(int64_t)(base + o) * NW + q * 8 + j] = v; // cumulative, first-interval coordinates
 					cumO[q * 8 + j] = v;
 				}
+				if (j == 0) tab[base + o].pad[1] = 1u; // (as k_cum: reached)
 				wave_sync();
 				if (want_first) { // this stretch settled by a follower that never saw the first one: as in k_cum
 					const int dt = (int)__shfl(q1.x, o, RB3_TENT_BLOCK) - 1;
@@ -2476,13 +2486,15 @@ __global__ void __launch_bounds__(256) k_sfin_x(const rb3_stretch_t *tab, const 
 	const int j = threadIdx.x & 7;
 	const int64_t na = sidctr[0] < (uint32_t)RB3_TENT_HALF ? sidctr[0] : RB3_TENT_HALF;
 	for (int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; s < na; s += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-		const uint32_t head = tab[s].pad[0];
+		const uint2 hp = *(const uint2*)tab[s].pad; // .x: 1 + the walker's first stretch, .y: k_cum_x reached this stretch
+		const uint32_t head = hp.x;
 		if (head == 0u || (head & RB3_FIRSTFLAG)) continue; // a first stretch: settled by a walker or by k_resolve_w_x
 		if (tab[s].w0 >> 62 != RB3_DEP_EVENT) continue;
 		{ // settled by a walker that ran into it: exact, whatever the first stretch says
 			const int dl = tab[s].del;
 			if (dl != 0) { if (j == 0 && dl >= 1 && dl <= 256 * Q) sfin[s] = dl; continue; }
 		}
+		if (hp.y == 0u) continue; // (see k_sfin: k_cum_x never reached this stretch, its mask is not cumulative)
 		int r0 = sfin[head - 1u];
 		if (r0 < 1) { // (see k_sfin: the first unknown derived from a later stretch, valid from that stretch on)
 			const int ch = tab[head - 1u].child, dl0 = tab[head - 1u].del;
@@ -2531,7 +2543,7 @@ __global__ void __launch_bounds__(256) k_wj_init_x(const rb3_stretch_t *tab, con
 				const int pl = RB3_DEP_PREV(w0); // the LAST stretch of the walker that ran into this one
 				const uint32_t hp = tab[pl].pad[0];
 				const int pf = (hp == 0u || (hp & RB3_FIRSTFLAG)) ? pl : (int)hp - 1;
-				if (pf >= 0 && pf < RB3_TENT_IDS && (pf >= RB3_TENT_HALF || (pf & (RB3_TENT_BLOCK - 1)) == 0)) {
+				if (pf >= 0 && pf < RB3_TENT_IDS && (pf >= RB3_TENT_HALF || (pf & (RB3_TENT_BLOCK - 1)) == 0) && (pf == pl || tab[pl].pad[1] != 0u)) { // (see k_wj_init: reached by k_cum_x)
 					n.ptr = wj_id(pf, nblk), n.c = (int32_t)tab[X].w1;
 					if (pl < RB3_TENT_HALF && (pf != pl || (tab[pf].pad[0] & RB3_FIRSTFLAG))) // the cumulative mask of its last stretch (k_cum_x keeps a copy in the first)
 						for (int q = 0; q < NW; ++q) n.M[q] = mx[(int64_t)pl * NW + q];

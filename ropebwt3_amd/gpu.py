@@ -274,6 +274,8 @@ SYMBOLS = {
     "rb3gpu_merge_bre": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(BreStats)]),
     "rb3gpu_merge_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rb3gpu_tune": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
+    "rb3gpu_test_settle": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "rb3gpu_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Stats)]),
     "rb3gpu_buffer_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int64)]),
     "rb3gpu_stats_reset": (None, [ctypes.c_void_p]),
@@ -534,6 +536,23 @@ class Rb3Gpu:
     def tune(self, key, value):
         """rb3gpu_tune: a diagnostic switch of this handle (see include/rb3gpu.h)"""
         self._chk(self._lib.rb3gpu_tune(self._h, key.encode(), int(value)), "rb3gpu_tune(%s)" % key)
+
+    def test_settle(self, ids, records, n_a, n_b, q=1, maxhops=64, engine=0, phase=1, masks=None, chunk_ctr=None):
+        """rb3gpu_test_settle (test build only): the merge's settle phase on a hand-made stretch table.  ids: ascending stretch ids;
+        records: uint32 array (len(ids), 16), the 64-byte records; masks: for q > 1, uint32 (len(ids), 8q).  Returns a dict: sfin
+        (int32 per id), masks (uint32 (len(ids), 8q)), bad (the three validation counters), second_chance (bool)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(ids.size, 16)
+        m = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint32).reshape(ids.size, 8 * q)
+        cc = None if chunk_ctr is None else np.ascontiguousarray(chunk_ctr, dtype=np.uint32).reshape(64)
+        sfin = np.zeros(ids.size, dtype=np.int32)
+        mout = np.zeros((ids.size, 8 * q), dtype=np.uint32)
+        bad = np.zeros(3, dtype=np.uint64)
+        sc = ctypes.c_int(0)
+        self._chk(self._lib.rb3gpu_test_settle(self._h, ids.size, ids.ctypes.data, rec.ctypes.data, None if m is None else m.ctypes.data, int(n_a), int(n_b),
+                                               None if cc is None else cc.ctypes.data, int(q), int(maxhops), int(engine), int(phase),
+                                               sfin.ctypes.data, mout.ctypes.data, bad.ctypes.data, ctypes.byref(sc)), "rb3gpu_test_settle")
+        return {"sfin": sfin, "masks": mout, "bad": bad, "second_chance": bool(sc.value)}
 
     def _chk(self, r, what):
         if r < 0:
