@@ -748,6 +748,35 @@ typedef struct { double ms_total, ms_count, ms_who, ms_emit, ms_reduce, ms_compa
                  int64_t n_strings, n_hits, n_kept, n_groups, n_capped_groups, n_capped_hits, n_emitters, n_slices, resident_bytes; } rb3gpu_reduce_stats_t;
 int rb3gpu_overlap_reduced(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_reduce_stats_t *st);
 
+/* the unitigs: the paths of the string graph along which nothing branches, each spelled as one sequence (no counterpart in the reference).  K is what
+ * rb3gpu_overlap_reduced delivers for the same min_len and max_hits, in its order; the vertices are the strings.  A record (a, b, o) of K is SIMPLE iff it is the only
+ * record of K out of a, the only one into b (records are counted, not partners) and a != b; the simple records join the vertices into disjoint paths and cycles.  A
+ * unitig is a path from its head to its tail -- a vertex without simple records is a unitig of one member -- or a cycle, cut in front of its smallest row: that row is
+ * the head and spells its whole string, and the overlap that closes the circle is the unitig's `circ` (> 0; 0 for a path).  Member v starts at off(v) in its unitig,
+ * off(head) = 0 and off(next) = off(v) + len(v) - o_in(next); its symbols [o_in, len) are the ones it adds, so the unitig's length is the head's plus the sum of
+ * len - o_in over the others.  Unitigs are numbered by ascending head.  The LINKS are the records of K that are not simple, in K's order: each goes from a tail to a head.
+ * pair != 0 (an index of both strands in input order: row v ^ 1 is the other strand of row v): the graph must be strand-symmetric, next[next[v] ^ 1] == v ^ 1 wherever
+ * v has a next -- n_asym counts the vertices where it is not, and with n_asym > 0 the call is RB3GPU_EUNSUP before any callback (contained sequences or max_hits do
+ * that: rb3gpu_dedup and rb3gpu_remove first, max_hits 0, or pair 0).  Chains then come as mirror pairs and one of each is delivered: a path iff head <= tail ^ 1 (equal:
+ * the path is its own mirror image), a cycle iff its head is even, a link iff a <= b ^ 1; an end of a link on a chain that is not delivered names the mirror chain's
+ * unitig with from_rev / to_rev = 1.  pair == 0: everything is delivered, every orientation 0.
+ * cb is called once per slice of consecutive unitigs whose lengths sum to at most rb3gpu_tune "utg_slice" symbols (a longer one alone): unitigs [u0, u0 + n), their
+ * members one unitig after the other by rank, and the symbols (nt6, text order) of unitig u0 + i at symbols[off[i], off[i + 1]).  lcb (may be NULL) is called once
+ * after the last slice, with all the links, if there are any.  Host memory is valid during the callback only; a callback that returns non-zero ends the call with
+ * that value.  The records stay on the device from the reduction to the links: the ceiling "ovl_resident" and the codes are rb3gpu_overlap_reduced's.  RB3GPU_EINVAL
+ * also for pair on an odd number of strings; RB3GPU_EINTERNAL also where the members delivered, the symbols written, the steps walked and the scanned totals differ.
+ * st (may be NULL): ms_reduce the stages of rb3gpu_overlap_reduced, ms_graph, ms_rank, ms_emit (HIP events); n_simple the simple records; n_rounds the rounds of
+ * pointer jumping; n_unitigs, n_members, n_symbols, n_cycles, max_members of what is delivered; n_steps_emit == n_symbols: one LF step per symbol of the output */
+typedef struct { int32_t head, tail, members, circ; int64_t len; } rb3gpu_unitig_t;
+typedef struct { int32_t row, o_in; int64_t off; } rb3gpu_unitig_member_t;
+typedef struct { int32_t from, to, len; uint8_t from_rev, to_rev, pad[2]; } rb3gpu_unitig_link_t;
+typedef struct { double ms_total, ms_reduce, ms_graph, ms_rank, ms_emit;
+                 int64_t n_strings, n_kept, n_simple, n_unitigs, n_members, n_symbols, n_steps_emit, n_cycles, n_asym, n_links, n_rounds, max_members, n_slices,
+                         resident_bytes; } rb3gpu_unitig_stats_t;
+typedef int (*rb3gpu_unitig_cb)(void *ud, int64_t u0, int64_t n, const rb3gpu_unitig_t *utg, const rb3gpu_unitig_member_t *mem, const int64_t *off, const uint8_t *symbols);
+typedef int (*rb3gpu_unitig_link_cb)(void *ud, int64_t n, const rb3gpu_unitig_link_t *links);
+int rb3gpu_unitigs(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int pair, rb3gpu_unitig_cb cb, void *ud, rb3gpu_unitig_link_cb lcb, rb3gpu_unitig_stats_t *st);
+
 /* regions of the indexed strings, read through the sampled suffix array the handle holds (rb3gpu_ssa_set / rb3gpu_ssa_keep; no counterpart in the reference;
  * DESIGN.md 7m): random access into the indexed text.  A region is (row r, beg, end): the symbols [beg, end) of string r, the string rb3gpu_retrieve spells for
  * row r < acc[1]; 0-based, end exclusive; valid iff 0 <= r < acc[1] and 0 <= beg < end <= the length of the string.  Sample x of the sampled suffix array says that
@@ -794,6 +823,7 @@ int rb3gpu_stream_sync(void *stream);
  *   "dedup_slice" N (strings per launch of rb3gpu_dedup; 0 = 4 M), "dedup_early" 0/1 (its walks end once the string is known to be unique; default 1);
  *   "ovl_strings" N (strings per launch of the counting walk of rb3gpu_overlap; 0 = 4 M), "ovl_slice" N (records of an emit slice; 0 = 16 M), "ovl_early" 0/1 (default 1);
  *   "ovl_resident" N (records rb3gpu_overlap_reduced may hold on the device; 0 = as many as can be allocated), "ovl_reduce_strings" N (strings per launch of its reduction; 0 = 4 M);
+ *   "utg_slice" N (symbols of an emit slice of rb3gpu_unitigs; 0 = 64 M), "utg_strings" N (members per launch of its emitting walk; 0 = 4 M);
  *   "get_piece" S (splitter spacing 2^S of rb3gpu_retrieve_pieces, 1..20; 0 = 8); "fetch_slice" N (symbols of a slice of regions of rb3gpu_fetch; 0 = 64 M);
  *   "seed_chunk" N (window starts per walker of rb3gpu_seed_present where the call names none; 0 = 2048), "seed_slice" N (its walkers per launch; 0 = 1 M);
  *   "locate_heap" N (entries of an octet's heap in LDS, rb3gpu_locate; 0 = 32, at most 80), "locate_slice" N (bytes of global-memory heaps at once; 0 = 256 MB);

@@ -2276,6 +2276,168 @@ static int main_overlap(int argc, char *argv[])
 	return ret;
 }
 
+/* unitig [-l INT] [-c INT] [--pair] [--gfa | --table] <idx> (no counterpart in the reference): the unambiguous paths of the string graph of the irreducible
+ * overlaps (those of `overlap --reduce` with the same -l and -c), each spelled as one sequence, through ONE call of rb3gpu_unitigs.  Per unitig `>utg<id>`, LN:i: its
+ * length, RC:i: its members, CL:i: the closing overlap of a circular one, then its letters on one line.  --gfa: H, one S line per unitig, one L line per overlap between
+ * unitigs and one per circular unitig onto itself.  --table: a line per member instead: utg, rank, string (--pair: sequence, strand), offset, overlap with the member in
+ * front.  --pair: an index of both strands in input order; one of every two mirror-image unitigs is printed.  -l below 1, -c below 0, --gfa with --table, --pair on a
+ * sorted index or on one strand, a graph whose strands differ, more overlaps than may be held on the device, a further argument and a file that is no index are one
+ * line on stderr each, exit 1, nothing on stdout. */
+static const struct option unitig_long_opts[] = {
+	{ "gpu", required_argument, 0, 301 },
+	{ "pair", no_argument, 0, 503 },
+	{ "gfa", no_argument, 0, 504 },
+	{ "table", no_argument, 0, 505 },
+	{ 0, 0, 0, 0 }
+};
+
+typedef struct { rb3h_buf_t out; int pair, mode, err; int64_t n_circ, m_circ, *circ; } unitig_out_t; /* mode 0: sequences, 1: GFA, 2: the table; circ: (id, overlap) of the circular ones */
+
+static int unitig_room(unitig_out_t *o, int64_t need)
+{
+	if (o->out.l + need > o->out.m) {
+		const int64_t m = (o->out.l + need) * 2;
+		uint8_t *t = (uint8_t*)realloc(o->out.s, (size_t)m);
+		if (t == 0) { o->err = 1; return -1; }
+		o->out.s = t, o->out.m = m;
+	}
+	return 0;
+}
+
+static int unitig_sink(void *ud, int64_t u0, int64_t n, const rb3gpu_unitig_t *utg, const rb3gpu_unitig_member_t *mem, const int64_t *off, const uint8_t *symbols)
+{
+	unitig_out_t *o = (unitig_out_t*)ud;
+	int64_t i, j, at = 0;
+	for (i = 0; i < n && !o->err; at += utg[i].members, ++i) {
+		const rb3gpu_unitig_t *u = &utg[i];
+		const int64_t len = off[i + 1] - off[i];
+		char *p;
+		if (o->mode == 2) {
+			for (j = 0; j < u->members && !o->err; ++j) {
+				const rb3gpu_unitig_member_t *v = &mem[at + j];
+				if (unitig_room(o, 160) < 0) break;
+				p = (char*)o->out.s + o->out.l;
+				if (o->pair) o->out.l += sprintf(p, "utg%ld\t%ld\t%d\t%c\t%ld\t%d\n", (long)(u0 + i), (long)j, v->row >> 1, "+-"[v->row & 1], (long)v->off, v->o_in);
+				else o->out.l += sprintf(p, "utg%ld\t%ld\t%d\t%ld\t%d\n", (long)(u0 + i), (long)j, v->row, (long)v->off, v->o_in);
+				if (out_flush(&o->out, 0) < 0) o->err = 2;
+			}
+			continue;
+		}
+		if (unitig_room(o, len + 160) < 0) break;
+		p = (char*)o->out.s + o->out.l;
+		p += o->mode == 1 ? sprintf(p, "S\tutg%ld\t", (long)(u0 + i)) : sprintf(p, ">utg%ld\tLN:i:%ld\tRC:i:%d", (long)(u0 + i), (long)u->len, u->members);
+		if (o->mode == 0 && u->circ) p += sprintf(p, "\tCL:i:%d", u->circ);
+		if (o->mode == 0) *p++ = '\n';
+		for (j = 0; j < len; ++j) *p++ = "$ACGTN"[symbols[off[i] + j] < 6 ? symbols[off[i] + j] : 5];
+		if (o->mode == 1) p += sprintf(p, "\tLN:i:%ld\tRC:i:%d", (long)u->len, u->members);
+		*p++ = '\n';
+		o->out.l = (uint8_t*)p - o->out.s;
+		if (o->mode == 1 && u->circ) {
+			if (o->n_circ == o->m_circ) {
+				const int64_t m = o->m_circ ? o->m_circ * 2 : 16;
+				int64_t *t = (int64_t*)realloc(o->circ, (size_t)m * 16);
+				if (t == 0) { o->err = 1; break; }
+				o->circ = t, o->m_circ = m;
+			}
+			o->circ[2 * o->n_circ] = u0 + i, o->circ[2 * o->n_circ + 1] = u->circ, ++o->n_circ;
+		}
+		if (out_flush(&o->out, 0) < 0) o->err = 2;
+	}
+	return o->err;
+}
+
+static int unitig_link_sink(void *ud, int64_t n, const rb3gpu_unitig_link_t *links)
+{
+	unitig_out_t *o = (unitig_out_t*)ud;
+	int64_t i;
+	for (i = 0; i < n && !o->err; ++i) {
+		const rb3gpu_unitig_link_t *l = &links[i];
+		if (unitig_room(o, 160) < 0) break;
+		o->out.l += sprintf((char*)o->out.s + o->out.l, "L\tutg%d\t%c\tutg%d\t%c\t%dM\n", l->from, "+-"[l->from_rev & 1], l->to, "+-"[l->to_rev & 1], l->len);
+		if (out_flush(&o->out, 0) < 0) o->err = 2;
+	}
+	return o->err;
+}
+
+static int main_unitig(int argc, char *argv[])
+{
+	int c, ret = 0, device = 0, pair = 0, gfa = 0, table = 0;
+	int64_t acc[7], min_len = 31, max_hits = 0, i;
+	rb3gpu_unitig_stats_t st;
+	rb3gpu_t *h;
+	index_host_t ih;
+	unitig_out_t o;
+	optind = 1;
+	while ((c = getopt_long(argc, argv, "l:c:", unitig_long_opts, 0)) >= 0) {
+		if (c == 301) device = atoi(optarg);
+		else if (c == 503) pair = 1;
+		else if (c == 504) gfa = 1;
+		else if (c == 505) table = 1;
+		else if (c == 'l') min_len = atol(optarg);
+		else if (c == 'c') max_hits = atol(optarg);
+		else if (c == '?') return 1;
+	}
+	if (argc - optind < 1) {
+		fprintf(stderr, "Usage: ropebwt3-amd unitig [options] <idx.fmd|fmr|bre>\n");
+		fprintf(stderr, "Options:\n");
+		fprintf(stderr, "  -l INT         min overlap length [%ld]\n", (long)min_len);
+		fprintf(stderr, "  -c INT         leave out an overlap shared with more than INT partners (0: none) [%ld]\n", (long)max_hits);
+		fprintf(stderr, "  --pair         an index of both strands in input order: one of every two mirror-image unitigs, links with orientations\n");
+		fprintf(stderr, "  --gfa          GFA 1.0: S lines, L lines for the overlaps between unitigs and for circular unitigs\n");
+		fprintf(stderr, "  --table        a line per member instead of sequences: utg, rank, string (--pair: sequence, strand), offset, overlap\n");
+		fprintf(stderr, "  --gpu INT      HIP device ordinal [0]\n");
+		fprintf(stderr, "Output: >utg<id> LN:i:<length> RC:i:<members> [CL:i:<closing overlap of a circular one>], then the letters on one line\n");
+		return 1;
+	}
+	if (min_len < 1) { fprintf(stderr, "ERROR: unitig: -l takes a length of at least 1\n"); return 1; }
+	if (max_hits < 0) { fprintf(stderr, "ERROR: unitig: -c takes a number of partners, 0 for no limit\n"); return 1; }
+	if (gfa && table) { fprintf(stderr, "ERROR: unitig: --gfa and --table are two outputs: name one\n"); return 1; }
+	if (argc - optind > 1) { fprintf(stderr, "ERROR: unitig: takes one index and nothing else ('%s')\n", argv[optind + 1]); return 1; }
+	if (pair && index_order(argv[optind]) != RB3GPU_SO_IO) {
+		fprintf(stderr, "ERROR: overlap: --pair numbers the sequences in input order; the strings of this index are sorted (build -s / -r): run it without --pair\n");
+		return 1;
+	}
+	memset(&ih, 0, sizeof(ih));
+	memset(&o, 0, sizeof(o));
+	memset(&st, 0, sizeof(st));
+	c = rb3h_verbose;
+	rb3h_verbose = 0; /* (the command refuses with ONE line: the loading says nothing until the index is accepted) */
+	if (index_host_read(argv[optind], &ih) < 0) {
+		rb3h_verbose = c;
+		fprintf(stderr, "ERROR: unitig: '%s' is not an index\n", argv[optind]);
+		return 1;
+	}
+	rb3h_verbose = c > 2 ? 2 : c;
+	h = open_index(device, argv[optind], &ih);
+	rb3h_verbose = c;
+	if (h == 0) return 1;
+	rb3gpu_tune(h, "verbose", rb3h_verbose);
+	rb3gpu_get_acc(h, acc);
+	if (pair && !both_strands(acc)) ret = 1;
+	if (ret == 0) {
+		o.pair = pair, o.mode = gfa ? 1 : table ? 2 : 0;
+		if (gfa && unitig_room(&o, 160) == 0) o.out.l += sprintf((char*)o.out.s, "H\tVN:Z:1.0\n");
+		c = o.err ? 0 : rb3gpu_unitigs(h, min_len, max_hits, pair, unitig_sink, &o, gfa ? unitig_link_sink : 0, &st);
+		for (i = 0; i < o.n_circ && c == 0 && !o.err; ++i)
+			if (unitig_room(&o, 160) == 0) o.out.l += sprintf((char*)o.out.s + o.out.l, "L\tutg%ld\t+\tutg%ld\t+\t%ldM\n", (long)o.circ[2 * i], (long)o.circ[2 * i], (long)o.circ[2 * i + 1]);
+		if (o.err == 1) { fprintf(stderr, "ERROR: out of memory\n"); ret = 1; }
+		else if (o.err == 2) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+		else if (c == RB3GPU_EUNSUP && st.n_asym > 0) { fprintf(stderr, "ERROR: unitig: --pair needs the same graph on both strands, and %ld overlaps have no mirror image (contained sequences or -c do that): run dedup --pair | remove --pair first, drop -c, or run it without --pair\n", (long)st.n_asym); ret = 1; }
+		else if (c == RB3GPU_EUNSUP) { fprintf(stderr, "ERROR: overlap: --reduce holds all the overlaps on the device, and there are more than RB3GPU_OVL_RESIDENT allows: raise -l, set -c, or run it without --reduce\n"); ret = 1; }
+		else if (c == RB3GPU_ENOMEM) { fprintf(stderr, "ERROR: overlap: --reduce holds all the overlaps on the device, and there are more than its memory takes: raise -l, set -c, or run it without --reduce\n"); ret = 1; }
+		else if (c != 0) { fprintf(stderr, "ERROR: the GPU engine failed to build the unitigs: %s\n", rb3gpu_strerror(c)); ret = 1; }
+	}
+	if (ret == 0 && (out_flush(&o.out, 1) < 0 || fflush(stdout) != 0)) { fprintf(stderr, "ERROR: failed to write the output\n"); ret = 1; }
+	if (ret == 0 && rb3h_verbose >= 3)
+		fprintf(stderr, "[M::%s::%.3f*%.2f] %lld strings: %lld kept overlaps, %lld simple; %lld unitigs of %lld members and %lld symbols, %lld circular, longest %lld members, %lld links; %lld rounds, %lld steps, %lld slice(s), %lld bytes resident; %.3f ms in the engine: reduce %.3f, graph %.3f, rank %.3f, emit %.3f ms\n",
+				__func__, rb3h_realtime(), rb3h_percent_cpu(), (long long)st.n_strings, (long long)st.n_kept, (long long)st.n_simple, (long long)st.n_unitigs, (long long)st.n_members, (long long)st.n_symbols,
+				(long long)st.n_cycles, (long long)st.max_members, (long long)st.n_links, (long long)st.n_rounds, (long long)st.n_steps_emit, (long long)st.n_slices, (long long)st.resident_bytes,
+				st.ms_total, st.ms_reduce, st.ms_graph, st.ms_rank, st.ms_emit);
+	free(o.out.s); free(o.circ);
+	rb3gpu_destroy(h);
+	return ret;
+}
+
 /* fetch [-f FILE] [--row] [-s INT] <idx> [region ...] (no counterpart in the reference): regions of the indexed sequences through the sampled suffix array,
  * ONE call of rb3gpu_fetch.  A region is the word name:beg-end[:+|:-] (rb3h_region_parse: 0-based, end-exclusive, the name cut at the last colons); -f adds BED lines.
  * Named regions need <idx>.ssa and <idx>.len.gz and an index of both strands in input order: sequence i forward is row 2i, region as given; strand - is row 2i + 1,
@@ -3110,6 +3272,7 @@ static int usage(FILE *fp)
 	fprintf(fp, "    remove     take sequences out of a BWT (on an MI355X)\n");
 	fprintf(fp, "    dedup      list sequences that are copies of, or lie inside, another one (on an MI355X)\n");
 	fprintf(fp, "    overlap    list the suffix-prefix overlaps of the sequences (on an MI355X)\n");
+	fprintf(fp, "    unitig     spell the unambiguous paths of the overlap graph (on an MI355X)\n");
 	fprintf(fp, "    fetch      retrieve regions of sequences through the sampled suffix array (on an MI355X)\n");
 	fprintf(fp, "    hapdiv     haplotype diversity with sliding k-mers (on an MI355X)\n");
 	fprintf(fp, "    sw         align queries end to end with CIGAR and positions (on an MI355X)\n");
@@ -3135,6 +3298,7 @@ int main(int argc, char *argv[])
 	else if (strcmp(argv[1], "remove") == 0) ret = main_remove(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "dedup") == 0) ret = main_dedup(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "overlap") == 0) ret = main_overlap(argc - 1, argv + 1);
+	else if (strcmp(argv[1], "unitig") == 0) ret = main_unitig(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "fetch") == 0) ret = main_fetch(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "hapdiv") == 0) ret = main_hapdiv(argc - 1, argv + 1);
 	else if (strcmp(argv[1], "sw") == 0) ret = main_sw(argc - 1, argv + 1);

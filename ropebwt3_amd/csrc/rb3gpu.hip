@@ -31,6 +31,7 @@
 #include "rb3gpu_dedup.h"
 #include "rb3gpu_overlap.h"
 #include "rb3gpu_reduce.h"
+#include "rb3gpu_unitig.h"
 #include "rb3gpu_fetch.h"
 #include "rb3gpu_hapdiv.h"
 #include "rb3gpu_sw.h"
@@ -184,6 +185,8 @@ struct Tune {
 	int ovl_early = 1;       // rb3gpu_overlap: a walk ends once its interval is one row (0: every walk goes down to its sentinel)
 	int64_t ovl_resident = 0;       // rb3gpu_overlap_reduced: the records it may hold on the device (0: as many as can be allocated)
 	int64_t ovl_reduce_strings = 0; // rb3gpu_overlap_reduced: strings per launch of the reduction (0: 4 M)
+	int64_t utg_slice = 0;   // rb3gpu_unitigs: symbols of an emit slice (0: 64 M; a unitig longer than that is a slice of its own)
+	int64_t utg_strings = 0; // rb3gpu_unitigs: members per launch of the emitting walk (0: 4 M)
 	int64_t seed_chunk = 0;  // rb3gpu_seed_present: window starts per walker where the caller names none (0: 2048)
 	int64_t seed_slice = 0;  // rb3gpu_seed_present: walkers per launch (0: 1 M)
 	int64_t get_slice = 0;   // rb3gpu_retrieve: symbols of an emit slice, i.e. bytes of output held on the device at once (0: 64 M; a row longer than that is a slice of its own)
@@ -768,6 +771,8 @@ static int tune_set(rb3gpu_t *h, const char *key, int64_t v)
 	else if (!strcmp(key, "ovl_early")) t.ovl_early = v != 0;
 	else if (!strcmp(key, "ovl_resident")) t.ovl_resident = v < 0 ? 0 : v;
 	else if (!strcmp(key, "ovl_reduce_strings")) t.ovl_reduce_strings = v < 0 ? 0 : v;
+	else if (!strcmp(key, "utg_slice")) t.utg_slice = v < 0 ? 0 : v;
+	else if (!strcmp(key, "utg_strings")) t.utg_strings = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_slice")) t.get_slice = v < 0 ? 0 : v;
 	else if (!strcmp(key, "get_piece")) t.get_piece = v < 1 ? 0 : v > 20 ? 20 : (int)v;
 	else if (!strcmp(key, "fetch_slice")) t.fetch_slice = v < 0 ? 0 : v;
@@ -812,7 +817,7 @@ int rb3gpu_tune(rb3gpu_t *h, const char *key, int64_t value)
 
 static void tune_from_env(rb3gpu_t *h) // once per handle
 {
-	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "ovl_strings", "ovl_slice", "ovl_early", "ovl_resident", "ovl_reduce_strings", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
+	static const char *keys[] = { "tent", "staged", "group_rebuild", "window_rebuild", "plane_rebuild", "reb_t1_rows", "part", "scan_place", "reb_force", "resolve_v1", "octs", "lpw", "blkmul", "blkcap", "chain_bs", "lf_after", "copy_walkers", "tent_q", "trec", "abs_limit", "abs_table", "ssa_split", "b2_split", "lf_check", "junction_check", "sh_block", "sh_states", "ev_blocks", "cum_blocks", "resw_blocks", "sfin_blocks", "sh_host_rounds", "fmd_piece", "bre_piece", "mem_slice", "hapdiv_slice", "hapdiv_table", "sw_slice", "sw_table", "suffix_slice", "dedup_slice", "dedup_early", "ovl_strings", "ovl_slice", "ovl_early", "ovl_resident", "ovl_reduce_strings", "utg_slice", "utg_strings", "get_slice", "get_piece", "fetch_slice", "seed_chunk", "seed_slice", "locate_heap", "locate_slice", "load_chunk", "log_alloc", "defer_free", "vmm", "vmm_reserve", "b2_tw", "poison", "guard",
 		"force_fallback", "hide_first", "tent_limit", "text_mode", "corrupt_pos", "corrupt_sfin", "reb_lcap", "reb_slot_cap", "pos_limit", "win_scratch", "slot_bytes", nullptr };
 	for (int i = 0; keys[i]; ++i) {
 		char name[64] = "RB3GPU_";
@@ -6690,6 +6695,113 @@ int rb3gpu_overlap(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len,
 
 #define RB3_OVL_REDUCE_STRINGS ((int64_t)1 << 22)    // strings per launch of the reduction
 
+/* the records of a plan that has any, resident on the device and reduced, shared by rb3gpu_overlap_reduced and rb3gpu_unitigs: rec[n] at the scanned offsets, keep[n + 1]
+ * (1: irreducible), pos[n + 1] its exclusive scan, and on the host koff[i]: the kept records in front of emitter i.  The device memory is the call's Scratch's */
+struct OvlResident {
+	OvlRec *d_rec = nullptr;
+	uint32_t *d_rank = nullptr, *d_keep = nullptr;
+	int64_t *d_pos = nullptr, *d_koff = nullptr;
+	void *d_tmp = nullptr; // the scan's, for n + 1 entries
+	size_t tmp_bytes = 0;
+	std::vector<int64_t> koff;
+	int64_t n_kept = 0, resident = 0;
+	double ms_emit = 0, ms_reduce = 0, ms_compact = 0;
+};
+
+static int ovl_resident(rb3gpu_t *h, Scratch &sc, const OvlPlan &P, int64_t max_hits, OvlResident &R)
+{
+	const int64_t m = h->acc[1];
+	const IdxView ix = view_of(h);
+	const int64_t n = P.n_hits, ne = P.n_emitters;
+	const std::vector<uint32_t> &em = P.em;
+	const std::vector<int64_t> &eoff = P.eoff;
+	unsigned long long *const d_ctr = P.d_ctr, *const h_ctr = P.h_ctr; // [56, 59): the reduction, [59]: the inverse rank table, [60]: the scatter
+	const unsigned long long *ce = h_ctr + 32, *cr = h_ctr + 56;
+	OvlRec *&d_rec = R.d_rec;
+	uint32_t *&d_rank = R.d_rank, *&d_keep = R.d_keep;
+	int64_t *&d_pos = R.d_pos, *&d_koff = R.d_koff;
+	void *&d_tmp = R.d_tmp;
+	size_t &tmp_bytes = R.tmp_bytes;
+	std::vector<int64_t> &koff = R.koff;
+	double &ms_emit = R.ms_emit, &ms_reduce = R.ms_reduce, &ms_compact = R.ms_compact;
+	int64_t &n_kept = R.n_kept, &resident = R.resident;
+	if (h->tn.ovl_resident > 0 && n > h->tn.ovl_resident) return RB3GPU_EUNSUP; // (said by the caller, as the allocation below: the alternatives are its to name)
+	// 1. the resident array: every record at its scanned offset, written by launches of `per` strings each, and the sentinel rank of every string
+	{
+		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, n + 1, h->st);
+		if (r < 0) return scan_err(r);
+	}
+	const size_t want[6] = { (size_t)n * sizeof(OvlRec), (size_t)m * 4, (size_t)(n + 1) * 4, (size_t)(n + 1) * 8, (size_t)(ne + 1) * 8, tmp_bytes + 256 };
+	void **const where[6] = { (void**)&d_rec, (void**)&d_rank, (void**)&d_keep, (void**)&d_pos, (void**)&d_koff, &d_tmp };
+	for (int i = 0; i < 6; ++i) {
+		if (sc.dev(where[i], want[i]) != hipSuccess) { // (too many records for this device: a larger min_len, a cap, or rb3gpu_overlap)
+			(void)hipGetLastError();
+			return RB3GPU_ENOMEM;
+		}
+		resident += (int64_t)want[i];
+	}
+	const auto first_emitter = [&](int64_t r) { return (int64_t)(std::lower_bound(em.begin(), em.end(), (uint32_t)r) - em.begin()); }; // the first one that is string r or behind it
+	const int64_t per = std::min(m, h->tn.ovl_strings > 0 ? h->tn.ovl_strings : RB3_OVL_STRINGS);
+	HIPCHK(hipMemsetAsync(d_rank, 0xFF, (size_t)m * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)(n + 1) * 4, h->st)); // (keep[n] = 0: the entry behind the last record)
+	HIPCHK(hipEventRecord(P.e0, h->st));
+	hipLaunchKernelGGL(k_ovl_rank, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->st, m, (const uint32_t*)P.d_who, d_rank, d_ctr + 59);
+	HIPCHK(hipEventRecord(P.e1, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	ms_emit += ev_ms(P.e0, P.e1);
+	for (int64_t r0 = 0; r0 < m; r0 += per) {
+		const int64_t i0 = first_emitter(r0), i1 = first_emitter(std::min(m, r0 + per));
+		if (i0 == i1) continue;
+		HIPCHK(hipMemsetAsync(d_ctr + 32, 0, 8, h->st));
+		const int64_t nb = std::min<int64_t>(((i1 - i0) * 8 + 255) / 256, 4096);
+		HIPCHK(hipEventRecord(P.e0, h->st));
+		hipLaunchKernelGGL(k_ovl_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, i0, i1, P.min32, max_hits, 0, (const uint32_t*)P.d_em, P.d_cnt, P.d_last,
+				(const int64_t*)P.d_off, (int64_t)0, (const uint32_t*)P.d_who, (const uint32_t*)P.d_len32, d_rec, n, d_ctr + 32);
+		HIPCHK(hipEventRecord(P.e1, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_emit += ev_ms(P.e0, P.e1);
+	}
+	// 2. reduce: an octet per record, launches of the records of `rper` strings each
+	const int64_t rper = std::min(m, h->tn.ovl_reduce_strings > 0 ? h->tn.ovl_reduce_strings : RB3_OVL_REDUCE_STRINGS);
+	for (int64_t r0 = 0; r0 < m; r0 += rper) {
+		const int64_t j0 = eoff[(size_t)first_emitter(r0)], j1 = eoff[(size_t)first_emitter(std::min(m, r0 + rper))];
+		if (j0 == j1) continue;
+		const int64_t nb = std::min<int64_t>(((j1 - j0) * 8 + 255) / 256, (int64_t)1 << 16);
+		HIPCHK(hipEventRecord(P.e0, h->st));
+		hipLaunchKernelGGL(k_ovl_reduce, dim3((unsigned)nb), dim3(256), 0, h->st, (const OvlRec*)d_rec, (const int64_t*)P.d_off, (const uint32_t*)d_rank, m, n, j0, j1, d_keep, d_ctr + 56);
+		HIPCHK(hipEventRecord(P.e1, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		HIPCHK(hipGetLastError());
+		ms_reduce += ev_ms(P.e0, P.e1);
+	}
+	// 3. compact: where every kept record goes, the kept records in front of every string that has records
+	HIPCHK(hipEventRecord(P.e0, h->st));
+	{
+		size_t tb = tmp_bytes + 256;
+		const int r = rb3kount_scan(d_tmp, &tb, d_keep, d_pos, n + 1, h->st);
+		if (r < 0) return scan_err(r);
+	}
+	hipLaunchKernelGGL(k_ovl_koff, dim3((unsigned)((ne + 256) / 256)), dim3(256), 0, h->st, ne, (const uint32_t*)P.d_em, m, n, (const int64_t*)P.d_off, (const int64_t*)d_pos, d_koff);
+	HIPCHK(hipEventRecord(P.e1, h->st));
+	koff.assign((size_t)ne + 1, 0);
+	HIPCHK(hipMemcpyAsync(koff.data(), d_koff, (size_t)(ne + 1) * 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipMemcpyAsync(h_ctr + 32, d_ctr + 32, 256, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(hipStreamSynchronize(h->st));
+	HIPCHK(hipGetLastError());
+	ms_compact += ev_ms(P.e0, P.e1);
+	n_kept = koff[(size_t)ne];
+	bool sound = ce[2] == 0 && ce[3] == 0 && ce[10] == 0 && (int64_t)ce[8] == n && cr[2] == 0 && cr[3] == 0 && koff[0] == 0 && (int64_t)cr[1] == n_kept && (int64_t)(cr[0] + cr[1]) == n;
+	for (int64_t i = 0; i < ne && sound; ++i) sound = koff[(size_t)i + 1] > koff[(size_t)i]; // the deepest group of a string is never reducible
+	if (!sound) {
+		if (h->opt.verbose >= 1)
+			fprintf(stderr, "[E::rb3gpu] overlap: of %lld records %llu were stored (%llu strings differ), %llu reduced, %llu kept and %llu left alone; the scan has %lld kept\n",
+					(long long)n, ce[8], ce[10], cr[0], cr[1], cr[2], (long long)n_kept);
+		return RB3GPU_EINTERNAL;
+	}
+	return 0;
+}
+
 int rb3gpu_overlap_reduced(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64_t *len, rb3gpu_overlap_cb cb, void *ud, rb3gpu_reduce_stats_t *st)
 {
 	if (st) memset(st, 0, sizeof(*st));
@@ -6703,96 +6815,21 @@ int rb3gpu_overlap_reduced(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64
 	const int64_t budget = h->tn.ovl_slice > 0 ? h->tn.ovl_slice : RB3_OVL_SLICE;
 	Scratch sc;
 	OvlPlan P;
+	OvlResident R;
 	if (const int e = ovl_plan(h, sc, min_len, max_hits, len, P)) return e;
-	const IdxView ix = view_of(h);
 	const int64_t n = P.n_hits, ne = P.n_emitters;
-	const std::vector<uint32_t> &em = P.em;
-	const std::vector<int64_t> &eoff = P.eoff;
-	unsigned long long *const d_ctr = P.d_ctr, *const h_ctr = P.h_ctr; // [56, 59): the reduction, [59]: the inverse rank table, [60]: the scatter
-	const unsigned long long *cw = h_ctr, *ce = h_ctr + 32, *cr = h_ctr + 56;
-	double ms_emit = 0, ms_reduce = 0, ms_compact = 0;
-	int64_t n_kept = 0, n_slices = 0, resident = 0;
+	const std::vector<int64_t> &eoff = P.eoff, &koff = R.koff;
+	unsigned long long *const d_ctr = P.d_ctr, *const h_ctr = P.h_ctr;
+	const unsigned long long *cw = h_ctr, *cr = h_ctr + 56;
+	int64_t n_slices = 0;
 	int ret = 0;
 	if (n > 0) {
-		if (h->tn.ovl_resident > 0 && n > h->tn.ovl_resident) return RB3GPU_EUNSUP; // (said by the caller, as the allocation below: the alternatives are its to name)
-		// 1. the resident array: every record at its scanned offset, written by launches of `per` strings each, and the sentinel rank of every string
-		OvlRec *d_rec = nullptr, *d_out = nullptr, *h_out = nullptr;
-		uint32_t *d_rank = nullptr, *d_keep = nullptr;
-		int64_t *d_pos = nullptr, *d_koff = nullptr;
-		void *d_tmp = nullptr;
-		size_t tmp_bytes = 0;
-		{
-			const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, n + 1, h->st);
-			if (r < 0) return scan_err(r);
-		}
-		const size_t want[6] = { (size_t)n * sizeof(OvlRec), (size_t)m * 4, (size_t)(n + 1) * 4, (size_t)(n + 1) * 8, (size_t)(ne + 1) * 8, tmp_bytes + 256 };
-		void **const where[6] = { (void**)&d_rec, (void**)&d_rank, (void**)&d_keep, (void**)&d_pos, (void**)&d_koff, &d_tmp };
-		for (int i = 0; i < 6; ++i) {
-			if (sc.dev(where[i], want[i]) != hipSuccess) { // (too many records for this device: a larger min_len, a cap, or rb3gpu_overlap)
-				(void)hipGetLastError();
-				return RB3GPU_ENOMEM;
-			}
-			resident += (int64_t)want[i];
-		}
-		const auto first_emitter = [&](int64_t r) { return (int64_t)(std::lower_bound(em.begin(), em.end(), (uint32_t)r) - em.begin()); }; // the first one that is string r or behind it
-		const int64_t per = std::min(m, h->tn.ovl_strings > 0 ? h->tn.ovl_strings : RB3_OVL_STRINGS);
-		HIPCHK(hipMemsetAsync(d_rank, 0xFF, (size_t)m * 4, h->st));
-		HIPCHK(hipMemsetAsync(d_keep, 0, (size_t)(n + 1) * 4, h->st)); // (keep[n] = 0: the entry behind the last record)
-		HIPCHK(hipEventRecord(P.e0, h->st));
-		hipLaunchKernelGGL(k_ovl_rank, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->st, m, (const uint32_t*)P.d_who, d_rank, d_ctr + 59);
-		HIPCHK(hipEventRecord(P.e1, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		ms_emit += ev_ms(P.e0, P.e1);
-		for (int64_t r0 = 0; r0 < m; r0 += per) {
-			const int64_t i0 = first_emitter(r0), i1 = first_emitter(std::min(m, r0 + per));
-			if (i0 == i1) continue;
-			HIPCHK(hipMemsetAsync(d_ctr + 32, 0, 8, h->st));
-			const int64_t nb = std::min<int64_t>(((i1 - i0) * 8 + 255) / 256, 4096);
-			HIPCHK(hipEventRecord(P.e0, h->st));
-			hipLaunchKernelGGL(k_ovl_walk<true>, dim3((unsigned)nb), dim3(256), 0, h->st, ix, i0, i1, P.min32, max_hits, 0, (const uint32_t*)P.d_em, P.d_cnt, P.d_last,
-					(const int64_t*)P.d_off, (int64_t)0, (const uint32_t*)P.d_who, (const uint32_t*)P.d_len32, d_rec, n, d_ctr + 32);
-			HIPCHK(hipEventRecord(P.e1, h->st));
-			HIPCHK(hipStreamSynchronize(h->st));
-			HIPCHK(hipGetLastError());
-			ms_emit += ev_ms(P.e0, P.e1);
-		}
-		// 2. reduce: an octet per record, launches of the records of `rper` strings each
-		const int64_t rper = std::min(m, h->tn.ovl_reduce_strings > 0 ? h->tn.ovl_reduce_strings : RB3_OVL_REDUCE_STRINGS);
-		for (int64_t r0 = 0; r0 < m; r0 += rper) {
-			const int64_t j0 = eoff[(size_t)first_emitter(r0)], j1 = eoff[(size_t)first_emitter(std::min(m, r0 + rper))];
-			if (j0 == j1) continue;
-			const int64_t nb = std::min<int64_t>(((j1 - j0) * 8 + 255) / 256, (int64_t)1 << 16);
-			HIPCHK(hipEventRecord(P.e0, h->st));
-			hipLaunchKernelGGL(k_ovl_reduce, dim3((unsigned)nb), dim3(256), 0, h->st, (const OvlRec*)d_rec, (const int64_t*)P.d_off, (const uint32_t*)d_rank, m, n, j0, j1, d_keep, d_ctr + 56);
-			HIPCHK(hipEventRecord(P.e1, h->st));
-			HIPCHK(hipStreamSynchronize(h->st));
-			HIPCHK(hipGetLastError());
-			ms_reduce += ev_ms(P.e0, P.e1);
-		}
-		// 3. compact: where every kept record goes, the kept records in front of every string that has records
-		HIPCHK(hipEventRecord(P.e0, h->st));
-		{
-			size_t tb = tmp_bytes + 256;
-			const int r = rb3kount_scan(d_tmp, &tb, d_keep, d_pos, n + 1, h->st);
-			if (r < 0) return scan_err(r);
-		}
-		hipLaunchKernelGGL(k_ovl_koff, dim3((unsigned)((ne + 256) / 256)), dim3(256), 0, h->st, ne, (const uint32_t*)P.d_em, m, n, (const int64_t*)P.d_off, (const int64_t*)d_pos, d_koff);
-		HIPCHK(hipEventRecord(P.e1, h->st));
-		std::vector<int64_t> koff((size_t)ne + 1);
-		HIPCHK(hipMemcpyAsync(koff.data(), d_koff, (size_t)(ne + 1) * 8, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipMemcpyAsync(h_ctr + 32, d_ctr + 32, 256, hipMemcpyDeviceToHost, h->st));
-		HIPCHK(hipStreamSynchronize(h->st));
-		HIPCHK(hipGetLastError());
-		ms_compact += ev_ms(P.e0, P.e1);
-		n_kept = koff[(size_t)ne];
-		bool sound = ce[2] == 0 && ce[3] == 0 && ce[10] == 0 && (int64_t)ce[8] == n && cr[2] == 0 && cr[3] == 0 && koff[0] == 0 && (int64_t)cr[1] == n_kept && (int64_t)(cr[0] + cr[1]) == n;
-		for (int64_t i = 0; i < ne && sound; ++i) sound = koff[(size_t)i + 1] > koff[(size_t)i]; // the deepest group of a string is never reducible
-		if (!sound) {
-			if (h->opt.verbose >= 1)
-				fprintf(stderr, "[E::rb3gpu] overlap: of %lld records %llu were stored (%llu strings differ), %llu reduced, %llu kept and %llu left alone; the scan has %lld kept\n",
-						(long long)n, ce[8], ce[10], cr[0], cr[1], cr[2], (long long)n_kept);
-			return RB3GPU_EINTERNAL;
-		}
+		// 1-3. the resident array, the reduction and the scan of what it keeps
+		if (const int e = ovl_resident(h, sc, P, max_hits, R)) return e;
+		OvlRec *const d_rec = R.d_rec, *d_out = nullptr, *h_out = nullptr;
+		const uint32_t *const d_keep = R.d_keep;
+		const int64_t *const d_pos = R.d_pos;
+		double &ms_compact = R.ms_compact;
 		// 4. slices of consecutive strings whose kept records sum to at most the budget, one with more alone
 		int64_t out_cap = 0;
 		for (int64_t i0 = 0; i0 < ne && ret == 0; ++n_slices) {
@@ -6820,10 +6857,271 @@ int rb3gpu_overlap_reduced(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int64
 		}
 	}
 	if (st) {
-		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = P.ms_count, st->ms_who = P.ms_who, st->ms_emit = ms_emit, st->ms_reduce = ms_reduce, st->ms_compact = ms_compact;
-		st->n_strings = m, st->n_hits = n, st->n_kept = n_kept, st->n_groups = (int64_t)cw[5], st->n_capped_groups = (int64_t)cw[6], st->n_capped_hits = (int64_t)cw[7];
-		st->n_emitters = ne, st->n_slices = n_slices, st->resident_bytes = resident;
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_count = P.ms_count, st->ms_who = P.ms_who, st->ms_emit = R.ms_emit, st->ms_reduce = R.ms_reduce, st->ms_compact = R.ms_compact;
+		st->n_strings = m, st->n_hits = n, st->n_kept = R.n_kept, st->n_groups = (int64_t)cw[5], st->n_capped_groups = (int64_t)cw[6], st->n_capped_hits = (int64_t)cw[7];
+		st->n_emitters = ne, st->n_slices = n_slices, st->resident_bytes = R.resident;
 	}
+	return ret;
+}
+
+/* ---- unitig: the unambiguous paths of the string graph, spelled (rb3gpu_unitig.h) --------------------------- */
+
+#define RB3_UTG_SLICE   ((int64_t)1 << 26)    // symbols of an emit slice
+#define RB3_UTG_STRINGS ((int64_t)1 << 22)    // members per launch of the emitting walk
+
+int rb3gpu_unitigs(rb3gpu_t *h, int64_t min_len, int64_t max_hits, int pair, rb3gpu_unitig_cb cb, void *ud, rb3gpu_unitig_link_cb lcb, rb3gpu_unitig_stats_t *st)
+{
+	static_assert(sizeof(UtgRec) == sizeof(rb3gpu_unitig_t) && sizeof(UtgRec) == 24 && sizeof(UtgMem) == sizeof(rb3gpu_unitig_member_t) && sizeof(UtgMem) == 16 &&
+			sizeof(UtgLink) == sizeof(rb3gpu_unitig_link_t) && sizeof(UtgLink) == 16, "one layout on both sides");
+	if (st) memset(st, 0, sizeof(*st));
+	if (!h || !cb || min_len < 1 || max_hits < 0) return RB3GPU_EINVAL;
+	if (h->n <= 0 || h->grp == nullptr) return RB3GPU_ESTATE;
+	const int64_t m = h->acc[1];
+	if (m <= 0) return RB3GPU_ESTATE; // (no index has no string)
+	if (m >= ((int64_t)1 << 31)) return RB3GPU_EUNSUP; // (a string is 32 bits of a record)
+	if (pair && (m & 1)) return RB3GPU_EINVAL; // (not both strands of anything)
+	double t0;
+	if (const int e = drv_enter(h, &t0)) return e;
+	const int64_t budget = h->tn.utg_slice > 0 ? h->tn.utg_slice : RB3_UTG_SLICE, per = h->tn.utg_strings > 0 ? h->tn.utg_strings : RB3_UTG_STRINGS;
+	Scratch sc;
+	OvlPlan P;
+	OvlResident R;
+	std::vector<int64_t> vlen((size_t)m);
+	// the stages of rb3gpu_overlap_reduced: the records stay where they are (a host array for the lengths: the plan then makes len32 whatever it finds)
+	if (const int e = ovl_plan(h, sc, min_len, max_hits, vlen.data(), P)) return e;
+	const int64_t n = P.n_hits;
+	if (n > 0)
+		if (const int e = ovl_resident(h, sc, P, max_hits, R)) return e;
+	const IdxView ix = view_of(h);
+	const hipEvent_t e0 = P.e0, e1 = P.e1;
+	const unsigned nbm = (unsigned)((m + 255) / 256), nbn = (unsigned)((n + 255) / 256);
+	unsigned long long *d_c = nullptr, *h_c = nullptr; // [0]: records outside the index, [1]: simple, [2]: asymmetric, [3]: cycles, [4, 7): the tails, [7]: unitigs, [8, 10): members, [10, 12): links, [12]: live, [20, 24): the emitting walk
+	uint32_t *d_dout = nullptr, *d_din = nullptr, *d_next = nullptr, *d_prev = nullptr, *d_flag = nullptr, *d_utail = nullptr, *d_umem = nullptr, *d_mu = nullptr, *d_lflag = nullptr;
+	int32_t *d_oin = nullptr, *d_circ = nullptr;
+	uint4 *d_st[2] = { nullptr, nullptr };
+	uint64_t *d_sym[2] = { nullptr, nullptr };
+	int64_t *d_ulen = nullptr, *d_upos = nullptr, *d_moff = nullptr, *d_soff = nullptr, *d_lpos = nullptr;
+	void *d_tmp = nullptr;
+	size_t tmp_bytes = 0;
+	int64_t resident = R.resident;
+	{
+		const int r = rb3kount_scan(nullptr, &tmp_bytes, nullptr, nullptr, m + 1, h->st);
+		if (r < 0) return scan_err(r);
+	}
+	{
+		const size_t m4 = (size_t)(m + 1) * 4, m8 = (size_t)(m + 1) * 8;
+		const size_t want[17] = { m4, m4, m4, m4, m4, m4, m4, m4, m4, (size_t)m * 16, (size_t)m * 16, m8, m8, m8, m8, tmp_bytes + 256, 512 };
+		void **const where[17] = { (void**)&d_dout, (void**)&d_din, (void**)&d_next, (void**)&d_prev, (void**)&d_oin, (void**)&d_circ, (void**)&d_flag, (void**)&d_utail, (void**)&d_umem,
+				(void**)&d_st[0], (void**)&d_st[1], (void**)&d_sym[0], (void**)&d_sym[1], (void**)&d_ulen, (void**)&d_upos, &d_tmp, (void**)&d_c };
+		for (int i = 0; i < 17; ++i) {
+			if (sc.dev(where[i], want[i]) != hipSuccess) {
+				(void)hipGetLastError();
+				return RB3GPU_ENOMEM;
+			}
+			resident += (int64_t)want[i];
+		}
+	}
+	HIPCHK(sc.pinned(&h_c, 512));
+	memset(h_c, 0, 512);
+	const auto fetch_ctr = [&]() -> hipError_t { // the counters as they are once the stream has run dry
+		const hipError_t e = hipMemcpyAsync(h_c, d_c, 512, hipMemcpyDeviceToHost, h->st);
+		return e != hipSuccess ? e : hipStreamSynchronize(h->st);
+	};
+	double ms_graph = 0, ms_rank = 0, ms_emit = 0;
+	// 1. the graph: degrees, the simple records, the symmetry of the two strands
+	HIPCHK(hipMemsetAsync(d_c, 0, 512, h->st));
+	HIPCHK(hipMemsetAsync(d_dout, 0, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_din, 0, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_next, 0xFF, (size_t)(m + 1) * 4, h->st)); // RB3_UTG_NONE
+	HIPCHK(hipMemsetAsync(d_prev, 0xFF, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_utail, 0xFF, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_oin, 0, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_circ, 0, (size_t)(m + 1) * 4, h->st));
+	HIPCHK(hipMemsetAsync(d_flag, 0, (size_t)(m + 1) * 4, h->st)); // (flag[m] = 0: the entry behind the last string)
+	HIPCHK(hipEventRecord(e0, h->st));
+	if (n > 0) {
+		hipLaunchKernelGGL(k_utg_degree, dim3(nbn), dim3(256), 0, h->st, n, (const OvlRec*)R.d_rec, (const uint32_t*)R.d_keep, m, d_dout, d_din, d_c + 0);
+		hipLaunchKernelGGL(k_utg_simple, dim3(nbn), dim3(256), 0, h->st, n, (const OvlRec*)R.d_rec, (const uint32_t*)R.d_keep, m, (const uint32_t*)d_dout, (const uint32_t*)d_din, d_next, d_prev, d_oin, d_c + 1);
+		if (pair) hipLaunchKernelGGL(k_utg_asym, dim3(nbm), dim3(256), 0, h->st, m, (const uint32_t*)d_next, d_c + 2);
+	}
+	HIPCHK(hipEventRecord(e1, h->st));
+	HIPCHK(fetch_ctr());
+	HIPCHK(hipGetLastError());
+	ms_graph += ev_ms(e0, e1);
+	if (h_c[0] != 0) return RB3GPU_EINTERNAL;
+	const int64_t n_simple = (int64_t)h_c[1], n_asym = (int64_t)h_c[2];
+	const auto fill_stats = [&](int64_t n_unitigs, int64_t n_members, int64_t n_symbols, int64_t n_steps, int64_t n_cycles, int64_t n_links, int64_t n_rounds, int64_t max_members, int64_t n_slices) {
+		if (!st) return;
+		st->ms_total = (now_s() - t0) * 1e3, st->ms_reduce = P.ms_count + P.ms_who + R.ms_emit + R.ms_reduce + R.ms_compact, st->ms_graph = ms_graph, st->ms_rank = ms_rank, st->ms_emit = ms_emit;
+		st->n_strings = m, st->n_kept = R.n_kept, st->n_simple = n_simple, st->n_unitigs = n_unitigs, st->n_members = n_members, st->n_symbols = n_symbols, st->n_steps_emit = n_steps;
+		st->n_cycles = n_cycles, st->n_asym = n_asym, st->n_links = n_links, st->n_rounds = n_rounds, st->max_members = max_members, st->n_slices = n_slices, st->resident_bytes = resident;
+	};
+	if (pair && n_asym > 0) { // nothing is guessed (said by the caller: the ways out are its to name)
+		fill_stats(0, 0, 0, 0, 0, 0, 0, 0, 0);
+		return RB3GPU_EUNSUP;
+	}
+	// 2. list ranking: pointer jumping along prev until no vertex has a pointer, or only the cycles' vertices have and each has seen all of its cycle; those are cut and ranked again
+	int cur = 0;
+	int64_t rounds = 0, live = 0;
+	const auto jump = [&]() -> hipError_t { // one round, and the vertices that still have a pointer after it
+		hipError_t e = hipMemsetAsync(d_c + 12, 0, 8, h->st);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL(k_utg_jump, dim3(nbm), dim3(256), 0, h->st, m, (const uint4*)d_st[cur], (const uint64_t*)d_sym[cur], d_st[cur ^ 1], d_sym[cur ^ 1], d_c + 12);
+		cur ^= 1, ++rounds;
+		if ((e = fetch_ctr()) != hipSuccess) return e;
+		live = (int64_t)h_c[12];
+		return hipGetLastError();
+	};
+	HIPCHK(hipEventRecord(e0, h->st));
+	hipLaunchKernelGGL(k_utg_init, dim3(nbm), dim3(256), 0, h->st, m, (const uint32_t*)d_prev, (const int32_t*)d_oin, (const uint32_t*)P.d_len32, 0, d_st[0], d_sym[0], d_c + 12);
+	HIPCHK(fetch_ctr());
+	HIPCHK(hipGetLastError());
+	live = (int64_t)h_c[12];
+	if (live != n_simple) return RB3GPU_EINTERNAL; // every simple record gave one vertex its prev
+	while (live > 0) {
+		const int64_t before = live;
+		HIPCHK(jump());
+		if (live > before || rounds > 64) return RB3GPU_EINTERNAL;
+		if (live == before && (rounds >= 62 || ((int64_t)1 << rounds) >= live)) break; // a path loses a vertex every round: these are cycles, seen whole
+	}
+	if (live > 0) {
+		HIPCHK(hipMemsetAsync(d_c + 12, 0, 8, h->st));
+		hipLaunchKernelGGL(k_utg_cut, dim3(nbm), dim3(256), 0, h->st, m, (const uint4*)d_st[cur], d_next, d_prev, d_oin, d_circ, d_c + 3);
+		hipLaunchKernelGGL(k_utg_init, dim3(nbm), dim3(256), 0, h->st, m, (const uint32_t*)d_prev, (const int32_t*)d_oin, (const uint32_t*)P.d_len32, 1, d_st[cur], d_sym[cur], d_c + 12);
+		HIPCHK(fetch_ctr());
+		HIPCHK(hipGetLastError());
+		if (h_c[3] == 0 || (int64_t)h_c[12] != live - (int64_t)h_c[3]) return RB3GPU_EINTERNAL; // every cycle has lost the pointer of its head
+		live = (int64_t)h_c[12];
+		while (live > 0) {
+			const int64_t before = live;
+			HIPCHK(jump());
+			if (live >= before || rounds > 128) return RB3GPU_EINTERNAL;
+		}
+	}
+	// 3. the chains: every tail names its chain to its head; the heads that are output, scanned, are the unitigs
+	hipLaunchKernelGGL(k_utg_tails, dim3(nbm), dim3(256), 0, h->st, m, pair ? 1 : 0, (const uint32_t*)d_next, (const uint4*)d_st[cur], (const uint64_t*)d_sym[cur], (const uint32_t*)P.d_len32,
+			(const int32_t*)d_circ, d_flag, d_utail, d_umem, d_ulen, d_c + 4);
+	{
+		size_t tb = tmp_bytes + 256;
+		const int r = rb3kount_scan(d_tmp, &tb, d_flag, d_upos, m + 1, h->st);
+		if (r < 0) return scan_err(r);
+	}
+	int64_t n_u = 0;
+	HIPCHK(hipMemcpyAsync(&n_u, d_upos + m, 8, hipMemcpyDeviceToHost, h->st));
+	HIPCHK(fetch_ctr());
+	HIPCHK(hipGetLastError());
+	if (h_c[6] != 0 || (int64_t)h_c[5] != m || (int64_t)h_c[4] != m - n_simple + (int64_t)h_c[3] || n_u <= 0 || n_u > (int64_t)h_c[4]) {
+		if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] unitigs: %llu tails with %llu members (%llu unsound) for %lld strings, %lld simple records and %llu cycles\n", h_c[4], h_c[5], h_c[6], (long long)m, (long long)n_simple, h_c[3]);
+		return RB3GPU_EINTERNAL; // every vertex belongs to exactly one chain
+	}
+	UtgRec *d_U = nullptr, *h_U = nullptr;
+	HIPCHK(sc.regrow(&d_U, &h_U, (size_t)n_u * sizeof(UtgRec)));
+	HIPCHK(sc.dev(&d_moff, (size_t)(n_u + 1) * 8));
+	HIPCHK(sc.dev(&d_soff, (size_t)(n_u + 1) * 8));
+	resident += n_u * (int64_t)(sizeof(UtgRec) + 16) + 16;
+	hipLaunchKernelGGL(k_utg_table, dim3(nbm), dim3(256), 0, h->st, m, (const uint32_t*)d_flag, (const int64_t*)d_upos, (const uint32_t*)d_utail, (const uint32_t*)d_umem, (const int64_t*)d_ulen,
+			(const int32_t*)d_circ, d_U, n_u, d_c + 7);
+	HIPCHK(hipMemcpyAsync(h_U, d_U, (size_t)n_u * sizeof(UtgRec), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(fetch_ctr());
+	HIPCHK(hipGetLastError());
+	if ((int64_t)h_c[7] != n_u) return RB3GPU_EINTERNAL;
+	std::vector<int64_t> moff((size_t)n_u + 1, 0), soff((size_t)n_u + 1, 0);
+	int64_t max_members = 0, n_cycles = 0;
+	for (int64_t u = 0; u < n_u; ++u) {
+		const UtgRec &r = h_U[u];
+		if (r.members < 1 || r.len < 0 || (u > 0 && r.head <= h_U[u - 1].head)) return RB3GPU_EINTERNAL;
+		moff[(size_t)u + 1] = moff[(size_t)u] + r.members, soff[(size_t)u + 1] = soff[(size_t)u] + r.len;
+		max_members = std::max<int64_t>(max_members, r.members), n_cycles += r.circ != 0;
+	}
+	const int64_t n_mem = moff[(size_t)n_u], n_sym = soff[(size_t)n_u];
+	if (n_mem > m || (!pair && n_mem != m)) return RB3GPU_EINTERNAL;
+	UtgMem *d_M = nullptr, *h_M = nullptr;
+	HIPCHK(sc.regrow(&d_M, &h_M, (size_t)n_mem * sizeof(UtgMem)));
+	HIPCHK(sc.dev(&d_mu, (size_t)n_mem * 4));
+	resident += n_mem * (int64_t)(sizeof(UtgMem) + 4);
+	HIPCHK(hipMemsetAsync(d_mu, 0xFF, (size_t)n_mem * 4, h->st)); // (a slot no member takes names no unitig)
+	HIPCHK(hipMemsetAsync(d_M, 0xFF, (size_t)n_mem * sizeof(UtgMem), h->st));
+	HIPCHK(hipMemcpyAsync(d_moff, moff.data(), (size_t)(n_u + 1) * 8, hipMemcpyHostToDevice, h->st));
+	HIPCHK(hipMemcpyAsync(d_soff, soff.data(), (size_t)(n_u + 1) * 8, hipMemcpyHostToDevice, h->st));
+	hipLaunchKernelGGL(k_utg_members, dim3(nbm), dim3(256), 0, h->st, m, (const uint4*)d_st[cur], (const uint64_t*)d_sym[cur], (const int32_t*)d_oin, (const uint32_t*)d_flag, (const int64_t*)d_upos,
+			(const int64_t*)d_moff, n_u, d_M, d_mu, d_c + 8);
+	HIPCHK(hipEventRecord(e1, h->st));
+	HIPCHK(hipMemcpyAsync(h_M, d_M, (size_t)n_mem * sizeof(UtgMem), hipMemcpyDeviceToHost, h->st));
+	HIPCHK(fetch_ctr());
+	HIPCHK(hipGetLastError());
+	ms_rank += ev_ms(e0, e1);
+	if ((int64_t)h_c[8] != n_mem || h_c[9] != 0) return RB3GPU_EINTERNAL; // the members output are the scan's total
+	// 4. the links: the kept records that are not simple, their ends as unitigs, in their order
+	int64_t n_links = 0;
+	UtgLink *d_L = nullptr, *h_L = nullptr;
+	if (n > 0) {
+		HIPCHK(sc.dev(&d_lflag, (size_t)(n + 1) * 4));
+		HIPCHK(sc.dev(&d_lpos, (size_t)(n + 1) * 8));
+		resident += (n + 1) * 12;
+		HIPCHK(hipMemsetAsync(d_lflag, 0, (size_t)(n + 1) * 4, h->st));
+		HIPCHK(hipEventRecord(e0, h->st));
+		hipLaunchKernelGGL(k_utg_linkflag, dim3(nbn), dim3(256), 0, h->st, n, (const OvlRec*)R.d_rec, (const uint32_t*)R.d_keep, m, (const uint32_t*)d_dout, (const uint32_t*)d_din, pair ? 1 : 0, d_lflag);
+		{
+			size_t tb = R.tmp_bytes + 256;
+			const int r = rb3kount_scan(R.d_tmp, &tb, d_lflag, d_lpos, n + 1, h->st);
+			if (r < 0) return scan_err(r);
+		}
+		HIPCHK(hipMemcpyAsync(&n_links, d_lpos + n, 8, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(hipStreamSynchronize(h->st));
+		if (n_links < 0 || n_links > R.n_kept - n_simple) return RB3GPU_EINTERNAL;
+		if (n_links > 0) {
+			HIPCHK(sc.regrow(&d_L, &h_L, (size_t)n_links * sizeof(UtgLink)));
+			resident += n_links * (int64_t)sizeof(UtgLink);
+			hipLaunchKernelGGL(k_utg_links, dim3(nbn), dim3(256), 0, h->st, n, (const OvlRec*)R.d_rec, (const uint32_t*)d_lflag, (const int64_t*)d_lpos, (const uint32_t*)d_next, (const uint32_t*)d_prev,
+					(const uint4*)d_st[cur], (const uint32_t*)d_flag, (const int64_t*)d_upos, m, pair ? 1 : 0, d_L, n_links, d_c + 10);
+			HIPCHK(hipMemcpyAsync(h_L, d_L, (size_t)n_links * sizeof(UtgLink), hipMemcpyDeviceToHost, h->st));
+		}
+		HIPCHK(hipEventRecord(e1, h->st));
+		HIPCHK(fetch_ctr());
+		HIPCHK(hipGetLastError());
+		ms_graph += ev_ms(e0, e1);
+		if ((int64_t)h_c[10] != n_links || h_c[11] != 0) return RB3GPU_EINTERNAL; // a link goes from a tail to a head, and both are on unitigs
+	}
+	// 5. emit: slices of consecutive unitigs whose lengths sum to at most the budget, one with more alone; launches of at most `per` members
+	uint8_t *d_out = nullptr, *h_out = nullptr;
+	int64_t out_cap = 0, n_slices = 0, n_steps = 0;
+	std::vector<int64_t> off;
+	int ret = 0;
+	for (int64_t u0 = 0; u0 < n_u && ret == 0; ++n_slices) {
+		int64_t u1 = u0 + 1;
+		while (u1 < n_u && soff[(size_t)u1 + 1] - soff[(size_t)u0] <= budget) ++u1;
+		const int64_t tot = soff[(size_t)u1] - soff[(size_t)u0];
+		if (tot > out_cap) { // (grows to the largest slice: the budget, or the one unitig that exceeds it)
+			out_cap = 0;
+			const int64_t oc = std::max(tot, std::min(budget, (int64_t)1 << 16));
+			HIPCHK(sc.regrow(&d_out, &h_out, (size_t)oc));
+			out_cap = oc;
+		}
+		HIPCHK(hipMemsetAsync(d_c + 20, 0, 32, h->st));
+		HIPCHK(hipEventRecord(e0, h->st));
+		for (int64_t i0 = moff[(size_t)u0]; i0 < moff[(size_t)u1]; i0 += per) {
+			const int64_t i1 = std::min(moff[(size_t)u1], i0 + per), nb = std::min<int64_t>(((i1 - i0) * 8 + 255) / 256, 4096);
+			HIPCHK(hipMemsetAsync(d_c + 20, 0, 8, h->st));
+			hipLaunchKernelGGL(k_utg_emit, dim3((unsigned)nb), dim3(256), 0, h->st, ix, (const UtgMem*)d_M, (const uint32_t*)d_mu, (const int64_t*)d_soff, (const uint32_t*)P.d_len32, n_u, i0, i1,
+					soff[(size_t)u0], d_out, tot, d_c + 20);
+		}
+		HIPCHK(hipEventRecord(e1, h->st));
+		if (tot > 0) HIPCHK(hipMemcpyAsync(h_out, d_out, (size_t)tot, hipMemcpyDeviceToHost, h->st));
+		HIPCHK(fetch_ctr());
+		HIPCHK(hipGetLastError());
+		ms_emit += ev_ms(e0, e1);
+		if ((int64_t)h_c[21] != tot || h_c[22] != 0 || h_c[23] != 0) { // the symbols written are the sum of the lengths and the steps walked, none before the sentinel, none outside the slice
+			if (h->opt.verbose >= 1) fprintf(stderr, "[E::rb3gpu] unitigs: a slice of %lld symbols took %llu steps, %llu walks met their sentinel, %llu symbols fell outside\n", (long long)tot, h_c[21], h_c[22], h_c[23]);
+			return RB3GPU_EINTERNAL;
+		}
+		n_steps += (int64_t)h_c[21];
+		off.resize((size_t)(u1 - u0) + 1);
+		for (int64_t u = u0; u <= u1; ++u) off[(size_t)(u - u0)] = soff[(size_t)u] - soff[(size_t)u0];
+		ret = cb(ud, u0, u1 - u0, (const rb3gpu_unitig_t*)(h_U + u0), (const rb3gpu_unitig_member_t*)(h_M + moff[(size_t)u0]), off.data(), h_out);
+		u0 = u1;
+	}
+	if (ret == 0 && lcb != nullptr && n_links > 0) ret = lcb(ud, n_links, (const rb3gpu_unitig_link_t*)h_L);
+	fill_stats(n_u, n_mem, n_sym, n_steps, n_cycles, n_links, rounds, max_members, n_slices);
 	return ret;
 }
 

@@ -204,6 +204,23 @@ class ReduceStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+UNITIG_REC = np.dtype([("head", "<i4"), ("tail", "<i4"), ("members", "<i4"), ("circ", "<i4"), ("len", "<i8")])  # rb3gpu_unitig_t
+UNITIG_MEMBER = np.dtype([("row", "<i4"), ("o_in", "<i4"), ("off", "<i8")])  # rb3gpu_unitig_member_t
+UNITIG_LINK = np.dtype([("from", "<i4"), ("to", "<i4"), ("len", "<i4"), ("from_rev", "u1"), ("to_rev", "u1"), ("pad", "u1", (2,))])  # rb3gpu_unitig_link_t
+UNITIG_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
+UNITIG_LINK_F = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
+
+
+class UnitigStats(ctypes.Structure):
+    _fields_ = [("ms_total", ctypes.c_double), ("ms_reduce", ctypes.c_double), ("ms_graph", ctypes.c_double), ("ms_rank", ctypes.c_double), ("ms_emit", ctypes.c_double),
+                ("n_strings", ctypes.c_int64), ("n_kept", ctypes.c_int64), ("n_simple", ctypes.c_int64), ("n_unitigs", ctypes.c_int64), ("n_members", ctypes.c_int64),
+                ("n_symbols", ctypes.c_int64), ("n_steps_emit", ctypes.c_int64), ("n_cycles", ctypes.c_int64), ("n_asym", ctypes.c_int64), ("n_links", ctypes.c_int64),
+                ("n_rounds", ctypes.c_int64), ("max_members", ctypes.c_int64), ("n_slices", ctypes.c_int64), ("resident_bytes", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FetchStats(ctypes.Structure):
     _fields_ = [("ms_total", ctypes.c_double), ("ms_table", ctypes.c_double), ("ms_plan", ctypes.c_double), ("ms_walk", ctypes.c_double), ("n_regions", ctypes.c_int64),
                 ("n_symbols", ctypes.c_int64), ("n_walkers", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_steps", ctypes.c_int64), ("max_walk_steps", ctypes.c_int64),
@@ -347,6 +364,7 @@ SYMBOLS = {
     "rb3gpu_dedup": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DedupStats)]),
     "rb3gpu_overlap": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, OVERLAP_F, ctypes.c_void_p, ctypes.POINTER(OverlapStats)]),
     "rb3gpu_overlap_reduced": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, OVERLAP_F, ctypes.c_void_p, ctypes.POINTER(ReduceStats)]),
+    "rb3gpu_unitigs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, UNITIG_F, ctypes.c_void_p, UNITIG_LINK_F, ctypes.POINTER(UnitigStats)]),
     "rb3gpu_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), FETCH_F, ctypes.c_void_p, ctypes.POINTER(FetchStats)]),
 }
 
@@ -1110,6 +1128,36 @@ class Rb3Gpu:
             stats.update(st.as_dict())
         rec = np.concatenate(got) if got else np.zeros(0, dtype=OVERLAP_REC)
         return (rec, ln[:m]) if lengths else rec
+
+    def unitigs(self, min_len, max_hits=0, pair=False, links=False, stats=None):
+        """rb3gpu_unitigs: the unambiguous paths of the string graph of the irreducible overlaps (those of overlap(reduce=True) for the same min_len and max_hits), each
+        spelled: (unitigs, members, sequences) -- a structured array (UNITIG_REC: head, tail, members, circ, len) by ascending head, one (UNITIG_MEMBER: row, o_in, off)
+        of their members, unitig after unitig by rank, and a list of uint8 arrays of nt6 codes in text order.  links=True: a fourth item, the structured array
+        (UNITIG_LINK) of the kept overlaps between unitigs.  pair=True: the index holds both strands in input order and one of every two mirror chains is returned; a
+        graph that is not strand-symmetric raises with RB3GPU_EUNSUP (stats still receives n_asym).  stats: a dict that receives rb3gpu_unitig_stats_t"""
+        utg, mem, seqs, lnk = [], [], [], []
+
+        def cb(_ud, _u0, n, u, mb, off, symbols):
+            n = int(n)
+            us = np.frombuffer(ctypes.string_at(u, n * UNITIG_REC.itemsize), dtype=UNITIG_REC)
+            o = np.frombuffer(ctypes.string_at(off, (n + 1) * 8), dtype=np.int64)
+            sym = np.frombuffer(ctypes.string_at(symbols, int(o[n])), dtype=np.uint8)
+            utg.append(us)
+            mem.append(np.frombuffer(ctypes.string_at(mb, int(us["members"].sum()) * UNITIG_MEMBER.itemsize), dtype=UNITIG_MEMBER))
+            seqs.extend(sym[int(o[i]):int(o[i + 1])].copy() for i in range(n))
+            return 0
+
+        def lcb(_ud, n, ls):
+            lnk.append(np.frombuffer(ctypes.string_at(ls, int(n) * UNITIG_LINK.itemsize), dtype=UNITIG_LINK))
+            return 0
+        st = UnitigStats()
+        code = self._lib.rb3gpu_unitigs(self._h, int(min_len), int(max_hits), 1 if pair else 0, UNITIG_F(cb), None, UNITIG_LINK_F(lcb) if links else UNITIG_LINK_F(),
+                                        ctypes.byref(st))
+        if stats is not None:
+            stats.update(st.as_dict())
+        self._chk(code, "rb3gpu_unitigs")
+        out = (np.concatenate(utg) if utg else np.zeros(0, dtype=UNITIG_REC), np.concatenate(mem) if mem else np.zeros(0, dtype=UNITIG_MEMBER), seqs)
+        return out + (np.concatenate(lnk) if lnk else np.zeros(0, dtype=UNITIG_LINK),) if links else out
 
     def fetch(self, rows, begs, ends, stats=False):
         """rb3gpu_fetch: the symbols [begs[i], ends[i]) of string rows[i] (0-based, end exclusive; string r is what retrieve([r]) spells), read through the
